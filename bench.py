@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the hot path on synthetic Gaussian clouds (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--config C3]
-  (N > 1 without WORLD_SIZE in the environment: re-executes itself under torch.distributed.run, one rank per GPU over RCCL)
+  python bench.py --gpus N --steps K --warmup W [--config C3] [--dump-outputs DIR] [--full]
+  (N > 1 without WORLD_SIZE in the environment: runs itself under torch.distributed.run, one rank per GPU over RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the result line (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, the configuration).  `--full` adds every other leg of the record below (per-step medians, stage
+table and roofline, the other learning rates / views / configs, densification, drop-in, kNN, CPU baseline).  `--dump-outputs DIR`
+writes what the last timed step computed to DIR/<name>.npy (see dump_outputs).
 
 A "step" is one full training iteration of GaussianMapper::trainForOneIteration (src/gaussian_mapper.cpp:614-774) on one
 keyframe per GPU: render (HIP rasterizer forward) -> masked L1 + 0.2*(1-SSIM) -> backward (HIP rasterizer backward) ->
@@ -10,7 +15,8 @@ densification statistics -> [gradient exchange when N>1] -> Adam.  Inputs are re
 N=1 workload = the configuration BASELINE.json's metric is quoted on: 2M Gaussians at 1920x1080 (config C3).
 
 Protocol:
-  * `value` / `ms_per_step`: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize (driver contract).
+  * `value` / `ms_per_step`: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize (driver contract);
+    under --full the timed steps also record HIP events around the backward blend (`roofline`), as every run did before.
   * The workload is STATIONARY: the timed legs run with every learning rate multiplied by 0 (`config.learning_rates`) -- the
     same kernels, the same bytes, the Adam moments update, the parameters do not move.  With the training learning rates
     the synthetic scene inflates by ~1 %/step (fitting one noisy view with Adam's eps 1e-15 drags opacities and scales
@@ -37,6 +43,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+PARAM_NAMES = ("xyz", "features", "opacity", "scaling", "rotation")   # the model's five leaves, in the optimizer's group order
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
 # committed counter profiles of the same build (tools/gpu_pmc.sh, tools/gpu_sq.sh): newest set first (names sort by round + tag)
 import glob
@@ -89,7 +96,7 @@ def config_leg(config, seed, steps=40, warmup=10, extra=()):
     kNN / densify / drop-in legs), reduced to its step time, the rasterizer alone, its own roofline entry and the blend kernels'
     VALU issue utilisation measured there."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", config, "--seed", str(seed), "--steps", str(steps), "--warmup", str(warmup),
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", config, "--seed", str(seed), "--steps", str(steps), "--warmup", str(warmup),
            "--median-steps", str(steps), "--no-cpu-baseline", "--no-knn-leg", "--densify-leg-steps", "0", "--dropin-steps", "0", "--no-config-legs"]
     cmd += list(extra)
     t0 = time.time()
@@ -183,7 +190,8 @@ def algorithmic_bytes(P, V, R, Npix, T, K=16, M=16, tile_passes=2, depth_passes=
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher: become `python -m torch.distributed.run ... bench.py ...`."""
+    """`python bench.py --gpus N` with N > 1 and no launcher: run `python -m torch.distributed.run ... bench.py ...` as a child
+    process and exit with its status."""
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -191,7 +199,8 @@ def self_launch(args):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 def cpu_train_step_baseline(scene, args, W, H, quick=False, want_inputs=False):
@@ -245,6 +254,8 @@ def dropin_unfused_leg(torch, dev, cl, kf, fovx, fovy, H, W, gt, steps, stationa
     path = os.path.join(ROOT, "oracle", "_ref", name)
     if not os.path.exists(path):
         return {"skipped": f"oracle/_ref/{name} was never built (python __graft_entry__.py where /root/reference exists)"}
+    from oracle import build_ref
+    build_ref.preload("hip")        # (this tree's lib/libcuda_rasterizer.so + libsimple_knn.so, whatever the prebuilt library's run path says)
     torch.ops.load_library(path)
     rops = torch.ops.photoslam_reference_host_fl if fused_loss else torch.ops.photoslam_reference_host
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -443,6 +454,32 @@ def mapper_loop_leg(torch, dev, ops, scene, steps, seed, sh_adam_window, morton_
             "note": "one HIP event per iteration; an iteration's time includes the maintenance calls that follow its optimizer step"}
 
 
+DUMP_ROWS = 32768                 # --dump-outputs: rows kept of every per-Gaussian array (one fixed, seeded sample)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, P):
+    """--dump-outputs: `arrays` ({name: tensor}, what the last timed step left to its caller) as out_dir/<name>.npy in float32
+    (float64 stays float64).  Arrays with one row per Gaussian keep the same DUMP_ROWS rows, drawn with a fixed seed from
+    range(P) and written as sample_rows.npy, so that two builds of the project can be compared output for output."""
+    import torch
+    rows = np.sort(np.random.default_rng(0).choice(P, size=min(P, DUMP_ROWS), replace=False))
+    idx = {}
+    out = {"sample_rows": rows.astype(np.float64)}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.dim() >= 1 and t.shape[0] == P:
+            t = t.index_select(0, idx.setdefault(t.device, torch.from_numpy(rows).to(t.device)))
+        a = t.cpu().numpy()
+        out[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -501,6 +538,13 @@ def main():
                     help="skip the `configs` block (the other single-GPU BASELINE configs -- C2, a C4 view, a C5 view -- each in a child process)")
     ap.add_argument("--no-sq-probe", dest="sq_probe", action="store_false",
                     help="do not measure the blend kernels' VALU issue with a rocprofv3 counter pass (the committed profile is cited instead)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run every other leg of the record: per-step medians, stage table and roofline (with "
+                         "the rocprofv3 counter pass), changing views, training learning rates, densification, drop-in, kNN, the other "
+                         "configs, the CPU baseline.  Without it a run only sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, parameters, Adam moments, densification "
+                         "statistics; per-Gaussian arrays as a fixed seeded sample of rows) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.cpu_baseline_only:
         import __graft_entry__ as entry
@@ -671,6 +715,7 @@ def main():
         loss_state["n"] += 1
 
     kf_now = [kf]   # (the changing-views leg swaps the keyframe between steps)
+    last = {}       # what the latest step handed back to its caller (--dump-outputs)
 
     def one_step():
         kf = kf_now[0]
@@ -678,6 +723,7 @@ def main():
             # one call: render + backward, the exchange (RCCL, issued by the C++ host), the optimizer
             loss = ops.trainer_train_one_iteration(handle, kf.world_view_transform_, kf.full_proj_transform_, kf.camera_center_,
                                                    fovx, fovy, H, W, gt, mask)
+            last["loss"] = loss
             read_loss_deferred(loss)
         elif ops is not None:
             loss = ops.trainer_render_and_backward(handle, kf.world_view_transform_, kf.full_proj_transform_,
@@ -710,13 +756,34 @@ def main():
                 ops.trainer_finish_end(handle)
             else:
                 ops.trainer_finish(handle)    # statistics + Adam
+            last["loss"] = loss
             read_loss_deferred(loss)
         elif args.raster_only:
             img, vsp, vis, radii = GaussianRenderer.render(kf, H, W, g, pipe, bg)
             img.backward(gt)
+            last.update(image=img, radii=radii, visible=vis,
+                        **{"grad_" + n: p.grad for n, p in zip(PARAM_NAMES, g.params_raw()) if p.grad is not None})
             g.optimizer_.zero_grad(set_to_none=True)
         else:
-            ts.trainForOneIteration(kf, gt, mask, sync_loss=True)
+            last["loss"] = ts.trainForOneIteration(kf, gt, mask, sync_loss=True)
+
+    def step_outputs():
+        """--dump-outputs: the last timed step's result as its caller sees it -- the loss, and the model it left behind
+        (parameters, both Adam moments, densification statistics); the rasterizer-only step: image, radii, gradients"""
+        arrays = {k: v for k, v in last.items()}
+        if args.raster_only:
+            return arrays
+        if ops is not None:
+            params, moments, stats = ops.trainer_params(handle), ops.trainer_moments(handle), ops.trainer_stats(handle)
+            avg, avg_sq = moments[:len(params)], moments[len(params):]
+        else:
+            params = g.params()
+            avg, avg_sq = zip(*(g.optimizer_.moments(p) for p in params))
+            stats = (g.xyz_gradient_accum_, g.denom_, g.max_radii2D_)
+        for n, p, m1, m2 in zip(PARAM_NAMES, params, avg, avg_sq):
+            arrays.update({n: p, "exp_avg_" + n: m1, "exp_avg_sq_" + n: m2})
+        arrays.update(zip(("xyz_gradient_accum", "denom", "max_radii2D"), stats))
+        return arrays
 
     def barrier():
         if world > 1:
@@ -792,16 +859,88 @@ def main():
     gc.disable()
     for _ in range(priming + args.warmup):
         one_step()
-    # Timed region: HIP events only around the backward blend, the dominant kernel (gsr_profile_enable(2)): every event
-    # record is a ~5 us bubble in the stream, and eleven of them per step cost 2 % of the step they are meant to measure.
-    capi.profile_enable(lib, 2)
-    capi.host_wait_stats(lib)                       # (reset)
-    elapsed, dom_ms = timed(args.steps, read_dominant=True)
+    # Timed region (--full): HIP events only around the backward blend, the dominant kernel (gsr_profile_enable(2)): every event
+    # record is a ~5 us bubble in the stream, and eleven of them per step cost 2 % of the step they are meant to measure.  A plain
+    # run records none.
+    if args.full:
+        capi.profile_enable(lib, 2)
+        capi.host_wait_stats(lib)                   # (reset)
+    elapsed, dom_ms = timed(args.steps, read_dominant=args.full)
     gc.enable()
     # how long the host was blocked in the forward pass's one synchronisation: a host that runs ahead of the device waits there
     # for most of a step; near zero = the device waits for the host (include/gsr.h: gsr_host_wait_stats)
-    host_wait_us, host_waits = capi.host_wait_stats(lib)
+    host_wait_us, host_waits = capi.host_wait_stats(lib) if args.full else (0.0, 0)
     capi.profile_enable(lib, 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(), P)
+
+    stationary_note = ("0 (stationary workload: every kernel runs and the Adam moments update, the parameters do not move)"
+                       if stationary else "training (GaussianOptimizationParams defaults; the synthetic scene drifts)")
+    fused_sh_adam = not dp and not args.raster_only   # both hosts fuse the SH Adam step into backward at one rank
+    lazy_window = args.sh_adam_window if fused_sh_adam and args.sh_adam_window >= 2 else 0
+    tile_first = bool(lib.gsr_binning_tile_first(0, P, W, H))   # the binning arrangement gsr_forward takes at this size
+
+    def result_line(V=None, R=None):
+        """the record's head: the timed steps and the configuration they ran (V, R: the view's statistics, --full only)"""
+        config = {"workload": f"{args.config}: {cfg['note']}", "gaussians": P, "width": W, "height": H}
+        if V is not None:
+            config.update(visible=V, instances=R, instances_per_visible=round(R / max(V, 1), 2))
+        config.update({
+            "keyframes_per_step": world, "sh_degree": 3,
+            "parallelism": "single GPU" if not dp else
+                           (f"dp{world} (one keyframe per GPU; ONE all-gather of 3 floats/Gaussian + the camera centre, issued "
+                            "behind preprocess_bwd on a second stream, + ONE all-reduce (sum) of 11 floats/Gaussian; SH "
+                            "gradient rebuilt and stepped lazily per rank; densification statistics accumulate per rank)") if factored else
+                           f"dp{world} (one keyframe per GPU, all-reduce of 59 floats/Gaussian)",
+            "raster_only": bool(args.raster_only), "densify_interval": args.densify_interval,
+            "learning_rates": stationary_note,
+            "cull_empty_tiles": os.environ.get("GSR_CULL_EMPTY_TILES", "0") == "1",   # (include/gsr.h: same image and gradients)
+            "binning": "tile-first" if tile_first else "depth-first",   # (include/gsr.h: GSR_BINNING_*; the same lists either way)
+            "sh_adam_fused_into_backward": fused_sh_adam,
+            "sh_adam_lazy_window": lazy_window, "scene_index_order": args.scene_order,
+            "geometry_adam_fused_into_backward": bool(fused_sh_adam and not args.no_fused_geom_adam),
+            "gaussians_after": int(g.xyz_.shape[0]) if ops is None else int(ops.trainer_params(handle)[0].shape[0]),
+            "host": "libtorch-c++ (photo-slam_amd/host)" if ops is not None else "python mirror"})
+        return {
+            "metric": "train iters/s (render + L1/SSIM loss + backward + Adam), 2M Gaussians @1080p"
+            if args.config == "C3" else f"train iters/s, config {args.config}",
+            "value": round(world * args.steps / elapsed, 3),
+            "unit": "iters/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "priming_steps_before_warmup": priming,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": config}
+
+    def rccl_record():
+        r = {"ranks": dist.get_world_size(), "backend": dist.get_backend(),
+             "collectives_issued_by": "python (trainer.py classes)" if (ops is None or py_exchange) else
+                                      "the C++ host (host/src/keyframe_batch_exchange.cpp on c10d::ProcessGroup)",
+             "NCCL_ALGO": os.environ.get("NCCL_ALGO", "default"), "NCCL_PROTO": os.environ.get("NCCL_PROTO", "default"),
+             "exchange": "view-factored" if factored else "all-reduce", "exchange_form": exchange_form}
+        if exchange_form:
+            r["packed_form_visible_counts_over"] = counts_over
+        return r
+
+    def emit(out):
+        if dp:
+            dist.destroy_process_group()
+        # RCCL writes its version banner to C stdout, which is block-buffered on a pipe and would otherwise land AFTER the
+        # result at exit: drain it first, so that the JSON line is the last line of the output
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+
+    if not args.full:
+        out = None
+        if rank == 0:
+            out = result_line()
+            if dp:
+                out["preflight"] = preflight
+                out["rccl"] = rccl_record()
+        emit(out)
+        return
 
     # ---- per-step times from HIP events on the stream: 20 warm-up + median of >= 100 (SURVEY.md 8d)
     n_med = max(args.median_steps, 0)
@@ -1061,10 +1200,6 @@ def main():
 
     T = ((W + 15) // 16) * ((H + 15) // 16)
     tile_bits = int(np.ceil(np.log2(max(T, 2))))
-    fused_sh_adam = not dp and not args.raster_only   # both hosts fuse the SH Adam step into backward at one rank
-    lazy_window = args.sh_adam_window if fused_sh_adam and args.sh_adam_window >= 2 else 0
-    from photo_slam_amd import capi as _capi
-    tile_first = bool(_capi.load().gsr_binning_tile_first(0, P, W, H))   # the binning arrangement gsr_forward takes at this size
     ab = algorithmic_bytes(P, V, R, W * H, T, tile_passes=(tile_bits + 7) // 8, fused_sh_adam=fused_sh_adam, lazy_window=lazy_window,
                            fused_geom_adam=fused_sh_adam and not args.no_fused_geom_adam, tile_first=tile_first)
     stages = {}
@@ -1087,39 +1222,11 @@ def main():
         stages[dom] = dict(ms=round(avg, 4), bytes=int(ab[dom]), GBps=round(ab[dom] / (avg * 1e-3) / 1e9, 1),
                            timed_region=True)
 
+    out = None
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        lr_note = ("0 (stationary workload: every kernel runs and the Adam moments update, the parameters do not move)"
-                   if stationary else "training (GaussianOptimizationParams defaults; the synthetic scene drifts)")
-        out = {
-            "metric": "train iters/s (render + L1/SSIM loss + backward + Adam), 2M Gaussians @1080p"
-            if args.config == "C3" else f"train iters/s, config {args.config}",
-            "value": round(world * args.steps / elapsed, 3),
-            "unit": "iters/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "priming_steps_before_warmup": priming,
-            "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.config}: {cfg['note']}", "gaussians": P, "width": W, "height": H,
-                       "visible": V, "instances": R, "instances_per_visible": round(R / max(V, 1), 2),
-                       "keyframes_per_step": world, "sh_degree": 3,
-                       "parallelism": "single GPU" if not dp else
-                                      (f"dp{world} (one keyframe per GPU; ONE all-gather of 3 floats/Gaussian + the camera centre, issued "
-                                       "behind preprocess_bwd on a second stream, + ONE all-reduce (sum) of 11 floats/Gaussian; SH "
-                                       "gradient rebuilt and stepped lazily per rank; densification statistics accumulate per rank)") if factored else
-                                      f"dp{world} (one keyframe per GPU, all-reduce of 59 floats/Gaussian)",
-                       "raster_only": bool(args.raster_only), "densify_interval": args.densify_interval,
-                       "learning_rates": lr_note,
-                       "cull_empty_tiles": os.environ.get("GSR_CULL_EMPTY_TILES", "0") == "1",   # (include/gsr.h: same image and gradients)
-                       "binning": "tile-first" if tile_first else "depth-first",   # (include/gsr.h: GSR_BINNING_*; the same lists either way)
-                       "sh_adam_fused_into_backward": fused_sh_adam,
-                       "sh_adam_lazy_window": lazy_window, "scene_index_order": args.scene_order,
-                       "geometry_adam_fused_into_backward": bool(fused_sh_adam and not args.no_fused_geom_adam),
-                       "gaussians_after": int(g.xyz_.shape[0]) if ops is None else int(ops.trainer_params(handle)[0].shape[0]),
-                       "host": "libtorch-c++ (photo-slam_amd/host)" if ops is not None else "python mirror"},
-            "mpix_per_s": round(world * W * H / (raster_ms * 1e-3) / 1e6, 1) if raster_ms > 0 else None,
-            "raster_fwd_bwd_ms": round(raster_ms, 4),
-        }
+        out = result_line(V, R)
+        out["mpix_per_s"] = round(world * W * H / (raster_ms * 1e-3) / 1e6, 1) if raster_ms > 0 else None
+        out["raster_fwd_bwd_ms"] = round(raster_ms, 4)
         if unfused_ms:
             # rasterizer stages without optimizer work (SH Adam as a separate pass): medians of 12 further steps
             ab_u = algorithmic_bytes(P, V, R, W * H, T, tile_passes=(tile_bits + 7) // 8, fused_sh_adam=False, tile_first=tile_first)
@@ -1177,13 +1284,7 @@ def main():
             out["per_rank"] = per_rank
             out["replicas_identical"] = replicas_identical
             out["replica_parameter_hash_rank0"] = param_hash
-            out["rccl"] = {"ranks": dist.get_world_size(), "backend": dist.get_backend(),
-                           "collectives_issued_by": "python (trainer.py classes)" if (ops is None or py_exchange) else
-                                                    "the C++ host (host/src/keyframe_batch_exchange.cpp on c10d::ProcessGroup)",
-                           "NCCL_ALGO": os.environ.get("NCCL_ALGO", "default"), "NCCL_PROTO": os.environ.get("NCCL_PROTO", "default"),
-                           "exchange": "view-factored" if factored else "all-reduce", "exchange_form": exchange_form}
-            if exchange_form:
-                out["rccl"]["packed_form_visible_counts_over"] = counts_over
+            out["rccl"] = rccl_record()
         traffic = traffic_src = None
         # HBM bytes per launch from rocprofv3 TCC counters (separate --pmc passes, tools/gpu_pmc.sh), corrected as
         # MI355X_MICROARCH.md prescribes for gfx950: bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024.  Measured for C3 only, on the
@@ -1290,14 +1391,7 @@ def main():
                            f"({main['loss_ops']}) / Adam; median {main['s_per_iteration_median']} s per iteration; C1 in full "
                            f"({base['C1']['iterations']} iterations) under `runs`"),
                 "runs": base}
-    if dp:
-        dist.destroy_process_group()
-    # RCCL writes its version banner to C stdout, which is block-buffered on a pipe and would otherwise land AFTER the
-    # result at exit: drain it first, so that the JSON line is the last line of the output
-    import ctypes
-    ctypes.CDLL(None).fflush(None)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@ CUDA / cooperative-groups / CUB / glm shims in oracle/ref_shim/ (our code: a fib
 published semantics of the two CUB calls and of the glm operators the sources use).
 
 TEST INFRASTRUCTURE ONLY.  It exists to PIN the CPU oracle (oracle/gsr_oracle.c) and, through committed fixtures
-(tests/golden/reference_small.npz, made by tests/golden/make_reference_golden.py), the HIP kernels against the
+(tests/golden/reference_small.*.npz, made by tests/golden/make_reference_golden.py), the HIP kernels against the
 reference's own code.  Nothing from /root/reference is copied into the repository: the sources are read where they lie;
 the only rewrite is the kernel-launch syntax `k<<<g, b>>>(args)` -> `CUDAEMU_LAUNCH((k), g, b, args)`, done on the fly
 into oracle/_ref/gen/ (git-ignored).  The reference tree is absent on the GPU boxes: there only the built .so or the
@@ -174,6 +174,43 @@ def build_densify(force=False):
     return dict(MODEL_OUT)
 
 
+def _origin_rpath(d):
+    """-rpath to this repository's library directory `d`, relative to oracle/_ref/ ($ORIGIN): the prebuilt binaries travel to
+    machines where the checkout lies elsewhere (the GPU boxes) and must find the libraries built there"""
+    return "-Wl,-rpath,$ORIGIN/" + os.path.relpath(d, OUT_DIR)
+
+
+def _build_host():
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "photo-slam_amd", "host"))
+    import build_host
+    return build_host
+
+
+def boundary_libraries(kind):
+    """This tree's libraries that the prebuilt oracle/_ref binaries of `kind` ("hip" | "emu") link against by name."""
+    out = _build_host().outputs(kind)
+    return [out["cuda_rasterizer"], out["simple_knn"]] if kind == "hip" else [out["cuda_rasterizer"]]
+
+
+def runtime_env(kind, env=None):
+    """The environment to run a prebuilt oracle/_ref executable of `kind` in: this tree's library directories first on
+    LD_LIBRARY_PATH.  The binaries' own run paths do not lead here when oracle/_ref was built in another checkout or is reached
+    through a link ($ORIGIN is where the file really lies)."""
+    env = dict(os.environ if env is None else env)
+    out = _build_host().outputs(kind)
+    dirs = sorted({os.path.dirname(p) for p in out.values()})
+    env["LD_LIBRARY_PATH"] = os.pathsep.join(dirs + [d for d in env.get("LD_LIBRARY_PATH", "").split(os.pathsep) if d])
+    return env
+
+
+def preload(kind):
+    """dlopen this tree's boundary libraries of `kind` (RTLD_GLOBAL), so that a prebuilt oracle/_ref library loaded next into this
+    process finds them by name, whatever its run path says (see runtime_env)."""
+    import ctypes
+    for lib in boundary_libraries(kind):
+        ctypes.CDLL(lib, mode=ctypes.RTLD_GLOBAL)
+
+
 LINK_OUT = {"emu": os.path.join(OUT_DIR, "ref_link_consumer_emu"), "hip": os.path.join(OUT_DIR, "ref_link_consumer_hip")}
 
 
@@ -219,7 +256,7 @@ def build_link_consumer(force=False):
                                   # libamdhip64.so.7) then satisfies libgsr_hip.so's request for libamdhip64.so.7 -- one runtime
                                   ["-Wl,--no-as-needed", src, "-o", out, "-L" + libdir, "-ltorch", "-ltorch_cpu", "-lc10"] + extra +
                                   ["-L" + d for d in dirs] + ["-l" + os.path.basename(l)[3:-3] for l in libs[kind]] +
-                                  ["-Wl,-rpath," + libdir] + ["-Wl,-rpath," + d for d in dirs])
+                                  ["-Wl,-rpath," + libdir] + [_origin_rpath(d) for d in dirs])
     finally:
         shutil.rmtree(GEN, ignore_errors=True)
     return dict(LINK_OUT)
@@ -344,7 +381,7 @@ def build_host_tree(force=False):
                                   ["-l" + os.path.basename(l)[3:-3] for l in libs[lib_kind]] +
                                   ["-L" + libdir, "-ltorch", "-ltorch_cpu", "-lc10"] + link +
                                   # --wrap=rand: the reference loop's std::rand() draws from the harness (oracle/ref_host.cpp)
-                                  ["-Wl,--no-undefined", "-Wl,--wrap=rand", "-Wl,-rpath," + libdir] + ["-Wl,-rpath," + d for d in link_dirs])
+                                  ["-Wl,--no-undefined", "-Wl,--wrap=rand", "-Wl,-rpath," + libdir] + [_origin_rpath(d) for d in link_dirs])
     finally:
         shutil.rmtree(GEN, ignore_errors=True)
     return dict(HOST_OUT)

@@ -24,6 +24,7 @@
 #include <torch/torch.h>
 #include <torch/library.h>
 
+#include <cstdlib>
 #include <filesystem>
 #include <memory>
 #include <mutex>
@@ -49,15 +50,17 @@ inline void refEmptyCache() {}
 #include <dlfcn.h>
 
 /* third_party/simple-knn's distCUDA2 (spatial.h:14) for increasePcd (:238,325): OURS -- the reference's is CUDA.  It calls the
- * CPU oracle's gsro_knn (oracle/libgsr_oracle.so, next to this library's directory), which tests/test_reference_pinning.py
- * pins bit for bit to the reference's own simple_knn.cu compiled for the host. */
+ * CPU oracle's gsro_knn (oracle/libgsr_oracle.so: $GSR_ORACLE_LIB, which oracle/ref_model.py sets, else next to this library's
+ * directory), which tests/test_reference_pinning.py pins bit for bit to the reference's own simple_knn.cu compiled for the host. */
 static torch::Tensor distCUDA2(const torch::Tensor& points)
 {
 	using knn_fn = void (*)(int, const float*, float*);
 	static knn_fn fn = [] {
 		Dl_info info;
 		TORCH_CHECK(dladdr(reinterpret_cast<void*>(&distCUDA2), &info) && info.dli_fname, "dladdr failed");
-		std::string path = std::filesystem::path(info.dli_fname).parent_path().parent_path() / "libgsr_oracle.so";
+		const char* given = std::getenv("GSR_ORACLE_LIB");   // (a prebuilt oracle/_ref may lie elsewhere than this tree's oracle/)
+		std::string path = given && *given ? std::string(given)
+		                                   : std::string(std::filesystem::path(info.dli_fname).parent_path().parent_path() / "libgsr_oracle.so");
 		void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
 		TORCH_CHECK(h, "cannot load ", path, ": ", dlerror());
 		auto f = reinterpret_cast<knn_fn>(dlsym(h, "gsro_knn"));

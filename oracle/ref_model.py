@@ -1,8 +1,10 @@
 """Python access to oracle/_ref/libref_densify{,_cuda}.so: the reference's own GaussianModel map-maintenance and optimizer
 code (src/gaussian_model.cpp:477-510, 553-831) behind torch ops -- see oracle/ref_densify.cpp.  TEST INFRASTRUCTURE ONLY."""
+import os
+
 import torch
 
-from . import build_ref
+from . import build_ref, oracle
 
 PARAMS = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")   # the reference's param-group order
 _ops = {}
@@ -16,6 +18,8 @@ def load(kind="cpu"):
         if path is None:
             _ops[kind] = None
         else:
+            # increasePcd's distCUDA2 calls THIS tree's CPU oracle (oracle/ref_densify.cpp), wherever the prebuilt library lies
+            os.environ["GSR_ORACLE_LIB"] = oracle.build()
             torch.ops.load_library(path)
             _ops[kind] = torch.ops.photoslam_reference_model if kind == "cpu" else torch.ops.photoslam_reference_model_cuda
     return _ops[kind]

@@ -85,8 +85,11 @@ def build(variant="hip", force=False):
             raise RuntimeError("host build failed: " + " ".join(cmd))
     common = ["-L" + libdir, "-L" + gsr_dir, "-lgsr_emu", "-ltorch", "-ltorch_cpu", "-lc10",
               "-Wl,-rpath," + libdir, "-Wl,-rpath," + gsr_dir, "-Wl,-rpath,$ORIGIN"]
-    subprocess.check_call(["g++", "-shared", "-o", EMU_OUT["cuda_rasterizer"]] + [objs[s] for s in BOUNDARY_SRCS] + common)
-    subprocess.check_call(["g++", "-shared", "-o", EMU_OUT["photoslam_host"]] + [objs[s] for s in HOST_SRCS] +
+    # (SONAMEs as CMake gives the hip targets: a copy already loaded into a process then satisfies a dependency by that name)
+    soname = lambda target: "-Wl,-soname," + os.path.basename(EMU_OUT[target])
+    subprocess.check_call(["g++", "-shared", "-o", EMU_OUT["cuda_rasterizer"], soname("cuda_rasterizer")] +
+                          [objs[s] for s in BOUNDARY_SRCS] + common)
+    subprocess.check_call(["g++", "-shared", "-o", EMU_OUT["photoslam_host"], soname("photoslam_host")] + [objs[s] for s in HOST_SRCS] +
                           ["-L" + gsr_dir, "-lcuda_rasterizer_emu"] + common)
     return EMU_OUT["photoslam_host"]
 

@@ -1,6 +1,6 @@
 """Regenerates tests/golden/oracle_small.npz: outputs of the CPU oracle on a small seeded scene.
 
-These vectors are oracle outputs (reference outputs are in reference_small.npz, see make_reference_golden.py); they
+These vectors are oracle outputs (reference outputs are in reference_small.*.npz, see make_reference_golden.py); they
 freeze the oracle together with the scene generator, so that later edits to either cannot silently change what the GPU
 path is compared against.
 

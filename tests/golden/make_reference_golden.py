@@ -1,4 +1,4 @@
-"""Regenerates tests/golden/reference_small.npz: outputs of the REFERENCE's own rasterizer sources
+"""Regenerates tests/golden/reference_small.*.npz: outputs of the REFERENCE's own rasterizer sources
 (/root/reference/cuda_rasterizer/*.cu compiled for the host by oracle/build_ref.py) on small seeded scenes.
 
 These are reference outputs -- modulo the host shims for CUDA blocks, the two CUB calls and the glm operators
@@ -8,6 +8,7 @@ The fixture lets the oracle AND the HIP kernels be checked against the reference
 
     python tests/golden/make_reference_golden.py
 """
+import glob
 import os
 import sys
 
@@ -79,7 +80,7 @@ def compute():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# tests/golden/reference_C1.npz: the reference's sources on BASELINE config C1 (50 k Gaussians @ 640x480, seed 0) -- the size at
+# tests/golden/reference_C1.*.npz: the reference's sources on BASELINE config C1 (50 k Gaussians @ 640x480, seed 0) -- the size at
 # which the paths the small cases cannot reach meet the reference ITSELF: tile lists longer than one 256-entry batch (303),
 # 258 Gaussians with more than 64 tiles (the long-run sums of the backward pass), 212 730 instances = 104 radix-sort blocks
 # in four block groups.  The inputs are NOT stored (12 MB): they are regenerated from the seed and checked against a digest.
@@ -146,11 +147,64 @@ def compute_c1():
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Storage: no committed file may exceed 1 MiB, so a fixture is a set of parts <stem>.0.npz, <stem>.1.npz, ...
+PART_BYTES = 900 * 1024
+
+
+def save_fixture(stem, arrays):
+    """np.savez_compressed of `arrays` into parts <stem>.<i>.npz of at most PART_BYTES each (estimated with zlib, checked after
+    writing).  An array that does not fit one part is cut along its first axis into pieces `<name>@<j>`; load_fixture() joins
+    them again.  Returns the paths written."""
+    import zlib
+    pieces = []
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        n = -(-len(zlib.compress(a.tobytes())) * 5 // (4 * PART_BYTES))   # (ceil, with a quarter of headroom)
+        if n > 1:
+            pieces += [(f"{k}@{j}", c) for j, c in enumerate(np.array_split(a, n, axis=0))]
+        else:
+            pieces.append((k, a))
+    parts, size = [{}], 0
+    for k, a in pieces:
+        est = len(zlib.compress(a.tobytes())) + 512
+        if parts[-1] and size + est > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += est
+    for old in glob.glob(stem + ".*.npz"):
+        os.remove(old)
+    paths = []
+    for i, part in enumerate(parts):
+        path = f"{stem}.{i}.npz"
+        np.savez_compressed(path, **part)
+        assert os.path.getsize(path) < 1 << 20, (path, os.path.getsize(path))
+        paths.append(path)
+    return paths
+
+
+def load_fixture(stem):
+    """{name: array} of the parts save_fixture() wrote for `stem`."""
+    files = sorted(glob.glob(stem + ".*.npz"), key=lambda f: int(f[len(stem) + 1:-4]))
+    if not files:
+        raise FileNotFoundError(stem + ".*.npz")
+    out, cut = {}, {}
+    for f in files:
+        with np.load(f) as z:
+            for k in z.files:
+                if "@" in k:
+                    name, j = k.rsplit("@", 1)
+                    cut.setdefault(name, {})[int(j)] = z[k]
+                else:
+                    out[k] = z[k]
+    for name, chunks in cut.items():
+        out[name] = np.concatenate([chunks[j] for j in sorted(chunks)], axis=0)
+    return out
+
+
 if __name__ == "__main__":
     here = os.path.dirname(os.path.abspath(__file__))
-    path = os.path.join(here, "reference_small.npz")
-    np.savez_compressed(path, **compute())
-    print("written", path, os.path.getsize(path), "bytes")
-    path = os.path.join(here, "reference_C1.npz")
-    np.savez_compressed(path, **compute_c1())
-    print("written", path, os.path.getsize(path), "bytes")
+    for stem, arrays in (("reference_small", compute()), ("reference_C1", compute_c1())):
+        for path in save_fixture(os.path.join(here, stem), arrays):
+            print("written", path, os.path.getsize(path), "bytes")

@@ -40,6 +40,7 @@ def _ops(kind):
     path = build_ref.build_host_tree().get(kind)
     if path is None or not os.path.exists(path):
         pytest.skip("oracle/_ref/libref_host_*.so was never built (no reference tree, no prebuilt library)")
+    build_ref.preload(kind.split("_")[0])     # ("hip_fused_loss" links what "hip" links)
     torch.ops.load_library(path)
     return getattr(torch.ops, build_ref.HOST_OPS[kind]), path
 

@@ -20,8 +20,10 @@ def _consumer(kind):
     return exe
 
 
-def _run(exe, *args):
-    out = subprocess.check_output([exe] + list(args), text=True, env=dict(os.environ, PYTEST_CURRENT_TEST="ref_link"))
+def _run(kind, *args):
+    from oracle import build_ref
+    out = subprocess.check_output([_consumer(kind)] + list(args), text=True,
+                                  env=build_ref.runtime_env(kind, dict(os.environ, PYTEST_CURRENT_TEST="ref_link")))
     m = re.search(r"class_vs_free=([-\d.e+]+) present=(\d+) vis=(\d+)", out)
     assert m, out
     # GaussianRasterizer / autograd == the free functions (two backward passes: on the GPU they differ by the order of the
@@ -33,12 +35,12 @@ def _run(exe, *args):
 
 
 def test_reference_declarations_link_and_run_on_the_emulator_host(emu_lib_path, oracle):
-    _check_against_oracle(_run(_consumer("emu")), oracle, "emu-wave64")
+    _check_against_oracle(_run("emu"), oracle, "emu-wave64")
 
 
 @pytest.mark.gpu
 def test_reference_declarations_link_and_run_on_the_gpu(oracle):
-    _check_against_oracle(_run(_consumer("hip"), "cuda"), oracle, "hip-gfx950")
+    _check_against_oracle(_run("hip", "cuda"), oracle, "hip-gfx950")
 
 
 def test_hip_consumer_loads_one_rocm_runtime_and_fails_loudly_without_a_device():
@@ -47,9 +49,10 @@ def test_hip_consumer_loads_one_rocm_runtime_and_fails_loudly_without_a_device()
     process died inside library initialisation) and, on a box without a GPU, stop at the first HIP call with the library's own
     message -- no CPU fallback, no segmentation fault."""
     import torch
+    from oracle import build_ref
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: the gpu-marked twin runs the consumer for real")
-    p = subprocess.run([_consumer("hip")], capture_output=True, text=True)
+    p = subprocess.run([_consumer("hip")], capture_output=True, text=True, env=build_ref.runtime_env("hip"))
     assert p.returncode == -6, (p.returncode, p.stderr[-400:])      # std::terminate on the uncaught std::runtime_error
     assert "HIP runtime error" in p.stderr and "no ROCm-capable device" in p.stderr, p.stderr[-400:]
 

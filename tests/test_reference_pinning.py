@@ -3,7 +3,7 @@ sources: /root/reference/cuda_rasterizer/{forward,backward,rasterizer_impl}.cu c
 against the CUDA / CUB / glm shims of oracle/ref_shim/.
 
   * where the reference tree exists (this container): the oracle is compared with a fresh run of the reference sources on
-    random scenes, and the committed fixture tests/golden/reference_small.npz is checked to be current;
+    random scenes, and the committed fixture tests/golden/reference_small.*.npz is checked to be current;
   * everywhere (incl. the GPU boxes, where /root/reference does not exist): the oracle, and under `-m gpu` the HIP kernels,
     are compared with the committed fixture.
 Forward quantities must agree BIT FOR BIT (both sides: IEEE fp32, no FMA contraction); gradients to 1e-5 relative L1 (the
@@ -18,7 +18,7 @@ import parity
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-FIXTURE = os.path.join(HERE, "golden", "reference_small.npz")
+FIXTURE = os.path.join(HERE, "golden", "reference_small")   # (parts reference_small.<i>.npz: make_reference_golden.load_fixture)
 GRADS = ("dL_dmeans2D", "dL_dopacity", "dL_dcolors", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations")
 
 
@@ -78,9 +78,9 @@ def test_oracle_matches_the_reference_sources(oracle, P, W, H, seed, deg):
 @needs_reference
 def test_reference_fixture_is_current():
     import make_reference_golden as mg
-    want, got = np.load(FIXTURE), mg.compute()
-    assert sorted(want.files) == sorted(got.keys())
-    for k in want.files:
+    want, got = mg.load_fixture(FIXTURE), mg.compute()
+    assert sorted(want) == sorted(got.keys())
+    for k in want:
         assert np.array_equal(want[k], got[k]), k      # the host build is deterministic: the fixture is reproduced exactly
 
 
@@ -128,9 +128,10 @@ def test_oracle_point_kernels_match_the_reference_sources(oracle):
 
 
 def _fixture_case(name):
-    f = np.load(FIXTURE)
-    d = {k[len(name) + 4:]: f[k] for k in f.files if k.startswith(name + "_in_")}
-    want = {k[len(name) + 1:]: f[k] for k in f.files if k.startswith(name + "_") and not k.startswith(name + "_in_")}
+    import make_reference_golden as mg
+    f = mg.load_fixture(FIXTURE)
+    d = {k[len(name) + 4:]: f[k] for k in f if k.startswith(name + "_in_")}
+    want = {k[len(name) + 1:]: f[k] for k in f if k.startswith(name + "_") and not k.startswith(name + "_in_")}
     return d, want
 
 
@@ -204,14 +205,14 @@ def test_emulated_hip_kernels_match_the_reference_fixture(emu_lib_path, oracle, 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# The mid-size fixture tests/golden/reference_C1.npz (make_reference_golden.py: compute_c1): the reference's own sources on
+# The mid-size fixture tests/golden/reference_C1.*.npz (make_reference_golden.py: compute_c1): the reference's own sources on
 # BASELINE config C1 -- multi-batch tile lists, Gaussians with more than 64 tiles, a radix sort over four block groups.
-FIXTURE_C1 = os.path.join(HERE, "golden", "reference_C1.npz")
+FIXTURE_C1 = os.path.join(HERE, "golden", "reference_C1")
 
 
 def _c1():
     import make_reference_golden as mg
-    want = np.load(FIXTURE_C1)
+    want = mg.load_fixture(FIXTURE_C1)
     d = mg.c1_inputs()
     assert np.array_equal(mg.inputs_digest(d), want["inputs_sha256"]), \
         "scene.make_config('C1', seed=0) no longer generates the cloud the fixture was made from (numpy generator change?)"
@@ -227,8 +228,8 @@ def _rel_l1(a, b):
 def test_reference_C1_fixture_is_current():
     mg, d, want = _c1()
     got = mg.compute_c1()
-    assert sorted(want.files) == sorted(got.keys())
-    for k in want.files:
+    assert sorted(want) == sorted(got.keys())
+    for k in want:
         assert np.array_equal(want[k], got[k]), k
 
 
@@ -240,7 +241,7 @@ def test_oracle_matches_the_reference_C1_fixture(oracle):
                                             "means2D", "conic_opacity", "rgb", "cov3D", "final_T")}
     fields.update(radii=radii, out_color=color)
     got = mg.reduce_c1(fields, grads)
-    for k in want.files:
+    for k in want:
         if k == "inputs_sha256":
             continue
         if k.startswith("dL_"):

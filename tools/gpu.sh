@@ -6,10 +6,10 @@
 #   build        python __graft_entry__.py
 #   tests        the whole -m gpu suite            tests:<expr>  only tests matching -k <expr>
 #   smoke        __graft_entry__.smoke()
-#   driver       the driver's command `bench.py --gpus 1 --steps 20 --warmup 5` (with the CPU baseline, timed)
-#   bench        `bench.py --no-cpu-baseline` (100 steps + median of 100)      bench:C2 | bench:C4 | bench:C5  other configs
+#   driver       the driver's command with every leg: `bench.py --full --gpus 1 --steps 20 --warmup 5` (with the CPU baseline, timed)
+#   bench        `bench.py --full --no-cpu-baseline` (100 steps + median of 100)      bench:C2 | bench:C4 | bench:C5  other configs
 #   big:<points> the C3 view with <points> Gaussians (default 16 M): the path at 8x the stated model size
-#   raster       `bench.py --raster-only --no-cpu-baseline`
+#   raster       `bench.py --full --raster-only --no-cpu-baseline`
 #   kstats       rocprofv3 --kernel-trace --stats of the driver's command (no CPU baseline) -> kernel_stats_bench_full_C3.csv   kstats:C2  another config
 #   knnstats     rocprofv3 --kernel-trace --stats of distCUDA2 at 100 k and 1 M points -> knn_kernel_stats_<points>.csv
 #   pmc          TCC traffic per launch, rasterizer only (two --pmc passes)      pmc:full  the fused train step   pmc:full:C2  another config
@@ -87,7 +87,7 @@ pmc_pass() {  # $1 = mode (raster|full), $2 = config (default C3) -> $OUT/pmc_tr
   local mode=$1 cfg=${2:-C3}
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_$c
-    (cd /tmp && timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -o p -- python $ROOT/bench.py --config $cfg --steps 3 --warmup 1 \
+    (cd /tmp && timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -o p -- python $ROOT/bench.py --full --config $cfg --steps 3 --warmup 1 \
         $( [ "$mode" = full ] || echo --raster-only ) --no-cpu-baseline --median-steps 0 --densify-leg-steps 0 --no-knn-leg --dropin-steps 0 > /tmp/pmc_$c.log 2>&1)
   done
   python - "$OUT/pmc_traffic_$mode$( [ $cfg = C3 ] || echo _$cfg ).json" <<'PY'
@@ -118,7 +118,7 @@ sq_pass() {  # $1 = mode (raster|full), $2 = config (default C3) -> $OUT/sq_coun
   local i=0
   for set in "${sets[@]}"; do
     rm -rf /tmp/sq_$i
-    (cd /tmp && timeout 400 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/sq_$i -o p -- python $ROOT/bench.py --config $cfg --steps 3 --warmup 1 \
+    (cd /tmp && timeout 400 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/sq_$i -o p -- python $ROOT/bench.py --full --config $cfg --steps 3 --warmup 1 \
         $( [ "$mode" = full ] || echo --raster-only ) --no-cpu-baseline --median-steps 0 --densify-leg-steps 0 --no-knn-leg --dropin-steps 0 > /tmp/sq_$i.log 2>&1)
     i=$((i+1))
   done
@@ -149,7 +149,7 @@ for step in "$@"; do
     tests)  if [ -n "$arg" ]; then timeout 1200 python -m pytest tests -q -m gpu -k "$arg" -s --durations=8 > $OUT/test_gpu.log 2>&1; else timeout 1200 python -m pytest tests -q -m gpu --durations=8 > $OUT/test_gpu.log 2>&1; fi
             grep -v Warning $OUT/test_gpu.log | tail -18 | cut -c1-300 ;;
     smoke)  timeout 300 python -c "import __graft_entry__ as e; e.smoke()" 2>&1 | tail -1 ;;
-    driver) ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver_cmd_C3.log 2>&1
+    driver) ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver_cmd_C3.log 2>&1
             grep "^{\"metric\"" $OUT/bench_driver_cmd_C3.log > $OUT/bench_driver_cmd_C3.json; grep real $OUT/bench_driver_cmd_C3.log
             python - $OUT/bench_driver_cmd_C3.json <<'PY'
 import json, sys
@@ -164,18 +164,18 @@ cb = d.get("cpu_baseline", {})
 print("cpu", cb.get("value"), json.dumps(cb.get("runs", {}).get("C1", {}).get("gpu_fused_step_same_sequence")))
 PY
             ;;
-    bench)  cfg=${arg:-C3}; timeout 500 python bench.py --config $cfg --no-cpu-baseline --no-knn-leg --dropin-steps 0 $( [ $cfg = C3 ] || echo --densify-leg-steps 0 ) > $OUT/bench_full_$cfg$SUF.json 2>$OUT/bench_err.log
+    bench)  cfg=${arg:-C3}; timeout 500 python bench.py --full --config $cfg --no-cpu-baseline --no-knn-leg --dropin-steps 0 $( [ $cfg = C3 ] || echo --densify-leg-steps 0 ) > $OUT/bench_full_$cfg$SUF.json 2>$OUT/bench_err.log
             python -c "
 import json; d=json.load(open('$OUT/bench_full_$cfg$SUF.json')); print('$cfg$SUF', d['ms_per_step'], 'median', d['protocol']['median_ms_per_step'], 'raster', d.get('rasterizer_only', {}).get('fwd_bwd_ms'), {k: v['ms'] for k, v in d['roofline']['stages'].items()})" ;;
-    benchq) cfg=${arg:-C3}; timeout 300 python bench.py --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/benchq_$cfg$SUF.json 2>$OUT/bench_err.log   # quick A/B form: no densify leg
+    benchq) cfg=${arg:-C3}; timeout 300 python bench.py --full --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/benchq_$cfg$SUF.json 2>$OUT/bench_err.log   # quick A/B form: no densify leg
             python -c "
 import json; d=json.load(open('$OUT/benchq_$cfg$SUF.json')); print('$cfg$SUF', d['ms_per_step'], 'median', d['protocol']['median_ms_per_step'], 'host blocked us/step', d.get('host', {}).get('blocked_in_forward_sync_us_per_step'), {k: v['ms'] for k, v in d['roofline']['stages'].items()})" ;;
     big)    # big:<points>: the C3 view with <points> Gaussians (default 16 M) -- does the path hold at 8x / 16x the stated model size?
-            n=${arg:-16000000}; timeout 900 python bench.py --points $n --steps 20 --warmup 5 --median-steps 20 --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/bench_C3_${n}_points.json 2>$OUT/big_err.log
+            n=${arg:-16000000}; timeout 900 python bench.py --full --points $n --steps 20 --warmup 5 --median-steps 20 --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/bench_C3_${n}_points.json 2>$OUT/big_err.log
             python -c "
 import json; d=json.load(open('$OUT/bench_C3_${n}_points.json')); print('C3 view,', d['config']['gaussians'], 'Gaussians:', d['ms_per_step'], 'ms', d['value'], 'it/s', 'visible', d['config']['visible'], 'instances', d['config']['instances'], {k: v['ms'] for k, v in d['roofline']['stages'].items()})" || tail -5 $OUT/big_err.log ;;
-    raster) timeout 400 python bench.py --raster-only --no-cpu-baseline --no-knn-leg > $OUT/bench_raster_only_C3.json 2>>$OUT/bench_err.log; cut -c1-200 $OUT/bench_raster_only_C3.json ;;
-    kstats) cfg=${arg:-C3}; kernel_stats $OUT/kernel_stats_bench_full_$cfg.csv python $ROOT/bench.py --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --densify-leg-steps 0 --no-knn-leg --dropin-steps 0 ;;
+    raster) timeout 400 python bench.py --full --raster-only --no-cpu-baseline --no-knn-leg > $OUT/bench_raster_only_C3.json 2>>$OUT/bench_err.log; cut -c1-200 $OUT/bench_raster_only_C3.json ;;
+    kstats) cfg=${arg:-C3}; kernel_stats $OUT/kernel_stats_bench_full_$cfg.csv python $ROOT/bench.py --full --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --densify-leg-steps 0 --no-knn-leg --dropin-steps 0 ;;
     knnstats) for n in 100000 1000000; do kernel_stats $OUT/knn_kernel_stats_$n.csv python $ROOT/tools/knn_probe.py $n; done ;;
     pmc)    IFS=: read m c <<< "$arg"; pmc_pass ${m:-raster} ${c:-C3} ;;   # pmc | pmc:full | pmc:full:C2
     sq)     IFS=: read m c <<< "$arg"; sq_pass ${m:-full} ${c:-C3} ;;       # sq | sq:raster | sq:full:C2
@@ -184,19 +184,19 @@ import json; d=json.load(open('$OUT/bench_C3_${n}_points.json')); print('C3 view
             [ "$arg" = packed ] && form=packed; [ "$arg" = dense ] && form=dense   # dp:packed | dp:dense: the form of the view-factored exchange (default: the guarded trial)
             [ "$arg" = late ] && export GSR_EARLY_GATHER=0 || unset GSR_EARLY_GATHER
             for cfg in ${DP_CONFIGS:-C3 C4}; do
-              GSR_BENCH_FORCE_DP=1 GSR_BENCH_EXCHANGE=$ex GSR_BENCH_PY_EXCHANGE=$pyx timeout 400 python bench.py --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 --exchange-form $form > $OUT/dp_$cfg.log 2>$OUT/dp_err.log
+              GSR_BENCH_FORCE_DP=1 GSR_BENCH_EXCHANGE=$ex GSR_BENCH_PY_EXCHANGE=$pyx timeout 400 python bench.py --full --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 --exchange-form $form > $OUT/dp_$cfg.log 2>$OUT/dp_err.log
               f=$OUT/bench_${cfg}_dp_path_1rank_rccl_${arg:-factored}$SUF.json
               grep '^{"metric"' $OUT/dp_$cfg.log > $f   # (the RCCL banner precedes the JSON line)
               python -c "
 import json; d=json.load(open('$f')); print('$cfg dp 1 rank ${arg:-factored}', d['ms_per_step'], 'median', d['protocol']['median_ms_per_step'], d['rccl']['collectives_issued_by'][:12], d['rccl'].get('exchange_form'), d.get('host', {}).get('blocked_in_forward_sync_us_per_step'), (d.get('per_rank') or [{}])[0].get('segments_ms_median'))" || tail -5 $OUT/dp_err.log
             done ;;
-    dpstats) GSR_BENCH_FORCE_DP=1 kernel_stats $OUT/kernel_stats_dp_path_1rank_C3${arg:+_$arg}$SUF.csv python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --densify-leg-steps 0 --no-knn-leg --median-steps 0 --dropin-steps 0 --exchange-form ${arg:-dense} ;;   # dpstats | dpstats:packed
+    dpstats) GSR_BENCH_FORCE_DP=1 kernel_stats $OUT/kernel_stats_dp_path_1rank_C3${arg:+_$arg}$SUF.csv python $ROOT/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --densify-leg-steps 0 --no-knn-leg --median-steps 0 --dropin-steps 0 --exchange-form ${arg:-dense} ;;   # dpstats | dpstats:packed
     share2) # share2 | share2:packed | share2:dense | share2:4 -- TWO (or N) ranks on the ONE GPU of the box over gloo, the exchange driven
             # by the C++ host: a functional check of bench.py's multi-rank glue (trial of the exchange forms, per-rank tables, replica
             # checksum) -- not a rate: the ranks share the device and gloo moves the bytes through the host
             n=2; form=auto; case "$arg" in packed|dense) form=$arg ;; [0-9]*) n=$arg ;; esac
             GSR_BENCH_SHARE_GPU=1 GSR_BENCH_BACKEND=gloo GSR_BENCH_CPP_EXCHANGE=1 GSR_EXCHANGE_ALLOW_GLOO_DEVICE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-              --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus $n --steps 10 --warmup 3 --config C2 --no-cpu-baseline --no-knn-leg \
+              --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus $n --steps 10 --warmup 3 --config C2 --no-cpu-baseline --no-knn-leg \
               --densify-leg-steps 0 --dropin-steps 0 --median-steps 20 --exchange-form $form > $OUT/share_${n}_$form.log 2>$OUT/share_err.log
             f=$OUT/bench_C2_${n}ranks_one_gpu_gloo_cpp_exchange_$form.json
             grep '^{"metric"' $OUT/share_${n}_$form.log > $f
@@ -204,26 +204,26 @@ import json; d=json.load(open('$f')); print('$cfg dp 1 rank ${arg:-factored}', d
 import json; d=json.load(open('$f')); print('C2 $n ranks one GPU gloo', d['n_gpus'], d['ms_per_step'], d['rccl'], 'replicas_identical', d.get('replicas_identical'), d.get('exposed_communication'), 'per_rank', len(d.get('per_rank') or []))" || tail -20 $OUT/share_err.log ;;
     mapper) timeout 900 python bench.py --mapper-loop $( [ "$arg" = morton ] && echo --morton-reindex ) $( [ "$arg" = percall ] && echo --no-persistent-workspace ) > $OUT/mapper_loop_C5$( [ -n "$arg" ] && echo _$arg ).json 2>$OUT/mapper_err.log; cut -c1-700 $OUT/mapper_loop_C5$( [ -n "$arg" ] && echo _$arg ).json; tail -3 $OUT/mapper_err.log ;;   # mapper | mapper:morton | mapper:percall (the rasterizer's scratch buffers allocated per call, as the reference)
     densify) # the stated-config leg alone (250 steps, densify every 100, training learning rates): the reference's row order, then morton_reindex
-            timeout 600 python bench.py --steps 5 --warmup 2 --median-steps 0 --no-cpu-baseline --no-knn-leg --dropin-steps 0 --no-config-legs --no-sq-probe > $OUT/densify_run_C3.json 2>>$OUT/bench_err.log
+            timeout 600 python bench.py --full --steps 5 --warmup 2 --median-steps 0 --no-cpu-baseline --no-knn-leg --dropin-steps 0 --no-config-legs --no-sq-probe > $OUT/densify_run_C3.json 2>>$OUT/bench_err.log
             python -c "
 import json; j=json.load(open('$OUT/densify_run_C3.json'))
 for k in ('densify_run', 'densify_run_morton_reindex'):
     d=j[k]; print(k, d['iters_per_s'], {q: d[q] for q in d if q in ('ms_per_step', 'ms_median_other_steps', 'ms_per_densifying_step', 'gaussians_after')})" ;;
     drv20)  # drv20[:n]: the driver's protocol (20 timed steps behind 5 warm-up steps) n times in a row on one box: the spread of `value`
             for i in $(seq 1 ${arg:-5}); do
-              timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 --no-config-legs --no-sq-probe > $OUT/drv20_$i.json 2>>$OUT/bench_err.log
+              timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 --no-config-legs --no-sq-probe > $OUT/drv20_$i.json 2>>$OUT/bench_err.log
               python -c "
 import json; d=json.load(open('$OUT/drv20_$i.json')); print('run $i: timed', d['ms_per_step'], 'ms  value', d['value'], ' median of 100 further steps', d['protocol']['median_ms_per_step'], 'p90', d['protocol']['p90_ms'])"
             done ;;
     zorder) # zorder[:n]: the driver's protocol at C3 with the cloud as generated and with its rows along a Z-order curve (--scene-order morton), alternating
             for i in $(seq 1 ${arg:-3}); do for o in random morton; do
-              timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --scene-order $o --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 --no-config-legs --no-sq-probe > $OUT/zorder_${o}_$i.json 2>>$OUT/bench_err.log
+              timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --scene-order $o --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 --no-config-legs --no-sq-probe > $OUT/zorder_${o}_$i.json 2>>$OUT/bench_err.log
               python -c "
 import json; d=json.load(open('$OUT/zorder_${o}_$i.json')); print('run $i $o: timed', d['ms_per_step'], 'ms  value', d['value'], ' median of 100 further steps', d['protocol']['median_ms_per_step'], {k: v['ms'] for k, v in d['roofline']['stages'].items() if k in ('preprocess_fwd', 'blend_fwd', 'blend_bwd', 'preprocess_bwd')})"
             done; done ;;
     dropin) timeout 600 python bench.py --dropin-only > $OUT/dropin_unfused_C3$SUF.json 2>$OUT/dropin_err.log; cut -c1-700 $OUT/dropin_unfused_C3$SUF.json; tail -3 $OUT/dropin_err.log ;;
     dropinstats) kernel_stats $OUT/kernel_stats_dropin_unfused_C3.csv python $ROOT/bench.py --dropin-only --dropin-steps 10 ;;
-    seeds)  for sd in 0 1 2 3 4; do timeout 300 python bench.py --seed $sd --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/benchq_C3_seed$sd.json 2>>$OUT/bench_err.log; done
+    seeds)  for sd in 0 1 2 3 4; do timeout 300 python bench.py --full --seed $sd --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/benchq_C3_seed$sd.json 2>>$OUT/bench_err.log; done
             python - $OUT <<'PY'
 import json, sys, statistics as st
 out = {"runs": []}
@@ -243,8 +243,8 @@ PY
             # built in this container: it travels with the snapshot) and of this tree on ONE box -> ab_<dir>.json (ms per step, per run)
             IFS=: read d n cfg <<< "$arg"; n=${n:-3}; cfg=${cfg:-C3}
             for i in $(seq 1 $n); do
-              (cd $ROOT/$d && timeout 300 python bench.py --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $ROOT/$OUT/ab_${d}_old_$i.json 2>>$ROOT/$OUT/bench_err.log)
-              timeout 300 python bench.py --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/ab_${d}_new_$i.json 2>>$OUT/bench_err.log
+              (cd $ROOT/$d && timeout 300 python bench.py $(grep -q -- '"--full"' bench.py && echo --full) --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $ROOT/$OUT/ab_${d}_old_$i.json 2>>$ROOT/$OUT/bench_err.log)
+              timeout 300 python bench.py --full --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/ab_${d}_new_$i.json 2>>$OUT/bench_err.log
             done
             python - $OUT $d $n $cfg <<'PY'
 import json, sys, statistics as st
@@ -265,8 +265,8 @@ PY
             IFS=: read spec n cfg <<< "$arg"; n=${n:-3}; cfg=${cfg:-C3}   # abenv:VAR=A,B[:pairs[:config]]
             var=${spec%%=*}; vals=${spec#*=}; va=${vals%%,*}; vb=${vals##*,}
             for i in $(seq 1 $n); do
-              env $var=$va timeout 300 python bench.py --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/abenv_${var}_a_$i.json 2>>$OUT/bench_err.log
-              env $var=$vb timeout 300 python bench.py --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/abenv_${var}_b_$i.json 2>>$OUT/bench_err.log
+              env $var=$va timeout 300 python bench.py --full --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/abenv_${var}_a_$i.json 2>>$OUT/bench_err.log
+              env $var=$vb timeout 300 python bench.py --full --config $cfg --no-cpu-baseline --no-knn-leg --densify-leg-steps 0 --dropin-steps 0 > $OUT/abenv_${var}_b_$i.json 2>>$OUT/bench_err.log
             done
             python - $OUT $var $va $vb $n $cfg <<'PY'
 import json, sys, statistics as st
