@@ -1,7 +1,8 @@
 // blend.h -- pieces shared by the forward and backward alpha-blend kernels.
 //
 // Work decomposition: the 16x16 tile stays the unit of binning (tile ids are part of the parity
-// contract), but the unit of execution is one WAVE per 8x8 pixel quad: a 64-thread workgroup
+// contract), but the unit of execution of the forward blend is one WAVE per 8x8 pixel quad (the backward blend runs one wave
+// per 16x8 half tile, two pixels per lane, and walks these quads' flags: blend_bwd.hip): a 64-thread workgroup
 // owns quad q of a tile, lane l the pixel (l&7, l>>3) inside it.  The four quads of a tile walk
 // the same depth-sorted list independently -- no workgroup barriers.  Per batch of 64 list
 // entries lane j gathers entry j's 48-byte record, evaluates the per-quad rejection test for it
@@ -114,8 +115,8 @@ __device__ __forceinline__ bool quad_keep(const float4 q0, const float4 q1, floa
 // preprocess_bwd (partials.h) applies them once per Gaussian instead of once per pixel pair
 // in `partials`, indexed by emission order: a Gaussian's instances were emitted contiguously
 // (row-major over its tile rectangle, binning.hip), so slot = first_slot + (ty-miny)*w + (tx-minx),
-// all of which ride in the spare words of the blend record.  The backward blend merges the four
-// quads of a tile in LDS and writes each touched slot once with plain stores; preprocess_bwd then
+// all of which ride in the spare words of the blend record.  The backward blend merges the two
+// half-tile waves of a tile in LDS and writes each touched slot once with plain stores; preprocess_bwd then
 // sums each Gaussian's contiguous run.  (The reference issues 9 atomics per pixel-Gaussian pair;
 // 33 M float atomics per view were measured to cost ~1 ms on MI355X at the C3 size.)
 constexpr int GRAD_ACC_FLOATS = 12;

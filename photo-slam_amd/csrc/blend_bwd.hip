@@ -1,5 +1,9 @@
 // blend_bwd.hip -- backward of the alpha blend: per-pixel loss gradients -> per-instance
-// gradients of colour, 2D mean, conic and opacity.  One wave per 8x8 quad, four quads = one 256-thread workgroup per tile.
+// gradients of colour, 2D mean, conic and opacity.  One wave per 16x8 half tile, two halves = one 128-thread workgroup per tile:
+// lane l of wave h holds TWO pixels, (l & 7, 8h + (l >> 3)) in the half's left quad 2h and the pixel 8 columns to its right in
+// its right quad 2h + 1 (the quads of the forward blend, blend.h, whose flags say which quads blend an entry).  Views with
+// fewer tiles than keep the machine busy that way run the same kernel with one wave per 8x8 quad (four waves, 256 threads and
+// 256-entry segments per tile; below, in front of the kernel).  What follows describes the half tiles.
 //
 // Per-pixel semantics are renderCUDA's backward (cuda_rasterizer/backward.cu:399-557): walk
 // the tile list back to front starting at each pixel's last contributor, recompute alpha,
@@ -7,22 +11,26 @@
 //
 // The reference issues nine global float atomics per contributing (pixel, Gaussian) pair
 // (backward.cu:523-554).  Here there are none (see blend.h):
-//   * entries behind the deepest last-contributor of the tile are never loaded; a segment of 256 list entries is staged once
-//     per tile by all 256 threads, and only the entries the forward blend flagged as blended by some quad of the tile
-//     (state.h: contrib); every quad-wave then walks the entries flagged for ITS quad;
+//   * entries behind the deepest last-contributor of the tile are never loaded; a segment of 128 list entries is staged once
+//     per tile by all 128 threads, and only the entries the forward blend flagged as blended by some quad of the tile
+//     (state.h: contrib); every half-tile wave then walks the union of the entries flagged for its two quads and evaluates,
+//     per entry, only the flagged quad(s) -- a wave-uniform branch on the two flag bits;
+//   * where both quads of a half blend an entry (three quarters of the quad visits at C3, 70 % at C2: tools/quad_pair_probe.py,
+//     profiles/r07_a_*) the nine products of the lane's two pixels are summed in the lane and reduced ONCE: one butterfly and
+//     one ds_add_f32 per (half tile, entry) instead of one per (quad, entry);
 //   * the per-pair arithmetic is branch-free; 1/(1-alpha) is one v_rcp_f32 shared by the two
 //     divisions of the reference;
 //   * "everything behind entry j, dotted with the pixel's loss gradient" is ONE running scalar per pixel (below) instead of
 //     the reference's three-channel accum_rec;
-//   * the nine terms are summed across the 64 pixels of a quad with a butterfly packed from the
+//   * the nine terms are summed across the wave's 64 lanes with a butterfly packed from the
 //     top through v_permlane32_swap / v_permlane16_swap (wave64.h, 19 VALU) that leaves eight
 //     totals in one register (one per 8-lane group) and the ninth as four row sums; ONE ds_add_f32
-//     with twelve active lanes adds them to the tile's LDS accumulators, where the four quads
+//     with twelve active lanes adds them to the tile's LDS accumulators, where the two halves
 //     of a tile meet;
 //   * the two mean2D terms are reduced as sum(dL_dG*G*dx), sum(dL_dG*G*dy); their conic
 //     combination (backward.cu:539-546) is linear in them and applied once per Gaussian in
 //     preprocess_bwd (partials.h);
-//   * at the end of a segment of 256 list entries the workgroup writes every touched entry's
+//   * at the end of a segment of 128 list entries the workgroup writes every touched entry's
 //     nine sums to that instance's private 48-byte slot with plain stores.
 //
 // The running scalar.  The reference keeps accum_rec = the colour blended BEHIND entry j, normalised by the transmittance
@@ -41,61 +49,89 @@
 
 namespace gsr {
 
-constexpr int BWD_SEG = 256;  // list entries accumulated in LDS per segment (9 x 256 floats = 9 KiB); thread i stages entry i of the segment
+// Two forms of one kernel, WAVES waves per tile:
+//   WAVES == 2  wave h owns the tile's half h (rows 8h .. 8h+7): quads 2h and 2h+1, two pixels per lane (the header above);
+//   WAVES == 4  wave q owns quad q, one pixel per lane: twice the waves for the same work -- the form for views whose half-tile
+//               grid does not fill the machine (BlendBwdParams::half_tiles, chosen in gsr_api.hip: blend_bwd_half_tiles).
+// A segment holds one list entry per thread (LDS 11.4 / 22.8 KB per workgroup of two / four waves: 7 waves per SIMD either way).
 
-__global__ void __launch_bounds__(256)
+// One pixel of a lane: its position, loss gradient, last contributor and the backward state (T, B: file header).
+struct BwdPixel {
+	typedef float v2f __attribute__((vector_size(8)));
+	v2f pxy, dprg;
+	float dpb, T, B;
+	uint32_t last;
+};
+
+template <int WAVES>
+__global__ void __launch_bounds__(64 * WAVES)
 blend_bwd_kernel(const BlendBwdParams p)
 {
-	static_assert(BWD_SEG == 256, "one thread per entry of a segment");
+	static_assert(WAVES == 2 || WAVES == 4, "half tiles or quads");
+	constexpr bool PAIRS = WAVES == 2;          // two pixels per lane
+	constexpr int BWD_THREADS = 64 * WAVES;
+	constexpr int BWD_SEG = BWD_THREADS;        // list entries accumulated in LDS per segment; thread i stages entry i of the segment
 	__shared__ float4 s_rec[BWD_SEG][3];   // per entry of the segment: (x, y, A', B') (C', opacity, r, g) (b, -, -, -)
 	__shared__ float s_acc[9][BWD_SEG];
 	__shared__ uint32_t s_slot[BWD_SEG];
-	__shared__ uint8_t s_flag[BWD_SEG];    // bit q: quad q of the tile blends the entry (a byte each: 7 workgroups per CU fit the 160 KiB of LDS)
-	__shared__ uint32_t s_wmax[4];
+	__shared__ uint8_t s_flag[BWD_SEG];    // bit q: quad q of the tile blends the entry
+	__shared__ uint32_t s_wmax[QUADS_PER_TILE];
 
 	const int tile = tile_assignment((int)blockIdx.x, p.deal);
 	if (tile >= p.tiles) return;
 	const int tile_x = tile % p.grid_x, tile_y = tile / p.grid_x;
-	const int quad = (int)wave_uniform_u32((uint32_t)wave_id());   // scalar: the LDS record address is SGPR arithmetic
+	const int w = (int)wave_uniform_u32((uint32_t)wave_id());   // scalar: the LDS record address is SGPR arithmetic
+	const int qa = PAIRS ? 2 * w : w, qb = qa + 1;              // the wave's (left) quad and, in pairs, the right one
 	const int l = lane_id(), tid = (int)threadIdx.x;
-	const int qx0 = tile_x * TILE + (quad & 1) * 8, qy0 = tile_y * TILE + (quad >> 1) * 8;
-	const int px = qx0 + (l & 7), py = qy0 + (l >> 3);
-	const bool inside = px < p.W && py < p.H;
 	typedef float v2f __attribute__((vector_size(8)));
-	const v2f pxy = {(float)px, (float)py};
 	const uint2 range = p.ranges[tile];
-	const size_t pix = (size_t)py * p.W + px;
 	const size_t plane = (size_t)p.H * p.W;
 
-	const uint32_t last_contributor = inside ? p.n_contrib[pix] : 0u;
-	// entries at or behind wmax touch no pixel of the quad; bmax: none of the tile
-	const uint32_t wmax = wave_uniform_u32(wave_max_u32(last_contributor));
-	if (l == 0) s_wmax[quad] = wmax;
+	// lane l: pixel (l & 7, l >> 3) of quad qa (pixel a) and, in pairs, the pixel 8 columns to its right, in quad qb (pixel b)
+	auto load_pixel = [&](int px, int py, BwdPixel& s) {
+		const bool inside = px < p.W && py < p.H;
+		const size_t pix = (size_t)py * p.W + px;
+		s.pxy = (v2f){(float)px, (float)py};
+		s.last = inside ? p.n_contrib[pix] : 0u;
+		const float T_final = inside ? p.final_T[pix] : 0.f;
+		float dpr = 0.f, dpg = 0.f, dpb = 0.f;
+		if (inside) {
+			dpr = p.dL_dpix[pix];
+			dpg = p.dL_dpix[plane + pix];
+			dpb = p.dL_dpix[2 * plane + pix];
+		}
+		s.dprg = (v2f){dpr, dpg};
+		s.dpb = dpb;
+		// the pixel's state behind its last contributor: T = the final transmittance, B = (everything blended behind, i.e. the
+		// background) . dpix
+		s.T = T_final;
+		s.B = T_final * (p.bg[0] * dpr + p.bg[1] * dpg + p.bg[2] * dpb);
+	};
+	const int pxa = tile_x * TILE + (qa & 1) * 8 + (l & 7), py = tile_y * TILE + (qa >> 1) * 8 + (l >> 3);
+	BwdPixel A, Bp;
+	load_pixel(pxa, py, A);
+	if (PAIRS) load_pixel(pxa + 8, py, Bp);
+
+	// entries at or behind s_wmax[q] touch no pixel of quad q; bmax: none of the tile
+	const uint32_t wmax_a = wave_uniform_u32(wave_max_u32(A.last));
+	const uint32_t wmax_b = PAIRS ? wave_uniform_u32(wave_max_u32(Bp.last)) : 0u;
+	if (l == 0) {
+		s_wmax[qa] = wmax_a;
+		if (PAIRS) s_wmax[qb] = wmax_b;
+	}
 	__syncthreads();
 	const uint32_t bmax = wave_uniform_u32(max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3])));
 
-	const float T_final = inside ? p.final_T[pix] : 0.f;
-	float dpr = 0.f, dpg = 0.f, dpb = 0.f;
-	if (inside) {
-		dpr = p.dL_dpix[pix];
-		dpg = p.dL_dpix[plane + pix];
-		dpb = p.dL_dpix[2 * plane + pix];
-	}
-	// the pixel's state behind its last contributor: T = the final transmittance, B = (everything blended behind, i.e. the
-	// background) . dpix
-	float T = T_final;
-	float B = T_final * (p.bg[0] * dpr + p.bg[1] * dpg + p.bg[2] * dpb);
 	// lanes 0, 8, .., 56 deliver the eight packed totals, lanes 1, 17, 33, 49 the four row sums of the ninth
 	// (wave_reduce9_swap_f32): one ds_add_f32 with twelve active lanes
 	const bool red_ninth = (l & 15) == 1;
 	const bool red_lane = ((l & 7) == 0) || red_ninth;
 	const int red_off = (red_ninth ? 8 : wave_swap9_component(l)) * BWD_SEG;
-	const v2f dprg = {dpr, dpg};
 
 	const int seg_first = (int)((bmax + BWD_SEG - 1) / BWD_SEG) - 1, seg_last = 0;
-	// The segment's records are staged ONCE per tile, by all 256 threads (thread i: list entry seg_lo + i), and only for the entries
-	// some quad of the tile blended (the forward blend's flags: a quarter of the entries of a 1080p view, a tenth at 640 x 480 with
-	// 2 M Gaussians).  The list entries and flags of the NEXT segment are asked for while this one is walked.
+	// The segment's records are staged ONCE per tile, by all the workgroup's threads (thread i: list entry seg_lo + i), and only
+	// for the entries some quad of the tile blended (the forward blend's flags: a quarter of the entries of a 1080p view, a tenth
+	// at 640 x 480 with 2 M Gaussians).  The list entries and flags of the NEXT segment are asked for while this one is walked.
 	auto seg_flags = [&](int seg_) -> uint32_t {
 		const uint32_t e = (uint32_t)seg_ * BWD_SEG + (uint32_t)tid;
 		uint32_t f = 0u;
@@ -111,11 +147,62 @@ blend_bwd_kernel(const BlendBwdParams p)
 		const uint32_t e = (uint32_t)seg_ * BWD_SEG + (uint32_t)tid;
 		return e < bmax ? p.point_list[range.x + e] : 0u;
 	};
+
+	// The alpha test of one pixel.  `ok` = the lanes whose pixel blends the entry (okl: this lane's).  In pairs it is the AND of
+	// three ballots of compares, a lane mask in an SGPR pair that the selects below take as their scalar operand (a ballot of the
+	// combined predicate, carried across the pair's branches, costs a v_cndmask + v_cmp per test); with one pixel per lane the
+	// plain predicate gives the shorter visit (one select less).
+	struct Hit {
+		v2f dxy;
+		float G, alpha;
+		unsigned long long ok;
+		bool okl;
+	};
+	auto test = [](const BwdPixel& s, const float4 g0, const float4 g1, uint32_t pos) -> Hit {
+		Hit h;
+		h.dxy = (v2f){g0.x, g0.y} - s.pxy;
+		const float dx = h.dxy[0], dy = h.dxy[1];
+		const float pw = g0.z * dx * dx + g1.x * dy * dy + g0.w * dx * dy;
+		h.G = __builtin_amdgcn_exp2f(pw);
+		h.alpha = fminf(0.99f, g1.y * h.G);
+		h.okl = (pos < s.last) && !(pw > 0.0f) && !(h.alpha < 1.0f / 255.0f);
+		h.ok = PAIRS ? wave_ballot(pos < s.last) & wave_ballot(!(pw > 0.0f)) & wave_ballot(!(h.alpha < 1.0f / 255.0f)) : wave_ballot(h.okl);
+		return h;
+	};
+	// ... and its gradient terms: the nine products of the pixel (order of the LDS accumulators below) and its state update.
+	// Lanes whose pixel does not blend the entry contribute exact zeros and keep their state.  The per-Gaussian constants
+	// (opacity, -1/2, W/2, H/2, the conic in the mean2D terms) are applied after the reduction (preprocess_bwd, partials.h);
+	// pairs of products ride in v_pk_mul_f32.
+	struct Terms {
+		v2f c01, t, m56;
+		float c3, t7, wG;
+	};
+	auto terms = [](BwdPixel& s, const Hit& h, const float4 g1, float gb) -> Terms {
+		const float rinv = __builtin_amdgcn_rcpf(1.f - h.alpha);
+		const float Tn = s.T * rinv;   // the transmittance in FRONT of this entry
+		// dL/dalpha = T_j (c_j . dpix) - B_{j+1} / (1 - alpha_j)   (the running scalar: file header)
+		const float cdp = g1.z * s.dprg[0] + g1.w * s.dprg[1] + gb * s.dpb;
+		const float dL_dalpha = cdp * Tn - s.B * rinv;
+		const float am = PAIRS ? mask_select0_f32(h.ok, h.alpha) : (h.okl ? h.alpha : 0.f);
+		const float dLm = PAIRS ? mask_select0_f32(h.ok, dL_dalpha) : (h.okl ? dL_dalpha : 0.f);
+		const float dcol = am * Tn;
+		Terms r;
+		r.wG = dLm * h.G;
+		r.c01 = s.dprg * (v2f){dcol, dcol};
+		r.t = h.dxy * (v2f){r.wG, r.wG};            // w dx, w dy
+		r.m56 = h.dxy * (v2f){r.t[0], r.t[0]};      // w dx dx, w dx dy
+		r.c3 = dcol * s.dpb;
+		r.t7 = r.t[1] * h.dxy[1];                    // w dy dy
+		s.T = PAIRS ? mask_select_f32(h.ok, Tn, s.T) : (h.okl ? Tn : s.T);
+		s.B += dcol * cdp;   // (dcol is zero where the entry is not blended)
+		return r;
+	};
+
 	uint32_t flags_next = seg_first >= 0 ? seg_flags(seg_first) : 0u, gid_next = seg_first >= 0 ? seg_gid(seg_first) : 0u;
 	for (int seg = seg_first; seg >= seg_last; seg--) {
 		const uint32_t seg_lo = (uint32_t)seg * BWD_SEG;
 		const uint32_t seg_hi = min(bmax, seg_lo + BWD_SEG);
-		for (int i = tid; i < 9 * BWD_SEG; i += 256) (&s_acc[0][0])[i] = 0.f;
+		for (int i = tid; i < 9 * BWD_SEG; i += BWD_THREADS) (&s_acc[0][0])[i] = 0.f;
 		{
 			const uint32_t f = flags_next, gid = gid_next;
 			uint32_t slot = 0xFFFFFFFFu;
@@ -143,7 +230,10 @@ blend_bwd_kernel(const BlendBwdParams p)
 		__syncthreads();
 
 		for (int b = (int)((seg_hi - seg_lo - 1u) >> 6); b >= 0; b--) {
-			unsigned long long m = wave_ballot((((uint32_t)s_flag[b * 64 + l] >> quad) & 1u) != 0u);
+			const uint32_t fl = s_flag[b * 64 + l];
+			// per quad of the half the entries of this batch it blends; the wave walks their union
+			const unsigned long long ma = wave_ballot(((fl >> qa) & 1u) != 0u), mb = PAIRS ? wave_ballot(((fl >> qb) & 1u) != 0u) : 0ull;
+			unsigned long long m = ma | mb;
 			const int base = (int)seg_lo + b * 64;
 			const float4(*rec_b)[3] = &s_rec[b * 64];
 			while (m) {
@@ -157,44 +247,49 @@ blend_bwd_kernel(const BlendBwdParams p)
 				const float4 g0 = rec_b[bit][0];
 				const float4 g1 = rec_b[bit][1];
 				const float gb = rec_b[bit][2].x;
-				const v2f dxy = (v2f){g0.x, g0.y} - pxy;
-				const float dx = dxy[0], dy = dxy[1];
-				const float pw = g0.z * dx * dx + g1.x * dy * dy + g0.w * dx * dy;
-				const float G = __builtin_amdgcn_exp2f(pw);
-				const float alpha = fminf(0.99f, g1.y * G);
-				const bool ok = (pos < last_contributor) && !(pw > 0.0f) && !(alpha < 1.0f / 255.0f);
-				if (wave_ballot(ok) == 0ull) continue;  // wave-uniform
-				const float rinv = __builtin_amdgcn_rcpf(1.f - alpha);
-				const float Tn = T * rinv;   // the transmittance in FRONT of this entry
-				// dL/dalpha = T_j (c_j . dpix) - B_{j+1} / (1 - alpha_j)   (the running scalar: file header)
-				const float cdp = g1.z * dpr + g1.w * dpg + gb * dpb;
-				const float dL_dalpha = cdp * Tn - B * rinv;
-				// lanes that do not blend this entry contribute exact zeros and keep their state
-				const float am = ok ? alpha : 0.f;
-				const float dLm = ok ? dL_dalpha : 0.f;
-				const float dcol = am * Tn;
-				// the per-Gaussian constants (opacity, -1/2, W/2, H/2, the conic in the mean2D terms) are applied
-				// after the reduction (preprocess_bwd, partials.h); pairs of products ride in v_pk_mul_f32
-				const float wG = dLm * G;
-				const v2f c01 = dprg * (v2f){dcol, dcol};
-				const v2f t = dxy * (v2f){wG, wG};          // sum w dx, sum w dy
-				const v2f m56 = dxy * (v2f){t[0], t[0]};    // sum w dx dx, sum w dx dy
+				// only the flagged quads of the pair are tested (wave-uniform branches on the two flag bits)
+				Hit ha, hb;
+				unsigned long long oka = 0ull, okb = 0ull;
+				if ((ma >> bit) & 1ull) {
+					ha = test(A, g0, g1, pos);
+					oka = ha.ok;
+				}
+				if (PAIRS && ((mb >> bit) & 1ull)) {
+					hb = test(Bp, g0, g1, pos);
+					okb = hb.ok;
+				}
 				// order of the nine sums in the LDS accumulators: 0 colour r, 1 w dx, 2 w dx dx, 3 colour b, 4 colour g, 5 w dy,
 				// 6 w dx dy, 7 w dy dy, 8 w -- chosen so that the halves of each packed product sit four apart: the
 				// butterfly's first level then adds (v0, v4) + (v1, v5) and (v2, v6) + (v3, v7) as register pairs
-				// without a move (wave_reduce9_swap_f32); the segment write-out below restores the slot order
+				// without a move (wave_reduce9_swap_f32); the segment write-out below restores the slot order.
+				// Where both pixels of the lane blend the entry their products are summed in the lane: ONE reduction per
+				// (half tile, entry).
+				Terms r;
+				if (PAIRS && oka && okb) {
+					const Terms ra = terms(A, ha, g1, gb), rb = terms(Bp, hb, g1, gb);
+					r.c01 = ra.c01 + rb.c01;
+					r.t = ra.t + rb.t;
+					r.m56 = ra.m56 + rb.m56;
+					r.c3 = ra.c3 + rb.c3;
+					r.t7 = ra.t7 + rb.t7;
+					r.wG = ra.wG + rb.wG;
+				} else if (oka) {
+					r = terms(A, ha, g1, gb);
+				} else if (PAIRS && okb) {
+					r = terms(Bp, hb, g1, gb);
+				} else {
+					continue;   // wave-uniform
+				}
 				float v[9];
-				v[0] = c01[0];
-				v[4] = c01[1];
-				v[1] = t[0];
-				v[5] = t[1];
-				v[2] = m56[0];
-				v[6] = m56[1];
-				v[3] = dcol * dpb;
-				v[7] = t[1] * dy;
-				v[8] = wG;
-				T = ok ? Tn : T;
-				B += dcol * cdp;   // (dcol is zero where the entry is not blended)
+				v[0] = r.c01[0];
+				v[4] = r.c01[1];
+				v[1] = r.t[0];
+				v[5] = r.t[1];
+				v[2] = r.m56[0];
+				v[6] = r.m56[1];
+				v[3] = r.c3;
+				v[7] = r.t7;
+				v[8] = r.wG;
 				float packed, ninth_row;
 				wave_reduce9_swap_f32(v, packed, ninth_row);
 				GSR_OPAQUE_F32(packed);      // keep the last butterfly adds fused with their DPP moves (the compiler otherwise
@@ -205,7 +300,7 @@ blend_bwd_kernel(const BlendBwdParams p)
 		__syncthreads();
 
 		// write every touched entry of the segment to its instance slot
-		for (int i = tid; i < (int)(seg_hi - seg_lo); i += 256) {
+		for (int i = tid; i < (int)(seg_hi - seg_lo); i += BWD_THREADS) {
 			const uint32_t slot = s_slot[i];
 			float any = 0.f;
 #pragma unroll
@@ -225,7 +320,10 @@ blend_bwd_kernel(const BlendBwdParams p)
 
 int launch_blend_bwd(const BlendBwdParams& p, hipStream_t stream)
 {
-	GSR_LAUNCH(blend_bwd_kernel, tile_grid(p.deal), 256, stream, p);
+	if (p.half_tiles)
+		GSR_LAUNCH(blend_bwd_kernel<2>, tile_grid(p.deal), 128, stream, p);
+	else
+		GSR_LAUNCH(blend_bwd_kernel<4>, tile_grid(p.deal), 256, stream, p);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

@@ -165,6 +165,23 @@ static int xcd_deal_mode(int tiles)
 	while (c > 1 && tiles < 8 * 16 * c) c >>= 1;
 	return c;
 }
+// The backward blend's form (blend_bwd.hip): one wave per 16x8 half tile (two pixels per lane, one gradient reduction per half and
+// entry) where the view has enough tiles to keep the machine busy with half as many waves, one wave per 8x8 quad below that.
+// Measured (profiles/r07_c_*): at C3 (8 160 tiles) the half tiles take blend_bwd from 0.403 to 0.370 ms; at C2 (3 225 tiles) they
+// cost +13 %, at a C4 / C5 view (1 200 / 1 410 tiles) +60 / +43 % -- there the half-tile grid is under 7 waves per SIMD and the
+// kernel waits for its longest tiles, which now run at half the parallelism.  Threshold: 24 tiles per CU of the MI355X (6 144).
+// GSR_BWD_HALF_TILES=0/1 overrides (A/B handle, tests); read per call, so that a test can select either form in one process.
+static bool blend_bwd_half_tiles(int tiles)
+{
+	const char* e = getenv("GSR_BWD_HALF_TILES");
+	if (e && *e) {
+		static bool logged = false;
+		if (!logged) fprintf(stderr, "[gsr] environment override GSR_BWD_HALF_TILES=%s\n", e);
+		logged = true;
+		return atoi(e) != 0;
+	}
+	return tiles >= 24 * 256;
+}
 // The depth sort's significant bits when it runs on key - DEPTH_KEY_BIAS with 9-bit digits (27 = three passes); 0 = the plain
 // sort of 32 bits in four passes.  GSR_DEPTH_SORT_9BIT=0 selects the plain sort (A/B handle); GSR_DEPTH_SORT_BITS=n (tests)
 // narrows the range so that ordinary scenes take the re-sort path.
@@ -655,6 +672,7 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 		bp.contrib = bs.contrib; bp.contrib_stride = (size_t)R;
 		bp.W = W; bp.H = H; bp.grid_x = grid_x; bp.tiles = tiles;
 		bp.deal = make_tile_deal(tiles, grid_x, xcd_deal_mode(tiles));
+		bp.half_tiles = blend_bwd_half_tiles(tiles) ? 1 : 0;
 		if ((st = launch_blend_bwd(bp, stream)) != GSR_OK) return fail(st);
 	}
 	PROF_BWD(2);

@@ -105,6 +105,7 @@ struct BlendBwdParams {
 	size_t contrib_stride;
 	int W, H, grid_x, tiles;
 	TileDeal deal;          // blend.h: the workgroup -> XCD deal of the tiles
+	int half_tiles;         // 1: one wave per 16x8 half tile, two pixels per lane; 0: one wave per 8x8 quad (blend_bwd.hip)
 };
 int launch_blend_bwd(const BlendBwdParams& p, hipStream_t stream);
 
