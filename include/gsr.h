@@ -161,6 +161,22 @@ typedef struct gsr_forward_args {
  * in LDS -- eight launches fewer, the arrangement for the small and mid-size views a SLAM session starts with. */
 #define GSR_BINNING_DEPTH_FIRST 32
 #define GSR_BINNING_TILE_FIRST 64
+/* ... and one for renders that no backward pass follows (a viewer, an evaluation pass, any no-grad render; ignored by
+ * gsr_backward): out_color, radii and *num_rendered are the same, bit for bit, as without it, but nothing the backward pass
+ * would need is prepared -- the binning buffer holds only the instance lists, their sort tables and one spare word per
+ * instance (no gradient slots, no slot flags, no per-quad contribution flags), the image buffer only the tile ranges (no final
+ * T, no last contributor), the forward blend stores neither, the clamp mask and the list of long runs are not written.
+ * gsr_binning_bytes_for / gsr_image_bytes_for give the sizes it requests.  The three scratch buffers are NOT valid input to
+ * gsr_backward: a cheap guard catches the usual mistake -- gsr_forward remembers, per thread, the geometry buffer of its last
+ * forward-only call (a training forward on that buffer clears the record) and gsr_backward refuses that buffer with
+ * GSR_ERR_INVALID_ARG.  A backward pass on another thread is not caught.
+ * Works with both GSR_BINNING_* arrangements, GSR_CULL_EMPTY_TILES, colors_precomp, cov3D_precomp and GSR_RAW_*.
+ * With sh_adam->lazy set (and only then: a non-lazy sh_adam is GSR_ERR_INVALID_ARG) the lazy rows are READ-ONLY: a visible row
+ * that lags behind (sh_adam->step - 1) is evaluated at its caught-up value -- the same zero-gradient steps, the same arithmetic
+ * as the training forward, taken in registers and LDS -- and nothing is written (not param, not the moments, not row_step).  A
+ * caller whose tensor has taken S steps passes step = S + 1 and lr_past[0] = the learning rates of step S: the image is then
+ * the one a training forward renders after gsr_sh_adam_flush. */
+#define GSR_FORWARD_ONLY 128
 
 /* Rasterizer::forward, cuda_rasterizer/rasterizer_impl.cu:198-336.
  * Fills out_color and radii, returns the number of (tile, Gaussian) instances in
@@ -334,6 +350,8 @@ int gsr_sh_adam_from_packed_views(int P, int D, int M, int n_views, const float*
                                   long long msg_stride, float scale, float* shs, const gsr_sh_adam* sh_adam, void* stream);
 /* Gaussians with radii > 0 in the last gsr_forward of the calling thread (-1 before the first; 0 after a call with P == 0) */
 int gsr_last_visible_count(void);
+/* 1 if the last gsr_forward of the calling thread had GSR_FORWARD_ONLY set, 0 if not, -1 before the first call */
+int gsr_last_forward_only(void);
 /* Diagnostic: forward passes of the calling thread whose depth sort ran a second time.  The depth sort takes three passes over 27
  * bits of (key - bits(0.2f)) -- every visible Gaussian has z > 0.2 -- and the host learns the largest key of the view with the
  * instance count; a view with a Gaussian at z >= 13 107 (or a depth that is not a number) is sorted again on all 32 bits.  The
@@ -509,6 +527,9 @@ int gsr_neighborhood_depth_pinhole(int N, int width, float fx, float fy, float c
 size_t gsr_geometry_bytes(int P);
 size_t gsr_binning_bytes(int num_rendered);
 size_t gsr_image_bytes(int width, int height);
+/* ... for a call with these raw_params bits: with GSR_FORWARD_ONLY the smaller layouts of that mode, otherwise the two above */
+size_t gsr_binning_bytes_for(int num_rendered, int raw_params);
+size_t gsr_image_bytes_for(int width, int height, int raw_params);
 size_t gsr_knn_scratch_bytes(int P);
 
 /* Optional per-stage timing with HIP events recorded on the caller's stream (process-wide switch,

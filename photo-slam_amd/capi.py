@@ -127,6 +127,7 @@ class DensifyGatherArgs(C.Structure):
 
 
 RAW_OPACITY, RAW_SCALING, RAW_ROTATION = 1, 2, 4   # GSR_RAW_* of include/gsr.h
+CULL_EMPTY_TILES, FORWARD_ONLY = 8, 128             # GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY
 
 
 # every symbol include/gsr.h declares
@@ -139,6 +140,7 @@ EXPORTED_SYMBOLS = [
     "gsr_neighborhood_depth_pinhole", "gsr_packed_view_words", "gsr_pack_scratch_bytes", "gsr_pack_color_view", "gsr_pack_view_plan",
     "gsr_sh_grad_from_packed_views", "gsr_sh_adam_from_packed_views", "gsr_last_visible_count", "gsr_check_packed_views", "gsr_depth_resort_count",
     "gsr_host_wait_stats", "gsr_binning_tile_first", "gsr_densify_morton_scratch_bytes",
+    "gsr_binning_bytes_for", "gsr_image_bytes_for", "gsr_last_forward_only",
 ]
 
 _libs = {}
@@ -178,6 +180,12 @@ def load(path=None):
         getattr(L, n).argtypes = [i32]
     L.gsr_image_bytes.restype = sz
     L.gsr_image_bytes.argtypes = [i32, i32]
+    L.gsr_binning_bytes_for.restype = sz
+    L.gsr_binning_bytes_for.argtypes = [i32, i32]
+    L.gsr_image_bytes_for.restype = sz
+    L.gsr_image_bytes_for.argtypes = [i32, i32, i32]
+    L.gsr_last_forward_only.restype = i32
+    L.gsr_last_forward_only.argtypes = []
     L.gsr_strerror.restype = C.c_char_p
     L.gsr_strerror.argtypes = [i32]
     L.gsr_last_hip_error.restype = i32

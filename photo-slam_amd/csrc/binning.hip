@@ -52,7 +52,8 @@ emit_instances_kernel(int P, uint32_t R, const uint32_t* __restrict__ order, con
 	// that holds the last slot: up to the end of the padded array) -- the backward pass then needs no memset of its own in
 	// front of the blend (two 5 us fill kernels and the bubble behind them); it leaves the flags cleared again when it is done
 	// (sh_bwd_rows_kernel), so any number of backward passes may follow one forward pass.
-	{
+	// (touched == null: a forward-only pass, GSR_FORWARD_ONLY -- there are no flags)
+	if (touched != nullptr) {
 		const uint32_t c_end = (s0 + (uint32_t)EMIT_SLOTS >= R) ? touched_bytes : s0 + (uint32_t)EMIT_SLOTS;
 		for (uint32_t o = s0 + 4u * (uint32_t)l; o < c_end; o += 256u) *reinterpret_cast<uint32_t*>(touched + o) = 0u;
 	}

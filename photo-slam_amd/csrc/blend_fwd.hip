@@ -8,11 +8,16 @@
 // Structure: see blend.h.  The per-pair arithmetic is branch-free (select instead of the
 // reference's nested continues), the next batch's list entries are prefetched while the current
 // batch is blended, and a wave leaves as soon as all its pixels are saturated.
+//
+// FWD_ONLY (GSR_FORWARD_ONLY, a render no backward pass follows): the same image from the same visits, without what only the
+// backward pass reads -- no contribution flags per (quad, entry), no final T and last contributor per pixel, and no scalar
+// bookkeeping of the flags (contrib_m) inside the visit loop.
 #include "blend.h"
 #include "kernels.h"
 
 namespace gsr {
 
+template <bool FWD_ONLY>
 __global__ void __launch_bounds__(64)
 blend_fwd_kernel(const BlendFwdParams p)
 {
@@ -61,7 +66,7 @@ blend_fwd_kernel(const BlendFwdParams p)
 		}
 		unsigned long long m = wave_ballot(keep);
 		wave_fence();
-		unsigned long long contrib_m = 0ull;   // entries of this batch that some pixel of the quad blends (scalar)
+		unsigned long long contrib_m = 0ull;   // entries of this batch that some pixel of the quad blends (scalar; training form only)
 		// The visit loop is bound by VALU issue AND by scalar issue (one scalar unit serves the CU's four SIMDs: ~4 SIMD cycles
 		// per scalar instruction against ~75 of VALU issue per visit; three more scalar instructions per visit cost 12 us per
 		// launch): its control flow is one scalar mask, the surviving entries not yet visited, cleared bit by bit with
@@ -82,16 +87,20 @@ blend_fwd_kernel(const BlendFwdParams p)
 			const unsigned long long ok_m = wave_ballot(!(pw > 0.0f)) & wave_ballot(!(alpha < 1.0f / 255.0f)) & ~done_m;
 			const float test_T = T * (1.f - alpha);
 			const unsigned long long below_m = wave_ballot(test_T < 0.0001f);
+			unsigned long long upd_m;
+			if constexpr (FWD_ONLY) {
+				upd_m = ok_m & ~below_m;   // (one s_andn2_b64: nobody wants the flags)
+			} else {
 #ifdef GSR_EMU
-			const unsigned long long upd_m = ok_m & ~below_m;
+			upd_m = ok_m & ~below_m;
 			if (upd_m) contrib_m |= 1ull << bit;
 #else
 			// upd_m = ok_m & ~below_m, and contrib_m |= upd_m ? 1 << bit : 0 off the SCC that s_andn2_b64 leaves (three scalar
 			// instructions for both; the compiler's select form of the second alone takes five)
-			unsigned long long upd_m;
 			asm volatile("s_andn2_b64 %[upd], %[ok], %[below]\n\ts_cbranch_scc0 1f\n\ts_bitset1_b64 %[c], %[bit]\n1:"
 			             : [upd] "=&s"(upd_m), [c] "+s"(contrib_m) : [ok] "s"(ok_m), [below] "s"(below_m), [bit] "s"(bit) : "scc");
 #endif
+			}
 			done_m |= ok_m & below_m;
 #ifdef GSR_EMU
 			const float wgt = mask_select0_f32(upd_m, alpha * T);
@@ -127,15 +136,17 @@ blend_fwd_kernel(const BlendFwdParams p)
 		const bool wave_done = ~done_m == 0ull;
 		// the backward pass walks the same batches: it visits only the entries flagged here (15 % of the entries that survive the
 		// quad rejection blend into no pixel -- alpha below 1/255 at every pixel centre, or every such pixel saturated)
-		if (have) p.contrib[(size_t)quad * p.contrib_stride + range.x + (uint32_t)(base + l)] = (uint8_t)((contrib_m >> l) & 1ull);
+		if (!FWD_ONLY && have) p.contrib[(size_t)quad * p.contrib_stride + range.x + (uint32_t)(base + l)] = (uint8_t)((contrib_m >> l) & 1ull);
 		if (wave_done) break;
 		wave_fence();  // all lanes have read this batch before the next one overwrites the slice
 	}
 	if (inside) {
 		const size_t pix = (size_t)py * p.W + px;
 		const size_t plane = (size_t)p.H * p.W;
-		p.final_T[pix] = T;
-		p.n_contrib[pix] = last_contributor;
+		if constexpr (!FWD_ONLY) {
+			p.final_T[pix] = T;
+			p.n_contrib[pix] = last_contributor;
+		}
 #ifdef GSR_EMU
 		const float Cr = Crg[0], Cg = Crg[1];
 #endif
@@ -147,7 +158,10 @@ blend_fwd_kernel(const BlendFwdParams p)
 
 int launch_blend_fwd(const BlendFwdParams& p, hipStream_t stream)
 {
-	GSR_LAUNCH(blend_fwd_kernel, quad_grid(p.deal), 64, stream, p);
+	if (p.forward_only)
+		GSR_LAUNCH(blend_fwd_kernel<true>, quad_grid(p.deal), 64, stream, p);
+	else
+		GSR_LAUNCH(blend_fwd_kernel<false>, quad_grid(p.deal), 64, stream, p);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

@@ -110,6 +110,10 @@ static gsr_status host_sync(HostSync** out)
 	return GSR_OK;
 }
 static thread_local int t_last_visible = -1;   // gsr_last_visible_count()
+static thread_local int t_last_forward_only = -1;   // gsr_last_forward_only()
+// the geometry buffer of this thread's last forward-only gsr_forward (GSR_FORWARD_ONLY): gsr_backward refuses it -- a cheap guard,
+// not a full check (a backward pass on another thread is not caught); a training forward on the same buffer clears it
+static thread_local const char* t_forward_only_geom = nullptr;
 // gsr_host_wait_stats(): how long the calling thread was blocked in gsr_forward's ONE host synchronisation (the instance count)
 static thread_local double t_sync_wait_us = 0.0;
 static thread_local long long t_sync_waits = 0;
@@ -262,17 +266,17 @@ static inline size_t geometry_bytes(int P)
 	GeometryState::carve(nullptr, (size_t)P, &b);
 	return b;
 }
-static inline size_t binning_bytes(int R)
+static inline size_t binning_bytes(int R, bool forward_only = false)
 {
 	size_t b = 0;
-	BinningState::carve(nullptr, (size_t)R, &b);
+	BinningState::carve(nullptr, (size_t)R, &b, forward_only);
 	return b;
 }
-static inline size_t image_bytes(int W, int H)
+static inline size_t image_bytes(int W, int H, bool forward_only = false)
 {
 	size_t b = 0;
 	const size_t T = (size_t)div_up(W, TILE) * div_up(H, TILE);
-	ImageState::carve(nullptr, (size_t)W * H, T, &b);
+	ImageState::carve(nullptr, (size_t)W * H, T, &b, forward_only);
 	return b;
 }
 
@@ -325,6 +329,8 @@ extern "C" {
 size_t gsr_geometry_bytes(int P) { return geometry_bytes(P < 0 ? 0 : P); }
 size_t gsr_binning_bytes(int R) { return binning_bytes(R < 0 ? 0 : R); }
 size_t gsr_image_bytes(int W, int H) { return (W <= 0 || H <= 0) ? 0 : image_bytes(W, H); }
+size_t gsr_binning_bytes_for(int R, int raw_params) { return binning_bytes(R < 0 ? 0 : R, (raw_params & GSR_FORWARD_ONLY) != 0); }
+size_t gsr_image_bytes_for(int W, int H, int raw_params) { return (W <= 0 || H <= 0) ? 0 : image_bytes(W, H, (raw_params & GSR_FORWARD_ONLY) != 0); }
 size_t gsr_knn_scratch_bytes(int P) { return knn_scratch_bytes(P < 0 ? 0 : P); }
 
 const char* gsr_strerror(int status)
@@ -354,6 +360,11 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 {
 	if (!a || !geometryBuffer || !binningBuffer || !imageBuffer || !num_rendered) return GSR_ERR_INVALID_ARG;
 	*num_rendered = 0;
+	// GSR_FORWARD_ONLY: no backward pass follows -- nothing is prepared for one (include/gsr.h)
+	const bool fwd_only = (a->raw_params & GSR_FORWARD_ONLY) != 0;
+	// (the read-only lazy rows exist; a non-lazy sh_adam means the caller expected a step the forward pass never takes)
+	if (fwd_only && a->sh_adam && !a->sh_adam->lazy) return GSR_ERR_INVALID_ARG;
+	t_last_forward_only = fwd_only ? 1 : 0;
 	int st = validate_common(a->P, a->D, a->M, a->width, a->height, a->shs, a->colors_precomp, a->scales, a->rotations,
 	                         a->cov3D_precomp);
 	if (a->P == 0) {   // src/rasterize_points.cu:81
@@ -370,9 +381,11 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	char* geom_chunk = geometryBuffer(geometry_ctx, geometry_bytes(P));
 	if (!geom_chunk) return GSR_ERR_ALLOC;
 	GeometryState g = GeometryState::carve(geom_chunk, (size_t)P);
-	char* img_chunk = imageBuffer(image_ctx, image_bytes(W, H));
+	if (fwd_only) t_forward_only_geom = geom_chunk;
+	else if (t_forward_only_geom == geom_chunk) t_forward_only_geom = nullptr;
+	char* img_chunk = imageBuffer(image_ctx, image_bytes(W, H, fwd_only));
 	if (!img_chunk) return GSR_ERR_ALLOC;
-	ImageState im = ImageState::carve(img_chunk, (size_t)W * H, (size_t)tiles);
+	ImageState im = ImageState::carve(img_chunk, (size_t)W * H, (size_t)tiles, nullptr, fwd_only);
 
 	HostSync* sync_ = nullptr;
 	if ((st = host_sync(&sync_)) != GSR_OK) return st;   // (GSR_ERR_UNSUPPORTED: a device ordinal beyond MAX_DEVICES)
@@ -394,6 +407,7 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	pp.raw_params = a->raw_params | (cov3D_stored() ? GSR_STORE_COV3D : 0);
 	pp.ranges = im.ranges; pp.tiles = tiles;   // zeroed there: rasterizer_impl.cu:310
 	pp.lazy = LazyAdam{};
+	pp.forward_only = fwd_only ? 1 : 0;
 	if (a->sh_adam && a->sh_adam->lazy) {   // lazy SH Adam: visible rows that lag behind take their missed steps first
 		if (!a->shs) return GSR_ERR_INVALID_ARG;
 		if ((st = make_lazy_adam(*a->sh_adam, a->shs, a->M, pp.lazy)) != GSR_OK) return st;
@@ -406,6 +420,10 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	RadixHostCount hc;
 	hc.pairs = g.wave_counts; hc.n = (int)wave_count_slots((size_t)P); hc.partials = g.count_partials; hc.host_out = t_sync.pinned_dev; hc.ready = t_sync.ev;
 
+	// the long runs are listed for the backward pass only (forward-only: the scans are handed no list)
+	uint32_t* const long_runs = fwd_only ? nullptr : g.long_runs;
+	uint32_t* const long_counts = fwd_only ? nullptr : g.long_counts;
+	const uint32_t long_capacity = fwd_only ? 0u : g.long_capacity;
 	// depth order (stable: equal depths keep ascending Gaussian id).  The first pass reads all P keys and drops the culled
 	// Gaussians (key 0xFFFFFFFF, RADIX_INVALID_KEY), leaving V in g.visible; the other three passes and the scan run over the
 	// V visible ones only (V = 0.47 P at C3).  order[V..P) is undefined, offsets[V..P) = R: the culled Gaussians used to sort
@@ -425,15 +443,15 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	auto offset_scan = [&]() {
 		// (g.sort_keys_b, the depth sort's spare buffer, is free again: it receives the emission's seeds -- binning.hip)
 		return launch_scan_rect_tiles(reinterpret_cast<const uint2*>(g.rect), g.order, g.offsets, g.rect_sorted, P, g.scan_scratch, stream,
-		                              g.visible, g.sort_keys_b, EMIT_SEED_STRIDE, (uint32_t)P, g.long_runs, g.long_counts, g.long_capacity);
+		                              g.visible, g.sort_keys_b, EMIT_SEED_STRIDE, (uint32_t)P, long_runs, long_counts, long_capacity);
 	};
 	const bool tile_first = binning_tile_first(a->raw_params, P, tiles);
 	if (tile_first) {
 		// no order among the Gaussians: the visible ones compacted by ascending id (g.order), their offsets, rectangles, the emission's
 		// seeds and the list of long runs in ONE pass; the counts reach the host from a one-workgroup launch in front of it
 		st = launch_compact_visible(g.tiles_touched, reinterpret_cast<const uint2*>(g.rect), g.wave_counts, hc.n, g.count_partials, g.order, g.offsets,
-		                            g.rect_sorted, P, t_sync.pinned_dev, t_sync.ev, stream, g.sort_keys_b, EMIT_SEED_STRIDE, (uint32_t)P, g.long_runs,
-		                            g.long_counts, g.long_capacity, g.visible);
+		                            g.rect_sorted, P, t_sync.pinned_dev, t_sync.ev, stream, g.sort_keys_b, EMIT_SEED_STRIDE, (uint32_t)P, long_runs,
+		                            long_counts, long_capacity, g.visible);
 		if (st != GSR_OK) return st;
 		PROF_FWD(2);
 	} else {
@@ -462,16 +480,16 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	if (!tile_first && narrow_bits && V64 != 0 && (t_sync.pinned[3] - DEPTH_KEY_BIAS) >> narrow_bits) {
 		// a depth beyond the three-pass range (z >= 13 107, or not a number): the order just produced is wrong for those keys --
 		// sort again on all 32 bits and redo the offsets (the list of long runs is built by the scan: its counters start over)
-		GSR_HIP(hipMemsetAsync(g.long_counts, 0, (size_t)LONG_LISTS * LONG_COUNT_STRIDE * sizeof(uint32_t), stream));
+		if (!fwd_only) GSR_HIP(hipMemsetAsync(g.long_counts, 0, (size_t)LONG_LISTS * LONG_COUNT_STRIDE * sizeof(uint32_t), stream));
 		if ((st = plain_depth_sort(nullptr)) != GSR_OK) return st;
 		if ((st = offset_scan()) != GSR_OK) return st;
 		t_depth_resorts++;
 	}
 	if (R64 > 0x7FFFFFFFull) return GSR_ERR_UNSUPPORTED;  // more than 2^31 instances
 	const int R = (int)R64;
-	char* bin_chunk = binningBuffer(binning_ctx, binning_bytes(R));
+	char* bin_chunk = binningBuffer(binning_ctx, binning_bytes(R, fwd_only));
 	if (!bin_chunk) return GSR_ERR_ALLOC;
-	BinningState bs = BinningState::carve(bin_chunk, (size_t)R);
+	BinningState bs = BinningState::carve(bin_chunk, (size_t)R, nullptr, fwd_only);
 
 	// (im.ranges: zeroed by preprocess_fwd)
 	uint32_t* point_list = bs.vals_a;
@@ -500,10 +518,11 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 		PROF_FWD(6);
 		if (tile_first) {
 			// the instances reached their tiles in id order: every tile's list by depth now (equal depths keep ascending id).  Scratch:
-			// the tile sort's spare pair and the forward blend's flag planes (4 R bytes, written only by the blend behind this)
+			// the tile sort's spare pair and R spare words (the forward blend's flag planes, written only by the blend behind this;
+			// forward-only: an array of their own)
 			const bool in_a = point_list == bs.vals_a;
 			if ((st = launch_tile_depth_sort(im.ranges, tiles, g.depth_key, point_list, in_a ? bs.keys_b : bs.keys_a, in_a ? bs.vals_b : bs.vals_a,
-			                                 reinterpret_cast<uint32_t*>(bs.contrib), stream)) != GSR_OK)
+			                                 bs.spare_words, stream)) != GSR_OK)
 				return st;
 		}
 	} else {
@@ -519,6 +538,7 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	bp.contrib = bs.contrib; bp.contrib_stride = (size_t)R;
 	bp.W = W; bp.H = H; bp.grid_x = grid_x; bp.tiles = tiles;
 	bp.deal = make_tile_deal(tiles, grid_x, xcd_deal_mode(tiles));
+	bp.forward_only = fwd_only ? 1 : 0;
 	if ((st = launch_blend_fwd(bp, stream)) != GSR_OK) return st;
 	PROF_FWD(8);
 	t_prof.fwd_done = t_prof.on == 1;
@@ -548,6 +568,8 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	if (a->dL_dcolor_view && !a->shs) return GSR_ERR_INVALID_ARG;
 	if (a->scales && (!a->dL_dscale || !a->dL_drot) && !a->geom_adam) return GSR_ERR_INVALID_ARG;
 	if (a->R > 0 && !a->binning_buffer) return GSR_ERR_INVALID_ARG;
+	// the buffers of a forward-only pass hold nothing a backward pass needs (GSR_FORWARD_ONLY; this thread's last such pass only)
+	if (t_forward_only_geom != nullptr && a->geom_buffer == t_forward_only_geom) return GSR_ERR_INVALID_ARG;
 	// (a stream cannot be made to wait for an event of its own future: refused HERE, before anything is enqueued and before the
 	// lazy rows' catch-up has advanced a step counter)
 	if (a->color_view_ready_stream && a->dL_dcolor_view && a->color_view_ready_stream == stream_) return GSR_ERR_INVALID_ARG;
@@ -828,6 +850,7 @@ int gsr_sh_adam_from_packed_views(int P, int D, int M, int n_views, const float*
 }
 
 int gsr_last_visible_count(void) { return t_last_visible; }
+int gsr_last_forward_only(void) { return t_last_forward_only; }
 long long gsr_depth_resort_count(void) { return t_depth_resorts; }
 int gsr_binning_tile_first(int raw_params, int P, int width, int height)
 {

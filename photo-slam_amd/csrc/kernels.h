@@ -65,6 +65,7 @@ struct PreprocessParams {
 	uint2* ranges;   // [tiles] per-tile instance ranges: zeroed here (identifyTileRanges fills only the tiles that have instances)
 	int tiles;
 	LazyAdam lazy;   // row_step != null: visible rows that lag behind (step - 1) are brought up to date before their SH evaluation
+	int forward_only;   // GSR_FORWARD_ONLY: no clamp mask; lazy rows are caught up in LDS only (nothing of the Adam state is written)
 };
 int launch_preprocess_fwd(const PreprocessParams& p, const GeometryState& g, hipStream_t stream);
 int launch_check_frustum(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t stream);
@@ -88,6 +89,7 @@ struct BlendFwdParams {
 	size_t contrib_stride;
 	int W, H, grid_x, tiles;
 	TileDeal deal;          // blend.h: the workgroup -> XCD deal of the tiles
+	int forward_only;       // GSR_FORWARD_ONLY: final_T, n_contrib and contrib are not written (and may be null)
 };
 int launch_blend_fwd(const BlendFwdParams& p, hipStream_t stream);
 

@@ -185,11 +185,15 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 			for (int r0 = 0; r0 < nvis; r0 += FWD_ROWS) {
 				const int count = (nvis - r0) < FWD_ROWS ? (nvis - r0) : FWD_ROWS;
 				wave_load_listed_rows(reinterpret_cast<const float4*>(p.shs), wave_first, nf4, r0, count, s_rows[w], s_list[w]);
-				if (lagging) wave_lazy_catch_up_listed(p.lazy, wave_first, r0, count, s_rows[w], s_list[w], s_lag[w]);
+				if (lagging) {
+					// (forward-only: the caught-up values live in the stage alone -- the row stays behind in HBM, shrows.h)
+					if (p.forward_only) wave_lazy_peek_listed(p.lazy, wave_first, r0, count, s_rows[w], s_list[w], s_lag[w]);
+					else wave_lazy_catch_up_listed(p.lazy, wave_first, r0, count, s_rows[w], s_list[w], s_lag[w]);
+				}
 				if (vis && rank >= r0 && rank < r0 + count) sh_row_to_rgb(s_rows[w][rank - r0], ncoef, direction(), rgb);
 				wave_fence();  // the next pass overwrites the slice
 			}
-			if (lag > 0) p.lazy.row_step[idx] = p.lazy.step - 1;
+			if (lag > 0 && !p.forward_only) p.lazy.row_step[idx] = p.lazy.step - 1;
 		} else if (vis) {
 			const float* sh = p.shs + (size_t)idx * p.M * 3;
 			const ShDir d = direction();
@@ -227,7 +231,7 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 			if (p.raw_params & GSR_RAW_OPACITY) opac = 1.0f / (1.0f + expf(-opac));   // getOpacityActivation, :68-71
 			g.rec[3 * (size_t)idx + 1] = make_float4(conz, opac, cr, cg);
 			g.rec[3 * (size_t)idx + 2] = make_float4(cb, __uint_as_float(rect_lo), __uint_as_float(rect_hi), 0.f);
-			g.clamped[idx] = clamp_bits;
+			if (!p.forward_only) g.clamped[idx] = clamp_bits;   // (read by the backward pass only)
 			reinterpret_cast<uint2*>(g.rect)[idx] = make_uint2(rect_lo, rect_hi);
 		}
 		g.depth_key[idx] = depth_key;

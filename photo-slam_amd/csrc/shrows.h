@@ -262,6 +262,32 @@ __device__ __forceinline__ void wave_lazy_catch_up_listed(const LazyAdam& a, siz
 	wave_fence();
 }
 
+// The read-only form for a forward pass no backward pass follows (GSR_FORWARD_ONLY): the same steps on the same values, but
+// only the stage receives the result -- param, the moments and row_step stay as they are in HBM (the row is still behind, and
+// the next training step or a flush takes the same steps again, bit for bit).
+__device__ __forceinline__ void wave_lazy_peek_listed(const LazyAdam& a, size_t first_row, int list_first, int count,
+                                                      float4 (*s_rows)[ROW_F4_PAD], const uint32_t* s_list, const uint32_t* s_lag)
+{
+	const int l = lane_id();
+	const int slot = l >> 4, col = l & 15;
+	wave_fence();
+	for (int j0 = 0; j0 < count; j0 += 4) {
+		const int j = j0 + slot;
+		if (col < ROW_F4 && j < count) {
+			const int lag = (int)s_lag[list_first + j];
+			if (lag > 0) {
+				const size_t i = (first_row + s_list[list_first + j]) * ROW_F4 + col;
+				float4 pv = s_rows[j][col];
+				float4 mv = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg) + i);
+				float4 vv = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg_sq) + i);
+				lazy_zero_grad_steps(a.t, lag, 1, col, pv, mv, vv);
+				s_rows[j][col] = pv;
+			}
+		}
+	}
+	wave_fence();
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // SH basis, cuda_rasterizer/auxiliary.h:22-39 + forward.cu:20-71 / backward.cu:20-139.
 __device__ static const float SHB_C0 = 0.28209479177387814f;

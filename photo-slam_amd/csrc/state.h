@@ -161,8 +161,13 @@ struct BinningState {
 	uint8_t*  touched;       // [R] 1 where the backward blend wrote the slot (cleared per backward; the slots themselves are not)
 	uint8_t*  contrib;       // [4][R] per quad of the tile: 1 where the forward blend found a pixel of the quad that blends the
 	                         // list entry (written by blend_fwd for the batches it walks, read by blend_bwd: blend.h)
+	uint32_t* spare_words;   // [R] the tile-first per-tile depth sort's third spare array: the contrib planes (written only by the
+	                         // blend behind it), or -- forward-only layout -- an array of its own
 
-	static BinningState carve(char* chunk, size_t R, size_t* bytes = nullptr)
+	// forward_only (GSR_FORWARD_ONLY): the lists and their sort tables at the same places as in the training layout (the tile sort
+	// and the tile-depth sort find their ping-pong arrays where they always do), then the spare words -- no gradient slots, no
+	// flags (partials / touched / contrib are null): 20 bytes per instance + the tables instead of ~70
+	static BinningState carve(char* chunk, size_t R, size_t* bytes = nullptr, bool forward_only = false)
 	{
 		BinningState b;
 		Carver c(chunk);
@@ -171,11 +176,20 @@ struct BinningState {
 		b.keys_b = c.take<uint32_t>(R);
 		b.vals_b = c.take<uint32_t>(R);
 		b.sort_scratch = c.take<uint32_t>(tile_sort_scratch_elems((int)R));
+		if (forward_only) {
+			b.partials = nullptr;
+			b.touched = nullptr;
+			b.contrib = nullptr;
+			b.spare_words = c.take<uint32_t>(R + 16);
+			if (bytes) *bytes = c.used(chunk) + 128;
+			return b;
+		}
 		b.partials = c.take<float>(4 * (size_t)SLOT_F4 * R);
 		// readers fetch flags 16 bytes at a time (+ 64); the clear covers touched_clear_bytes(R): a multiple of 256 bytes, because
 		// the runtime splits a memset of any other size into two kernels (body + tail, 5 us each)
 		b.touched = c.take<uint8_t>(touched_clear_bytes(R));
 		b.contrib = c.take<uint8_t>(4 * R + 64);
+		b.spare_words = reinterpret_cast<uint32_t*>(b.contrib);
 		if (bytes) *bytes = c.used(chunk) + 128;
 		return b;
 	}
@@ -198,12 +212,13 @@ struct ImageState {
 	uint32_t* n_contrib;  // [N]
 	uint2*    ranges;     // [T]
 
-	static ImageState carve(char* chunk, size_t N, size_t T, size_t* bytes = nullptr)
+	// forward_only (GSR_FORWARD_ONLY): the ranges alone (final_T / n_contrib are null)
+	static ImageState carve(char* chunk, size_t N, size_t T, size_t* bytes = nullptr, bool forward_only = false)
 	{
 		ImageState im;
 		Carver c(chunk);
-		im.final_T = c.take<float>(N);
-		im.n_contrib = c.take<uint32_t>(N);
+		im.final_T = forward_only ? nullptr : c.take<float>(N);
+		im.n_contrib = forward_only ? nullptr : c.take<uint32_t>(N);
 		im.ranges = c.take<uint2>(T);
 		if (bytes) *bytes = c.used(chunk) + 128;
 		return im;

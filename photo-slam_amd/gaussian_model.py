@@ -117,6 +117,21 @@ class FusedAdam:
         st["lr_hist"].insert(0, (d["lr"], d["lr_tail"]))
         del st["lr_hist"][st["window"]:]
 
+    def lazy_view_args(self, i):
+        """The lazy state of single-tensor group i for a FORWARD-ONLY render between train steps (GSR_FORWARD_ONLY with
+        gsr_sh_adam_lazy): the rows the view sees are caught up to the steps taken so far in registers only -- step is the next
+        one, lr_past[0] belongs to the last one taken -- and nothing is written.  None when the group is not lazy."""
+        grp = self.param_groups[i]
+        (p,) = grp["params"]
+        st = self.state.get(id(p))
+        if st is None or "row_step" not in st:
+            return None
+        hist = st["lr_hist"]
+        lr, lr_tail = hist[0] if hist else (float(grp["lr"]) * self.lr_scale, float(grp.get("lr_tail", grp["lr"])) * self.lr_scale)
+        return dict(exp_avg=st["exp_avg"], exp_avg_sq=st["exp_avg_sq"], lr=lr, lr_tail=lr_tail, beta1=self.betas[0],
+                    beta2=self.betas[1], eps=self.eps, step=st["step"] + 1, row_step=st["row_step"], window=st["window"],
+                    lr_past=[a for a, _ in hist], lr_tail_past=[b for _, b in hist])
+
     def is_lazy(self, p):
         st = self.state.get(id(p))
         return st is not None and "row_step" in st

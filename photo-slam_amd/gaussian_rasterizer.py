@@ -7,6 +7,7 @@ from dataclasses import dataclass
 
 import torch
 
+from . import capi
 from . import rasterize_points as rp
 
 
@@ -44,6 +45,10 @@ class GaussianRasterizationSettings:
     # extension: rasterize_points.RasterWorkspace -- the caller's persistent scratch buffers (None = fresh buffers per call, as the
     # reference)
     workspace_: object = None
+    # extension (GSR_FORWARD_ONLY, include/gsr.h): render without preparing a backward pass even with grad mode on (a viewer's
+    # renderFromPose).  GaussianRasterizer.forward also takes that path by itself under torch.no_grad() and when no input
+    # requires grad; the outputs then carry no grad_fn.
+    forward_only_: bool = False
 
 
 class GaussianRasterizerFunction(torch.autograd.Function):
@@ -89,6 +94,19 @@ class GaussianRasterizerFunction(torch.autograd.Function):
                 g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
 
 
+def _rasterize_forward_only(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s):
+    """The forward pass alone (GSR_FORWARD_ONLY): RasterizeGaussiansCUDA directly, no autograd node, no buffers kept.  Only the
+    lazy form of sh_adam_ concerns a forward pass (its rows are then read, not written)."""
+    lazy = s.sh_adam_ if s.sh_adam_ is not None and s.sh_adam_.get("row_step") is not None else None
+    with torch.no_grad():
+        _, color, radii, _, _, _ = rp.RasterizeGaussiansCUDA(
+            s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
+            s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
+            s.campos_, s.prefiltered_,
+            s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0) | capi.FORWARD_ONLY, lazy, s.workspace_)
+    return color, radii
+
+
 def rasterizeGaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
     """include/gaussian_rasterizer.h:78-100"""
     return GaussianRasterizerFunction.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
@@ -120,6 +138,13 @@ class GaussianRasterizer(torch.nn.Module):
         scales = scales if has_scales else empty
         rotations = rotations if has_rotations else empty
         cov3D_precomp = cov3D_precomp if has_cov3D_precomp else empty
+        # no backward pass can follow (grad mode off, or nothing to differentiate), or the caller says none will: the forward pass
+        # alone (GSR_FORWARD_ONLY -- the same image and radii, no scratch for a backward pass, no autograd node)
+        s = self.raster_settings_
+        if s.forward_only_ or not torch.is_grad_enabled() or not any(
+                t is not None and t.requires_grad
+                for t in (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)):
+            return _rasterize_forward_only(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, s)
         color, radii = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                           cov3D_precomp, self.raster_settings_)
         return color, radii

@@ -36,7 +36,7 @@ class GaussianRenderer:
     @staticmethod
     def render(viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color=None,
                scaling_modifier=1.0, use_override_color=False, fuse_activations=True, sh_grad_view=None, sh_adam=None, view_stats=None,
-               geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None):
+               geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None, forward_only=False):
         """returns (render, viewspace_points, visibility_filter, radii)
 
         fuse_activations (extension; False = the reference data flow): hand the raw opacity / scaling / rotation
@@ -47,17 +47,35 @@ class GaussianRenderer:
         GaussianRasterizationSettings.  training_outputs_only: the viewspace gradient and dL_dcov3D are not computed (for a caller
         whose densification statistics are fused: view_stats); implied by geom_adam.  cull_empty_tiles: instances of tiles in which
         no pixel can blend the Gaussian leave the list (same image and gradients; off by default -- measured a wash, DESIGN.md
-        section 10); the environment variable GSR_CULL_EMPTY_TILES=0/1, when set, overrides the argument (an A/B handle)."""
+        section 10); the environment variable GSR_CULL_EMPTY_TILES=0/1, when set, overrides the argument (an A/B handle).
+
+        forward_only (extension): no backward pass follows (a viewer's or an evaluation render; implied under torch.no_grad()) --
+        the rasterizer prepares nothing for one (GSR_FORWARD_ONLY), screenspace_points is a plain tensor, and on a model whose SH
+        rows are stepped lazily the rows are read as they are and caught up in registers only: the model is neither flushed nor
+        changed, and its lazy state survives for the next train step."""
         env = os.environ.get("GSR_CULL_EMPTY_TILES")
         if env:
             cull_empty_tiles = env == "1"
+        forward_only = bool(forward_only) or not torch.is_grad_enabled()
         # (with the fused geometry step nobody reads its gradient and the rasterizer never reads its values: no zero fill then)
         slim = geom_adam is not None or training_outputs_only
-        screenspace_points = (torch.empty_like if slim else torch.zeros_like)(pc.getXYZ(), requires_grad=True)
-        try:
-            screenspace_points.retain_grad()
-        except Exception:
-            pass
+        if forward_only:
+            screenspace_points = torch.zeros_like(pc.getXYZ())
+        else:
+            screenspace_points = (torch.empty_like if slim else torch.zeros_like)(pc.getXYZ(), requires_grad=True)
+            try:
+                screenspace_points.retain_grad()
+            except Exception:
+                pass
+        # a model whose SH rows are stepped lazily: a forward-only render reads the tensor as it is (no flush) and hands the lazy
+        # state over read-only -- the rows it sees are caught up in registers (gsr.h: GSR_FORWARD_ONLY with sh_adam->lazy)
+        lazy_view = None
+        if forward_only and sh_adam is None and not use_override_color and not pipe.convert_SHs_ and \
+                getattr(pc, "optimizer_", None) is not None and getattr(pc, "_features", None) is not None:
+            from .trainer import FEATURES_GROUP
+            lazy_view = pc.optimizer_.lazy_view_args(FEATURES_GROUP)
+            if lazy_view is not None:
+                sh_adam = lazy_view
         # SH evaluated in torch (convert_SHs_) or colours given: the rasterizer sees no SH tensor, so the SH extensions are off
         sh_in_rasterizer = not use_override_color and not pipe.convert_SHs_
         raw = 7 if fuse_activations and not pipe.compute_cov3D_ else 0
@@ -67,7 +85,7 @@ class GaussianRenderer:
             viewpoint_camera.camera_center_, False, raw,
             sh_grad_view if sh_in_rasterizer else None, sh_adam if sh_in_rasterizer else None, view_stats,
             geom_adam if raw == 7 else None, bool((geom_adam is not None or training_outputs_only) and raw == 7),
-            cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace)
+            cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace, forward_only_=forward_only)
         rasterizer = GaussianRasterizer(raster_settings)
         means3D = pc.getXYZ()
         means2D = screenspace_points
@@ -90,6 +108,8 @@ class GaussianRenderer:
             dir_pp_normalized = dir_pp / torch.norm(dir_pp, dim=1, keepdim=True)
             sh2rgb = sh_utils.eval_sh(pc.active_sh_degree_, shs_view, dir_pp_normalized)
             colors_precomp, has_color_precomp = torch.clamp_min(sh2rgb + 0.5, 0.0), True
+        elif lazy_view is not None:
+            shs, has_shs = pc._features, True   # (raw: getFeatures() would flush the lazy rows)
         else:
             shs, has_shs = pc.getFeatures(), True
         has_sr = not pipe.compute_cov3D_

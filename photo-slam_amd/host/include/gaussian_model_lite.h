@@ -273,6 +273,12 @@ public:
 	// persistent_workspace_ = false: fresh buffers per call, as the reference's resizeFunctional
 	bool persistent_workspace_ = true;
 	RasterWorkspace workspace_;
+	// A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe): forward-only
+	// (GSR_FORWARD_ONLY) into a second workspace of its own -- a view between a training forward and its backward must not
+	// overwrite the buffers that forward saved -- with lazily stepped SH rows read as they are: no flush, no counter advanced,
+	// nothing of the model touched.  Returns the [3,H,W] image.
+	torch::Tensor renderView(std::shared_ptr<GaussianKeyframe> kf);
+	RasterWorkspace view_workspace_;
 	bool early_gather_ = true;        // the exchange's all-gather waits for the colour gradients only, not for the whole backward pass
 	// The view-factored exchange in its PACKED form (include/gsr.h: gsr_pack_color_view): every rank sends only the rows its
 	// view sees -- 11.7 MB instead of 24 MB per rank and link at 2 M Gaussians.  The ranks agree on the message capacity by

@@ -90,6 +90,10 @@ struct GaussianRasterizationExtensions {
 	// persistent scratch buffers of a caller that renders iteration after iteration (rasterize_points.h: RasterWorkspace; the
 	// caller owns it and keeps it alive until the backward pass has run); nullptr = fresh buffers per call, as the reference
 	RasterWorkspace* workspace_ = nullptr;
+	// GSR_FORWARD_ONLY (include/gsr.h): render without preparing a backward pass even with grad mode on -- for code shaped like
+	// the reference's GaussianMapper::renderFromPose.  GaussianRasterizer(Ex)::forward also takes that path by itself when grad
+	// mode is off or no input requires grad; the outputs then carry no grad_fn.
+	bool forward_only_ = false;
 };
 
 class GaussianRasterizerFunctionEx : public torch::autograd::Function<GaussianRasterizerFunctionEx> {

@@ -30,6 +30,43 @@ struct GaussianPipelineParams {   // include/gaussian_parameters.h:41-49
 };
 #endif
 
+namespace gsr_renderer_detail {
+// A model whose SH rows are stepped lazily (this repository's GaussianModel, gaussian_model_lite.h: features_row_step_ defined):
+// the lazy state handed to a FORWARD-ONLY render read-only -- step = the next one, lr_past[0] = the learning rates of the last
+// one taken, so that the rows the view sees are caught up in registers to the steps taken so far (include/gsr.h:
+// GSR_FORWARD_ONLY) -- and the SH tensor as it is (in_lazy_step_ around getFeatures(): no flush).  false for any other model
+// (the reference's GaussianModel has no lazy rows).
+template <class Model>
+auto lazy_view(Model& m, ShAdamStep& s, torch::Tensor& shs, int)
+    -> decltype((void)m.features_row_step_, (void)m.features_lr_hist_, (void)m.in_lazy_step_, (void)m.groups_, bool())
+{
+	if (!m.features_row_step_.defined() || m.groups_.size() < 2) return false;
+	const auto& grp = m.groups_[1];
+	s = ShAdamStep();
+	s.exp_avg = grp.exp_avg;
+	s.exp_avg_sq = grp.exp_avg_sq;
+	s.step = grp.step + 1;
+	s.lr = m.features_lr_hist_.empty() ? grp.lr * m.lr_scale_ : m.features_lr_hist_[0].first;
+	s.lr_tail = m.features_lr_hist_.empty() ? grp.lr_tail * m.lr_scale_ : m.features_lr_hist_[0].second;
+	s.row_step = m.features_row_step_;
+	s.window = m.features_lazy_window_;
+	for (const auto& h : m.features_lr_hist_) {
+		s.lr_past.push_back(h.first);
+		s.lr_tail_past.push_back(h.second);
+	}
+	const bool was = m.in_lazy_step_;
+	m.in_lazy_step_ = true;
+	shs = m.getFeatures();
+	m.in_lazy_step_ = was;
+	return true;
+}
+template <class Model>
+bool lazy_view(Model&, ShAdamStep&, torch::Tensor&, long)
+{
+	return false;
+}
+}  // namespace gsr_renderer_detail
+
 class GaussianRenderer {
 public:
 	// returns (render, viewspace_points, visibility_filter, radii)
@@ -43,17 +80,27 @@ public:
 	    std::vector<torch::Tensor> view_stats = {} /* extension: GaussianRasterizationExtensions::view_stats_ */,
 	    GeomAdamStep geom_adam = GeomAdamStep() /* extension: GaussianRasterizationExtensions::geom_adam_ */,
 	    bool cull_empty_tiles = false /* extension: GaussianRasterizationExtensions::cull_empty_tiles_ */,
-	    RasterWorkspace* workspace = nullptr /* extension: GaussianRasterizationExtensions::workspace_ */)
+	    RasterWorkspace* workspace = nullptr /* extension: GaussianRasterizationExtensions::workspace_ */,
+	    bool forward_only = false /* extension: GaussianRasterizationExtensions::forward_only_ (implied when grad mode is off) */)
 	{
+		// forward_only (extension): no backward pass follows (a viewer's or an evaluation render) -- the rasterizer prepares
+		// nothing for one (GSR_FORWARD_ONLY), screenspace_points is a plain tensor, and on a model whose SH rows are stepped lazily
+		// the rows are read as they are and caught up in registers only: the model is neither flushed nor changed
+		forward_only = forward_only || !torch::GradMode::is_enabled();
 		// fuse_activations (extension): hand the raw opacity_/scaling_/rotation_ leaves to the rasterizer, which applies
 		// sigmoid / exp / normalize and their chain rule in-kernel (include/gsr.h raw_params)
 		// dummy input whose gradient is dL/dmean2D (the densification statistic)
 		// (with geom_adam.training_outputs_only nobody reads its gradient and the rasterizer never reads its values: the 12 P
 		// bytes are then not even zero-filled)
-		auto screenspace_points = geom_adam.training_outputs_only
-		                              ? torch::empty_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true))
-		                              : torch::zeros_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true));
-		screenspace_points.retain_grad();
+		torch::Tensor screenspace_points;
+		if (forward_only) {
+			screenspace_points = torch::zeros_like(pc->getXYZ(), torch::TensorOptions().requires_grad(false));
+		} else {
+			screenspace_points = geom_adam.training_outputs_only
+			                         ? torch::empty_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true))
+			                         : torch::zeros_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true));
+			screenspace_points.retain_grad();
+		}
 
 		const float tanfovx = std::tan(viewpoint_camera->FoVx_ * 0.5f);
 		const float tanfovy = std::tan(viewpoint_camera->FoVy_ * 0.5f);
@@ -69,6 +116,14 @@ public:
 		if (sh_in_rasterizer) ext.sh_adam_ = sh_adam;
 		ext.view_stats_ = view_stats;
 		ext.workspace_ = workspace;
+		ext.forward_only_ = forward_only;
+		torch::Tensor lazy_shs;
+		bool lazy_rows = false;
+		if (forward_only && sh_in_rasterizer && !sh_adam.row_step.defined()) {
+			ShAdamStep view_adam;
+			lazy_rows = gsr_renderer_detail::lazy_view(*pc, view_adam, lazy_shs, 0);
+			if (lazy_rows) ext.sh_adam_ = view_adam;
+		}
 		// (the same image and gradients either way; off by default: measured a wash, DESIGN.md section 10.  The caller's
 		// argument decides; the environment variable GSR_CULL_EMPTY_TILES=0/1, when set, overrides it -- an A/B handle)
 		static const int cull_env = [] { const char* e = std::getenv("GSR_CULL_EMPTY_TILES"); return (e && *e) ? (e[0] == '1' ? 1 : 0) : -1; }();
@@ -104,7 +159,7 @@ public:
 			colors_precomp = torch::clamp_min(sh2rgb + 0.5, 0.0);
 			has_color_precomp = true;
 		} else {
-			shs = pc->getFeatures();
+			shs = lazy_rows ? lazy_shs : pc->getFeatures();
 			has_shs = true;
 		}
 		auto result = rasterizer.forward(means3D, screenspace_points, opacity, has_shs, has_color_precomp, has_scales,

@@ -1,7 +1,10 @@
 // gaussian_rasterizer.cpp -- autograd glue, counterpart of src/gaussian_rasterizer.cpp:18-234.
 #include "gaussian_rasterizer.h"
 
+#include <initializer_list>
 #include <stdexcept>
+
+#include "../../../include/gsr.h"
 
 torch::Tensor GaussianRasterizer::markVisibleGaussians(torch::Tensor& positions)
 {
@@ -164,6 +167,33 @@ void validate_and_fill(const torch::Tensor& means3D, bool has_shs, bool has_colo
 	if (!has_cov3D_precomp) cov3D_precomp = empty;
 }
 
+// No backward pass can follow: grad mode is off, or none of the differentiable inputs requires grad
+bool no_backward(const std::initializer_list<const torch::Tensor*> inputs)
+{
+	if (!torch::GradMode::is_enabled()) return true;
+	for (const torch::Tensor* t : inputs)
+		if (t->defined() && t->requires_grad()) return false;
+	return true;
+}
+
+// The forward pass alone (GSR_FORWARD_ONLY): RasterizeGaussiansCUDA directly with the bit, no autograd node, no buffers kept.
+// Only the lazy form of sh_adam_ concerns a forward pass (its rows are then read, not written).
+std::tuple<torch::Tensor, torch::Tensor> forward_only_impl(const torch::Tensor& means3D, const torch::Tensor& sh,
+                                                           const torch::Tensor& colors_precomp, const torch::Tensor& opacities,
+                                                           const torch::Tensor& scales, const torch::Tensor& rotations,
+                                                           const torch::Tensor& cov3Ds_precomp, const GaussianRasterizationSettings& s,
+                                                           const GaussianRasterizationExtensions& e)
+{
+	torch::NoGradGuard no_grad;
+	const ShAdamStep lazy = e.sh_adam_.row_step.defined() ? e.sh_adam_ : ShAdamStep();
+	auto r = RasterizeGaussiansCUDA(s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_,
+	                                cov3Ds_precomp, s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_,
+	                                s.image_height_, s.image_width_, sh, s.sh_degree_, s.campos_, s.prefiltered_,
+	                                e.raw_params_ | (e.cull_empty_tiles_ ? GSR_CULL_EMPTY_TILES : 0) | GSR_FORWARD_ONLY, lazy,
+	                                e.workspace_);
+	return std::make_tuple(std::get<1>(r), std::get<2>(r));
+}
+
 }  // namespace
 
 torch::autograd::tensor_list GaussianRasterizerFunction::forward(
@@ -204,6 +234,10 @@ std::tuple<torch::Tensor, torch::Tensor> GaussianRasterizer::forward(
 {
 	validate_and_fill(means3D, has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp,
 	                  scales, rotations, cov3D_precomp);
+	// (a render no backward pass can follow -- NoGradGuard, or nothing to differentiate: the forward pass alone)
+	if (no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp}))
+		return forward_only_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings_,
+		                         GaussianRasterizationExtensions());
 	auto result = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
 	                                 raster_settings_);
 	return std::make_tuple(result[0], result[1]);
@@ -216,6 +250,10 @@ std::tuple<torch::Tensor, torch::Tensor> GaussianRasterizerEx::forward(
 {
 	validate_and_fill(means3D, has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp,
 	                  scales, rotations, cov3D_precomp);
+	if (extensions_.forward_only_ ||
+	    no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp}))
+		return forward_only_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings_,
+		                         extensions_);
 	auto result = GaussianRasterizerFunctionEx::apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
 	                                                  cov3D_precomp, raster_settings_, extensions_);
 	return std::make_tuple(result[0], result[1]);

@@ -34,6 +34,37 @@ std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians(torch::Tensor means
 	                 has(cov3Ds_precomp), sh, colors_precomp, scales, rotations, cov3Ds_precomp);
 }
 
+// GaussianRasterizer(Ex)::forward as a caller of the forward-only path reaches it: ex = GaussianRasterizerEx with raw_params /
+// GSR_CULL_EMPTY_TILES / forward_only_ (extension_forward_only), otherwise the reference's GaussianRasterizer; no_grad = under
+// torch::NoGradGuard.  (image, radii)
+std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_modes(torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh,
+                                                                   torch::Tensor colors_precomp, torch::Tensor opacities,
+                                                                   torch::Tensor scales, torch::Tensor rotations,
+                                                                   torch::Tensor cov3Ds_precomp, torch::Tensor bg, double scale_modifier,
+                                                                   torch::Tensor viewmatrix, torch::Tensor projmatrix, double tanfovx,
+                                                                   double tanfovy, int64_t image_height, int64_t image_width,
+                                                                   int64_t sh_degree, torch::Tensor campos, bool ex, int64_t raw_params,
+                                                                   bool extension_forward_only, bool no_grad)
+{
+	GaussianRasterizationSettings s((int)image_height, (int)image_width, (float)tanfovx, (float)tanfovy, bg,
+	                                (float)scale_modifier, viewmatrix, projmatrix, (int)sh_degree, campos, false);
+	auto has = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
+	c10::optional<torch::NoGradGuard> guard;
+	if (no_grad) guard.emplace();
+	if (!ex) {
+		GaussianRasterizer r(s);
+		return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
+		                 colors_precomp, scales, rotations, cov3Ds_precomp);
+	}
+	GaussianRasterizationExtensions e;
+	e.raw_params_ = (int)raw_params & 7;
+	e.cull_empty_tiles_ = (raw_params & 8) != 0;
+	e.forward_only_ = extension_forward_only;
+	GaussianRasterizerEx r(s, e);
+	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
+	                 colors_precomp, scales, rotations, cov3Ds_precomp);
+}
+
 torch::Tensor mark_visible(torch::Tensor means3D, torch::Tensor viewmatrix, torch::Tensor projmatrix)
 {
 	return markVisible(means3D, viewmatrix, projmatrix);
@@ -142,6 +173,12 @@ std::tuple<torch::Tensor, torch::Tensor> trainer_render(int64_t h, torch::Tensor
 	auto pkg = GaussianRenderer::render(make_kf(view, proj, campos, fovx, fovy, H, W), (int)H, (int)W, t->gaussians_, pipe,
 	                                    t->background_, override_color, 1.0f, false, fuse_activations);
 	return std::make_tuple(std::get<0>(pkg), std::get<3>(pkg));
+}
+// TrainStep::renderView: a forward-only render of the current model into the trainer's second workspace (the image, detached)
+torch::Tensor trainer_render_view(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx, double fovy,
+                                  int64_t H, int64_t W)
+{
+	return get(h)->renderView(make_kf(view, proj, campos, fovx, fovy, H, W));
 }
 void trainer_finish(int64_t h) { get(h)->finishOneIteration(); }
 void trainer_finish_begin(int64_t h) { get(h)->finishBegin(); }
@@ -387,6 +424,7 @@ void trainer_destroy(int64_t h)
 TORCH_LIBRARY(photoslam_amd, m)
 {
 	m.def("rasterize_gaussians", &rasterize_gaussians);
+	m.def("rasterize_gaussians_modes", &rasterize_gaussians_modes);
 	m.def("mark_visible", &mark_visible);
 	m.def("dist_cuda2", &dist_cuda2);
 	m.def("l1_ssim_loss", &l1_ssim_loss);
@@ -411,6 +449,7 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("trainer_create", &trainer_create);
 	m.def("trainer_render_and_backward", &trainer_render_and_backward);
 	m.def("trainer_render", &trainer_render);
+	m.def("trainer_render_view", &trainer_render_view);
 	m.def("trainer_finish", &trainer_finish);
 	m.def("trainer_finish_begin", &trainer_finish_begin);
 	m.def("trainer_adam_group", &trainer_adam_group);

@@ -181,6 +181,16 @@ void GaussianModel::addDensificationStats(torch::Tensor& viewspace_point_tensor,
 	denom_.index_put_({update_filter}, denom_.index({update_filter}) + 1);
 }
 
+torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf)
+{
+	torch::NoGradGuard no_grad;
+	torch::Tensor override_color;
+	auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_, override_color, 1.0f,
+	                                    false, /*fuse_activations=*/true, torch::Tensor(), ShAdamStep(), {}, GeomAdamStep(),
+	                                    cull_empty_tiles_, persistent_workspace_ ? &view_workspace_ : nullptr, /*forward_only=*/true);
+	return std::get<0>(pkg);
+}
+
 torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask)
 {
 	auto& g = gaussians_;

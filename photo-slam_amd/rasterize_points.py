@@ -100,9 +100,12 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
                            viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                            prefiltered, raw_params=0, sh_adam=None, workspace=None):
     """raw_params (extension, default 0 = reference contract): GSR_RAW_* mask -- opacity / scales / rotations are the
-    model's raw parameters and are activated in-kernel (include/gsr.h).
+    model's raw parameters and are activated in-kernel (include/gsr.h).  With capi.FORWARD_ONLY in it the call renders the same
+    image and radii without preparing anything for a backward pass: the returned buffers are then NOT valid input to
+    RasterizeGaussiansBackwardCUDA (include/gsr.h: GSR_FORWARD_ONLY).
     sh_adam (extension, default None): the dict RasterizeGaussiansBackwardCUDA takes; only its lazy mode (row_step set,
-    gsr_sh_adam_lazy) concerns the forward pass: visible rows that lag behind take their missed zero-gradient steps first."""
+    gsr_sh_adam_lazy) concerns the forward pass: visible rows that lag behind take their missed zero-gradient steps first
+    (forward-only: in registers only -- nothing of the Adam state is written)."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # AT_ERROR, rasterize_points.cu:57-59
     lib = _lib()
@@ -319,6 +322,12 @@ def shAdamFromViews(means3D, campos_views, dL_dcolor_views, degree, scale, sh, s
         st = lib.gsr_sh_adam_from_views(P, int(degree), int(sh.size(1)), n_views, p1, pc, sc, pv, sv, float(scale),
                                         C.c_void_p(sh.data_ptr()), C.byref(adam), _stream_ptr(means3D))
         capi.check(lib, st, "shAdamFromViews")
+
+
+def lastForwardOnly():
+    """gsr_last_forward_only: 1 if this thread's last RasterizeGaussiansCUDA was forward-only (GSR_FORWARD_ONLY), 0 if not, -1 before
+    the first"""
+    return int(_lib().gsr_last_forward_only())
 
 
 def lastVisibleCount():

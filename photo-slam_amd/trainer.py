@@ -213,6 +213,9 @@ class TrainStep:
         from . import rasterize_points as rp
         self.persistent_workspace_ = True
         self.workspace_ = rp.RasterWorkspace()
+        # ... and a second set for render_view(): a view between a training forward and its backward must not overwrite the
+        # buffers that forward saved
+        self.view_workspace_ = rp.RasterWorkspace()
         self.cull_empty_tiles_ = bool(cull_empty_tiles)   # option of this object; GSR_CULL_EMPTY_TILES only overrides (gaussian_renderer.py)
         self.gaussians_, self.opt_, self.pipe_, self.background_ = gaussians, opt, pipe, background
         self.cameras_extent_ = cameras_extent if cameras_extent is not None else gaussians.spatial_lr_scale_
@@ -235,6 +238,17 @@ class TrainStep:
         # (TrainStep::fused_geom_adam_ of the C++ host), on the same iterations
         self.fused_geom_adam_ = fused_geom_adam
         self.ema_loss_for_log_ = 0.0
+
+    def render_view(self, viewpoint_cam):
+        """A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe):
+        forward-only (GSR_FORWARD_ONLY), into the trainer's second workspace, with lazily stepped SH rows read as they are --
+        no flush, no counter advanced, nothing of the model or the training workspace touched.  Returns the [3,H,W] image."""
+        with torch.no_grad():
+            image, _, _, _ = GaussianRenderer.render(
+                viewpoint_cam, viewpoint_cam.image_height_, viewpoint_cam.image_width_, self.gaussians_, self.pipe_,
+                self.background_, cull_empty_tiles=self.cull_empty_tiles_,
+                workspace=self.view_workspace_ if self.persistent_workspace_ else None, forward_only=True)
+        return image
 
     def _effective_mask(self, mask):
         """rendered * mask with a mask of ones is the identity (src/gaussian_mapper.cpp:692-693; most keyframes carry a full
