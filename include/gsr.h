@@ -133,6 +133,17 @@ typedef struct gsr_forward_args {
 	 * rows of visible Gaussians that lag behind (sh_adam->step - 1) take their missed zero-gradient Adam steps before their
 	 * coefficients are evaluated -- the forward pass then WRITES sh_adam->param (== shs), the moments and row_step. */
 	const gsr_sh_adam* sh_adam;
+	/* Extension (NULL = the reference contract): a depth map and an alpha map, [H,W] each, written for every pixel; either may
+	 * be set without the other.  For pixel p, with the same list entries, alpha_j, T_j and early stop as the colour blend:
+	 *   out_depth[p] = sum_j z_j alpha_j T_j,   z_j = the view-space z of Gaussian j's mean, transformPoint4x3(mean, view).z
+	 *                  (the value the depth sort keys on).  Not normalised and without a background term: an empty pixel has
+	 *                  depth 0; the expected depth is out_depth / out_alpha.
+	 *   out_alpha[p] = 1 - T_final[p], the T the forward pass keeps for the backward pass.
+	 * Works with and without GSR_FORWARD_ONLY, in both GSR_BINNING_* arrangements, with GSR_CULL_EMPTY_TILES, colors_precomp,
+	 * cov3D_precomp and GSR_RAW_*; out_color, radii and *num_rendered are the same, bit for bit, as without them.  P == 0 leaves
+	 * them untouched, as out_color.  Gradients: gsr_backward_args.dL_ddepth / dL_dalpha. */
+	float* out_depth;
+	float* out_alpha;
 } gsr_forward_args;
 
 #define GSR_RAW_OPACITY 1   /* opacities are logits */
@@ -276,6 +287,16 @@ typedef struct gsr_backward_args {
 	 * words).  The same bits as gsr_pack_color_view(P, dL_dcolor_view, campos, packed_capacity_rows, ...). */
 	uint32_t* packed_view;
 	int packed_capacity_rows;
+	/* Extension (NULL = the reference contract): upstream gradients of gsr_forward_args.out_depth / out_alpha, [H,W] each; either
+	 * may be NULL (zeros).  The forward pass need not have rendered the maps: the depths and the final transmittance are always
+	 * in the buffers of a training forward.  With dD = dL_ddepth, dA = dL_dalpha and S^z_{j+1} the depth blended behind entry j:
+	 *   dL/dalpha_j += T_j z_j dD - (S^z_{j+1} dD - T_final dA) / (1 - alpha_j)   (reaches dL_dopacity, dL_dmean2D, dL_dconic,
+	 *                                                                              the covariance and scale / rotation)
+	 *   dL/dz_j      = sum_p alpha_j T_j dD_p, added to dL_dmean3D through dz/dmean = (view[2], view[6], view[10]).
+	 * Colours and SH get nothing from them; dL_dmean2D is the full gradient (so are the fused densification statistics and the
+	 * fused Adam steps, geom_adam included). */
+	const float* dL_ddepth;
+	const float* dL_dalpha;
 } gsr_backward_args;
 
 /* Rasterizer::backward, cuda_rasterizer/rasterizer_impl.cu:340-433.
@@ -399,6 +420,16 @@ int gsr_knn_mean_dist2(int P, const float* points, float* meanDists,
 size_t gsr_loss_scratch_bytes(int width, int height);
 int gsr_l1_ssim_loss(const float* rendered, const float* gt, const float* mask, int width, int height,
                      float lambda_dssim, float* grad_rendered, float* loss, char* scratch, void* stream);
+
+/* Depth L1 loss of an RGB-D keyframe against the rendered depth map (gsr_forward_args.out_depth), Photo-SLAM's
+ * RGBD.min_depth / RGBD.max_depth as the sensor's valid range:
+ *   loss = weight * sum_{valid p} |depth[p] - gt_depth[p]| / (H W),   valid = min_depth < gt_depth[p] < max_depth
+ *   grad_depth[p] = weight * sign(depth[p] - gt_depth[p]) * valid / (H W)   (sign(0) = 0; written for every pixel)
+ * *loss (device) and grad_depth [H,W] are written; the sum is deterministic (fixed grid, fixed order: two launches).
+ * scratch: gsr_depth_loss_scratch_bytes(width, height) device bytes. */
+size_t gsr_depth_loss_scratch_bytes(int width, int height);
+int gsr_depth_l1_loss(const float* depth, const float* gt_depth, int width, int height, float min_depth, float max_depth,
+                      float weight, float* grad_depth, float* loss, char* scratch, void* stream);
 
 /* One torch::optim::Adam step (no amsgrad / weight decay; src/gaussian_model.cpp:477-510 uses eps 1e-15)
  * on a flat fp32 tensor: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;

@@ -31,7 +31,8 @@ class ForwardArgs(C.Structure):
                 ("scale_modifier", C.c_float), ("rotations", C.c_void_p), ("cov3D_precomp", C.c_void_p),
                 ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p), ("cam_pos", C.c_void_p),
                 ("tan_fovx", C.c_float), ("tan_fovy", C.c_float), ("prefiltered", C.c_int),
-                ("out_color", C.c_void_p), ("radii", C.c_void_p), ("raw_params", C.c_int), ("sh_adam", C.c_void_p)]
+                ("out_color", C.c_void_p), ("radii", C.c_void_p), ("raw_params", C.c_int), ("sh_adam", C.c_void_p),
+                ("out_depth", C.c_void_p), ("out_alpha", C.c_void_p)]
 
 
 SH_LAZY_WINDOW = 32   # GSR_SH_LAZY_WINDOW
@@ -109,7 +110,8 @@ class BackwardArgs(C.Structure):
                 ("dL_dcolor_view", C.c_void_p), ("sh_adam", C.POINTER(ShAdam)),
                 ("stat_grad_accum", C.c_void_p), ("stat_denom", C.c_void_p), ("stat_max_radii", C.c_void_p),
                 ("geom_adam", C.POINTER(GeomAdam)), ("color_view_ready_stream", C.c_void_p),
-                ("packed_view", C.c_void_p), ("packed_capacity_rows", C.c_int)]
+                ("packed_view", C.c_void_p), ("packed_capacity_rows", C.c_int),
+                ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p)]
 
 class DensifySelectArgs(C.Structure):
     _fields_ = [("P", C.c_int), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p), ("scaling", C.c_void_p),
@@ -141,6 +143,7 @@ EXPORTED_SYMBOLS = [
     "gsr_sh_grad_from_packed_views", "gsr_sh_adam_from_packed_views", "gsr_last_visible_count", "gsr_check_packed_views", "gsr_depth_resort_count",
     "gsr_host_wait_stats", "gsr_binning_tile_first", "gsr_densify_morton_scratch_bytes",
     "gsr_binning_bytes_for", "gsr_image_bytes_for", "gsr_last_forward_only",
+    "gsr_depth_loss_scratch_bytes", "gsr_depth_l1_loss",
 ]
 
 _libs = {}
@@ -202,6 +205,10 @@ def load(path=None):
     L.gsr_loss_scratch_bytes.argtypes = [i32, i32]
     L.gsr_l1_ssim_loss.restype = i32
     L.gsr_l1_ssim_loss.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]
+    L.gsr_depth_loss_scratch_bytes.restype = sz
+    L.gsr_depth_loss_scratch_bytes.argtypes = [i32, i32]
+    L.gsr_depth_l1_loss.restype = i32
+    L.gsr_depth_l1_loss.argtypes = [vp, vp, i32, i32, f32, f32, f32, vp, vp, vp, vp]
     L.gsr_adam_step.restype = i32
     f64 = C.c_double
     L.gsr_adam_step.argtypes = [vp, vp, vp, vp, C.c_longlong, f64, f64, f64, f64, i32, i32, i32, f64, vp]

@@ -44,6 +44,13 @@
 // per (tile, group of segments) -- parity green, -7 % of this kernel at 500 k @ 1200 x 680 and 2 M @ 640 x 480, nothing elsewhere,
 // +4 us in the forward blend and 16 bytes per instance: removed, commit 2e10ed9, EXPERIMENTS.md R6.)
 //
+// DEPTH (gsr_backward_args.dL_ddepth / dL_dalpha): the depth map D = sum_j z_j alpha_j T_j is one more colour channel and the alpha
+// map A = 1 - T_final moves only the start of the running scalar:
+//   B_final = T_final (bg . dpix - dA),   B_j = B_{j+1} + (c_j . dpix + z_j dD) alpha_j T_j,
+// and dL/dz_j = sum over the pixels of alpha_j T_j dD, a tenth sum.  It costs no LDS: z rides in the spare word s_rec[i][2].y and
+// the tenth sum is accumulated in s_rec[i][2].z (zeroed at staging), reduced like the ninth -- row sums of 16 lanes, merged by four
+// more lanes of the same ds_add_f32 -- and written to slot word [9].
+//
 #include "blend.h"
 #include "kernels.h"
 
@@ -60,10 +67,11 @@ struct BwdPixel {
 	typedef float v2f __attribute__((vector_size(8)));
 	v2f pxy, dprg;
 	float dpb, T, B;
+	float dD;   // DEPTH: the pixel's dL/ddepth
 	uint32_t last;
 };
 
-template <int WAVES>
+template <int WAVES, bool DEPTH>
 __global__ void __launch_bounds__(64 * WAVES)
 blend_bwd_kernel(const BlendBwdParams p)
 {
@@ -71,7 +79,8 @@ blend_bwd_kernel(const BlendBwdParams p)
 	constexpr bool PAIRS = WAVES == 2;          // two pixels per lane
 	constexpr int BWD_THREADS = 64 * WAVES;
 	constexpr int BWD_SEG = BWD_THREADS;        // list entries accumulated in LDS per segment; thread i stages entry i of the segment
-	__shared__ float4 s_rec[BWD_SEG][3];   // per entry of the segment: (x, y, A', B') (C', opacity, r, g) (b, -, -, -)
+	__shared__ float4 s_rec[BWD_SEG][3];   // per entry of the segment: (x, y, A', B') (C', opacity, r, g) (b, z, sum dL/dz, -)
+	                                       // (DEPTH only: z and the tenth sum)
 	__shared__ float s_acc[9][BWD_SEG];
 	__shared__ uint32_t s_slot[BWD_SEG];
 	__shared__ uint8_t s_flag[BWD_SEG];    // bit q: quad q of the tile blends the entry
@@ -105,7 +114,13 @@ blend_bwd_kernel(const BlendBwdParams p)
 		// the pixel's state behind its last contributor: T = the final transmittance, B = (everything blended behind, i.e. the
 		// background) . dpix
 		s.T = T_final;
-		s.B = T_final * (p.bg[0] * dpr + p.bg[1] * dpg + p.bg[2] * dpb);
+		if constexpr (DEPTH) {   // (+ the alpha map's -dA: file header)
+			s.dD = (inside && p.dL_ddepth) ? p.dL_ddepth[pix] : 0.f;
+			const float dA = (inside && p.dL_dalpha) ? p.dL_dalpha[pix] : 0.f;
+			s.B = T_final * ((p.bg[0] * dpr + p.bg[1] * dpg + p.bg[2] * dpb) - dA);
+		} else {
+			s.B = T_final * (p.bg[0] * dpr + p.bg[1] * dpg + p.bg[2] * dpb);
+		}
 	};
 	const int pxa = tile_x * TILE + (qa & 1) * 8 + (l & 7), py = tile_y * TILE + (qa >> 1) * 8 + (l >> 3);
 	BwdPixel A, Bp;
@@ -127,6 +142,10 @@ blend_bwd_kernel(const BlendBwdParams p)
 	const bool red_ninth = (l & 15) == 1;
 	const bool red_lane = ((l & 7) == 0) || red_ninth;
 	const int red_off = (red_ninth ? 8 : wave_swap9_component(l)) * BWD_SEG;
+	// DEPTH: lanes 2, 18, 34, 50 add the four row sums of the tenth to s_rec[entry][2].z (12 floats per entry)
+	const bool red_tenth = DEPTH && (l & 15) == 2;
+	float* const red_base = red_tenth ? &s_rec[0][2].z : &s_acc[0][0] + red_off;
+	const int red_stride = red_tenth ? 12 : 1;
 
 	const int seg_first = (int)((bmax + BWD_SEG - 1) / BWD_SEG) - 1, seg_last = 0;
 	// The segment's records are staged ONCE per tile, by all the workgroup's threads (thread i: list entry seg_lo + i), and only
@@ -176,12 +195,14 @@ blend_bwd_kernel(const BlendBwdParams p)
 	struct Terms {
 		v2f c01, t, m56;
 		float c3, t7, wG;
+		float z9;   // DEPTH: alpha T dL/ddepth
 	};
-	auto terms = [](BwdPixel& s, const Hit& h, const float4 g1, float gb) -> Terms {
+	auto terms = [](BwdPixel& s, const Hit& h, const float4 g1, float gb, float gz) -> Terms {
 		const float rinv = __builtin_amdgcn_rcpf(1.f - h.alpha);
 		const float Tn = s.T * rinv;   // the transmittance in FRONT of this entry
-		// dL/dalpha = T_j (c_j . dpix) - B_{j+1} / (1 - alpha_j)   (the running scalar: file header)
-		const float cdp = g1.z * s.dprg[0] + g1.w * s.dprg[1] + gb * s.dpb;
+		// dL/dalpha = T_j (c_j . dpix) - B_{j+1} / (1 - alpha_j)   (the running scalar: file header; DEPTH: z_j dD is one more channel)
+		float cdp = g1.z * s.dprg[0] + g1.w * s.dprg[1] + gb * s.dpb;
+		if constexpr (DEPTH) cdp += gz * s.dD;
 		const float dL_dalpha = cdp * Tn - s.B * rinv;
 		const float am = PAIRS ? mask_select0_f32(h.ok, h.alpha) : (h.okl ? h.alpha : 0.f);
 		const float dLm = PAIRS ? mask_select0_f32(h.ok, dL_dalpha) : (h.okl ? dL_dalpha : 0.f);
@@ -193,6 +214,7 @@ blend_bwd_kernel(const BlendBwdParams p)
 		r.m56 = h.dxy * (v2f){r.t[0], r.t[0]};      // w dx dx, w dx dy
 		r.c3 = dcol * s.dpb;
 		r.t7 = r.t[1] * h.dxy[1];                    // w dy dy
+		if constexpr (DEPTH) r.z9 = dcol * s.dD;
 		s.T = PAIRS ? mask_select_f32(h.ok, Tn, s.T) : (h.okl ? Tn : s.T);
 		s.B += dcol * cdp;   // (dcol is zero where the entry is not blended)
 		return r;
@@ -207,10 +229,12 @@ blend_bwd_kernel(const BlendBwdParams p)
 			const uint32_t f = flags_next, gid = gid_next;
 			uint32_t slot = 0xFFFFFFFFu;
 			float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0, q2 = q0;
+			float z = 0.f;
 			if (f) {
 				q0 = p.rec[3 * (size_t)gid + 0];
 				q1 = p.rec[3 * (size_t)gid + 1];
 				q2 = p.rec[3 * (size_t)gid + 2];
+				if constexpr (DEPTH) z = p.depth[gid];
 			}
 			if (seg > seg_last) {   // (asked for in front of the wait for the records)
 				flags_next = seg_flags(seg - 1);
@@ -220,12 +244,14 @@ blend_bwd_kernel(const BlendBwdParams p)
 				s_rec[tid][0] = prescale_q0(q0);
 				s_rec[tid][1] = make_float4(prescale_c(q1.x), q1.y, q1.z, q1.w);
 				s_rec[tid][2].x = q2.x;
+				if constexpr (DEPTH) s_rec[tid][2].y = z;
 				const uint32_t rlo = __float_as_uint(q2.y), rhi = __float_as_uint(q2.z);
 				const uint32_t minx = rlo & 0xFFFFu, miny = rlo >> 16, maxx = rhi & 0xFFFFu;
 				slot = __float_as_uint(q2.w) + ((uint32_t)tile_y - miny) * (maxx - minx) + ((uint32_t)tile_x - minx);
 			}
 			s_slot[tid] = slot;
 			s_flag[tid] = (uint8_t)f;
+			if constexpr (DEPTH) s_rec[tid][2].z = 0.f;   // the tenth sum
 		}
 		__syncthreads();
 
@@ -246,7 +272,14 @@ blend_bwd_kernel(const BlendBwdParams p)
 				const uint32_t pos = (uint32_t)(base + bit);
 				const float4 g0 = rec_b[bit][0];
 				const float4 g1 = rec_b[bit][1];
-				const float gb = rec_b[bit][2].x;
+				float gb, gz = 0.f;
+				if constexpr (DEPTH) {
+					const float2 bz = *reinterpret_cast<const float2*>(&rec_b[bit][2]);
+					gb = bz.x;
+					gz = bz.y;
+				} else {
+					gb = rec_b[bit][2].x;
+				}
 				// only the flagged quads of the pair are tested (wave-uniform branches on the two flag bits)
 				Hit ha, hb;
 				unsigned long long oka = 0ull, okb = 0ull;
@@ -266,17 +299,18 @@ blend_bwd_kernel(const BlendBwdParams p)
 				// (half tile, entry).
 				Terms r;
 				if (PAIRS && oka && okb) {
-					const Terms ra = terms(A, ha, g1, gb), rb = terms(Bp, hb, g1, gb);
+					const Terms ra = terms(A, ha, g1, gb, gz), rb = terms(Bp, hb, g1, gb, gz);
 					r.c01 = ra.c01 + rb.c01;
 					r.t = ra.t + rb.t;
 					r.m56 = ra.m56 + rb.m56;
 					r.c3 = ra.c3 + rb.c3;
 					r.t7 = ra.t7 + rb.t7;
 					r.wG = ra.wG + rb.wG;
+					if constexpr (DEPTH) r.z9 = ra.z9 + rb.z9;
 				} else if (oka) {
-					r = terms(A, ha, g1, gb);
+					r = terms(A, ha, g1, gb, gz);
 				} else if (PAIRS && okb) {
-					r = terms(Bp, hb, g1, gb);
+					r = terms(Bp, hb, g1, gb, gz);
 				} else {
 					continue;   // wave-uniform
 				}
@@ -291,10 +325,24 @@ blend_bwd_kernel(const BlendBwdParams p)
 				v[7] = r.t7;
 				v[8] = r.wG;
 				float packed, ninth_row;
-				wave_reduce9_swap_f32(v, packed, ninth_row);
-				GSR_OPAQUE_F32(packed);      // keep the last butterfly adds fused with their DPP moves (the compiler otherwise
-				GSR_OPAQUE_F32(ninth_row);   // sinks them into the 12-lane branch as mov_dpp + add)
-				if (red_lane) atomicAdd(&(&s_acc[0][0])[red_off + ((int)pos - (int)seg_lo)], red_ninth ? ninth_row : packed);
+				if constexpr (DEPTH) {   // the tenth (dL/dz) is reduced like the ninth: row sums, four more lanes of the same ds_add_f32
+					float v10[10];
+#pragma unroll
+					for (int c = 0; c < 9; c++) v10[c] = v[c];
+					v10[9] = r.z9;
+					float tenth_row;
+					wave_reduce10_swap_f32(v10, packed, ninth_row, tenth_row);
+					GSR_OPAQUE_F32(packed);
+					GSR_OPAQUE_F32(ninth_row);
+					GSR_OPAQUE_F32(tenth_row);
+					if (red_lane || red_tenth)
+						atomicAdd(red_base + ((int)pos - (int)seg_lo) * red_stride, red_tenth ? tenth_row : (red_ninth ? ninth_row : packed));
+				} else {
+					wave_reduce9_swap_f32(v, packed, ninth_row);
+					GSR_OPAQUE_F32(packed);      // keep the last butterfly adds fused with their DPP moves (the compiler otherwise
+					GSR_OPAQUE_F32(ninth_row);   // sinks them into the 12-lane branch as mov_dpp + add)
+					if (red_lane) atomicAdd(&(&s_acc[0][0])[red_off + ((int)pos - (int)seg_lo)], red_ninth ? ninth_row : packed);
+				}
 			}
 		}
 		__syncthreads();
@@ -305,13 +353,15 @@ blend_bwd_kernel(const BlendBwdParams p)
 			float any = 0.f;
 #pragma unroll
 			for (int c = 0; c < 9; c++) any += fabsf(s_acc[c][i]);
+			if constexpr (DEPTH) any += fabsf(s_rec[i][2].z);
 			if (slot != 0xFFFFFFFFu && any != 0.f) {   // untouched / all-zero entries stay unflagged: the per-Gaussian sum skips them
 				p.touched[slot] = 1;
 				float4* dst = reinterpret_cast<float4*>(p.partials + (size_t)slot * (4 * SLOT_F4));
 				// slot order (partials.h): colour r g b, w dx, w dy, w dx dx, w dx dy, w dy dy, w
 				dst[0] = make_float4(s_acc[0][i], s_acc[4][i], s_acc[3][i], s_acc[1][i]);
 				dst[1] = make_float4(s_acc[5][i], s_acc[2][i], s_acc[6][i], s_acc[7][i]);
-				reinterpret_cast<float*>(dst + 2)[0] = s_acc[8][i];
+				if constexpr (DEPTH) *reinterpret_cast<float2*>(dst + 2) = make_float2(s_acc[8][i], s_rec[i][2].z);   // + [9] dL/dz
+				else reinterpret_cast<float*>(dst + 2)[0] = s_acc[8][i];
 			}
 		}
 		if (seg > seg_last) __syncthreads();
@@ -320,10 +370,16 @@ blend_bwd_kernel(const BlendBwdParams p)
 
 int launch_blend_bwd(const BlendBwdParams& p, hipStream_t stream)
 {
-	if (p.half_tiles)
-		GSR_LAUNCH(blend_bwd_kernel<2>, tile_grid(p.deal), 128, stream, p);
+	const bool depth = p.dL_ddepth || p.dL_dalpha;
+	if (depth && !p.depth) return GSR_ERR_INVALID_ARG;
+	if (p.half_tiles && depth)
+		GSR_LAUNCH((blend_bwd_kernel<2, true>), tile_grid(p.deal), 128, stream, p);
+	else if (p.half_tiles)
+		GSR_LAUNCH((blend_bwd_kernel<2, false>), tile_grid(p.deal), 128, stream, p);
+	else if (depth)
+		GSR_LAUNCH((blend_bwd_kernel<4, true>), tile_grid(p.deal), 256, stream, p);
 	else
-		GSR_LAUNCH(blend_bwd_kernel<4>, tile_grid(p.deal), 256, stream, p);
+		GSR_LAUNCH((blend_bwd_kernel<4, false>), tile_grid(p.deal), 256, stream, p);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

@@ -12,16 +12,20 @@
 // FWD_ONLY (GSR_FORWARD_ONLY, a render no backward pass follows): the same image from the same visits, without what only the
 // backward pass reads -- no contribution flags per (quad, entry), no final T and last contributor per pixel, and no scalar
 // bookkeeping of the flags (contrib_m) inside the visit loop.
+//
+// DEPTH (gsr_forward_args.out_depth / out_alpha, either form): the depth map sum_j z_j alpha_j T_j and the alpha map 1 - T from
+// the same visits.  z_j, the view-space depth the lists are sorted by, is gathered at staging into the spare word of the LDS
+// record; the visit adds ONE v_fmac under the same EXEC mask as the colour channels.
 #include "blend.h"
 #include "kernels.h"
 
 namespace gsr {
 
-template <bool FWD_ONLY>
+template <bool FWD_ONLY, bool DEPTH>
 __global__ void __launch_bounds__(64)
 blend_fwd_kernel(const BlendFwdParams p)
 {
-	__shared__ float4 s_rec[64][3];   // per staged entry: (x, y, A', B') (C', opacity, r, g) (b, -, -, -)
+	__shared__ float4 s_rec[64][3];   // per staged entry: (x, y, A', B') (C', opacity, r, g) (b, z (DEPTH), -, -)
 
 	int tile, quad;
 	quad_assignment((int)blockIdx.x, p.deal, tile, quad);
@@ -43,6 +47,7 @@ blend_fwd_kernel(const BlendFwdParams p)
 	float Cr = 0.f, Cg = 0.f;
 #endif
 	float Cb = 0.f;
+	float Cd = 0.f;   // DEPTH: sum z alpha T
 	uint32_t last_contributor = 0;
 	// pixel state predicates live as 64-bit lane masks in SGPR pairs; their logic is scalar
 	unsigned long long done_m = wave_ballot(!inside);
@@ -63,6 +68,7 @@ blend_fwd_kernel(const BlendFwdParams p)
 			s_rec[l][0] = prescale_q0(q0);
 			s_rec[l][1] = make_float4(prescale_c(q1.x), q1.y, q1.z, q1.w);
 			s_rec[l][2].x = cb;
+			if constexpr (DEPTH) s_rec[l][2].y = p.depth[gid];
 		}
 		unsigned long long m = wave_ballot(keep);
 		wave_fence();
@@ -80,7 +86,14 @@ blend_fwd_kernel(const BlendFwdParams p)
 #endif
 			const float4 g0 = s_rec[bit][0];
 			const float4 g1 = s_rec[bit][1];
-			const float gb = s_rec[bit][2].x;
+			float gb, gz = 0.f;
+			if constexpr (DEPTH) {
+				const float2 bz = *reinterpret_cast<const float2*>(&s_rec[bit][2]);
+				gb = bz.x;
+				gz = bz.y;
+			} else {
+				gb = s_rec[bit][2].x;
+			}
 			const float dx = g0.x - pxf, dy = g0.y - pyf;
 			const float pw = g0.z * dx * dx + g1.x * dy * dy + g0.w * dx * dy;   // log2(e) * power
 			const float alpha = fminf(0.99f, g1.y * __builtin_amdgcn_exp2f(pw));
@@ -106,6 +119,7 @@ blend_fwd_kernel(const BlendFwdParams p)
 			const float wgt = mask_select0_f32(upd_m, alpha * T);
 			Crg += (v2f){g1.z, g1.w} * (v2f){wgt, wgt};
 			Cb += gb * wgt;
+			if constexpr (DEPTH) Cd += gz * wgt;
 			T = mask_select_f32(upd_m, test_T, T);
 			last_contributor = mask_select_u32(upd_m, (uint32_t)(base + bit + 1), last_contributor);
 #else
@@ -116,6 +130,21 @@ blend_fwd_kernel(const BlendFwdParams p)
 				const float wgt = alpha * T;
 				const uint32_t contributor = (uint32_t)(base + bit + 1);
 				unsigned long long saved_exec;
+				if constexpr (DEPTH) {   // (the same block with the depth channel's v_fmac)
+				asm volatile("s_and_saveexec_b64 %[save], %[upd]\n\t"
+				             "v_fmac_f32 %[cr], %[gr], %[w]\n\t"
+				             "v_fmac_f32 %[cg], %[gg], %[w]\n\t"
+				             "v_fmac_f32 %[cb], %[gbv], %[w]\n\t"
+				             "v_fmac_f32 %[cd], %[gzv], %[w]\n\t"
+				             "v_mov_b32 %[t], %[tt]\n\t"
+				             "v_mov_b32 %[last], %[c]\n\t"
+				             "s_mov_b64 exec, %[save]"
+				             : [save] "=&s"(saved_exec), [cr] "+v"(Cr), [cg] "+v"(Cg), [cb] "+v"(Cb), [cd] "+v"(Cd), [t] "+v"(T),
+				               [last] "+v"(last_contributor)
+				             : [upd] "s"(upd_m), [gr] "v"(g1.z), [gg] "v"(g1.w), [gbv] "v"(gb), [gzv] "v"(gz), [w] "v"(wgt), [tt] "v"(test_T),
+				               [c] "s"(contributor)
+				             : "scc");
+				} else {
 				asm volatile("s_and_saveexec_b64 %[save], %[upd]\n\t"
 				             "v_fmac_f32 %[cr], %[gr], %[w]\n\t"
 				             "v_fmac_f32 %[cg], %[gg], %[w]\n\t"
@@ -126,6 +155,7 @@ blend_fwd_kernel(const BlendFwdParams p)
 				             : [save] "=&s"(saved_exec), [cr] "+v"(Cr), [cg] "+v"(Cg), [cb] "+v"(Cb), [t] "+v"(T), [last] "+v"(last_contributor)
 				             : [upd] "s"(upd_m), [gr] "v"(g1.z), [gg] "v"(g1.w), [gbv] "v"(gb), [w] "v"(wgt), [tt] "v"(test_T), [c] "s"(contributor)
 				             : "scc");
+				}
 			}
 #endif
 			// (No test for "every pixel saturated" here: the rest of the batch then changes nothing -- ok_m excludes the saturated
@@ -153,15 +183,25 @@ blend_fwd_kernel(const BlendFwdParams p)
 		p.out_color[pix] = Cr + T * p.bg[0];
 		p.out_color[plane + pix] = Cg + T * p.bg[1];
 		p.out_color[2 * plane + pix] = Cb + T * p.bg[2];
+		if constexpr (DEPTH) {
+			if (p.out_depth) p.out_depth[pix] = Cd;
+			if (p.out_alpha) p.out_alpha[pix] = 1.f - T;
+		}
 	}
 }
 
 int launch_blend_fwd(const BlendFwdParams& p, hipStream_t stream)
 {
-	if (p.forward_only)
-		GSR_LAUNCH(blend_fwd_kernel<true>, quad_grid(p.deal), 64, stream, p);
+	const bool depth = p.out_depth || p.out_alpha;
+	if (depth && !p.depth) return GSR_ERR_INVALID_ARG;
+	if (p.forward_only && depth)
+		GSR_LAUNCH((blend_fwd_kernel<true, true>), quad_grid(p.deal), 64, stream, p);
+	else if (p.forward_only)
+		GSR_LAUNCH((blend_fwd_kernel<true, false>), quad_grid(p.deal), 64, stream, p);
+	else if (depth)
+		GSR_LAUNCH((blend_fwd_kernel<false, true>), quad_grid(p.deal), 64, stream, p);
 	else
-		GSR_LAUNCH(blend_fwd_kernel<false>, quad_grid(p.deal), 64, stream, p);
+		GSR_LAUNCH((blend_fwd_kernel<false, false>), quad_grid(p.deal), 64, stream, p);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

@@ -539,6 +539,8 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	bp.W = W; bp.H = H; bp.grid_x = grid_x; bp.tiles = tiles;
 	bp.deal = make_tile_deal(tiles, grid_x, xcd_deal_mode(tiles));
 	bp.forward_only = fwd_only ? 1 : 0;
+	bp.depth = reinterpret_cast<const float*>(g.depth_key);   // (the float bits of the view-space z: preprocess.hip)
+	bp.out_depth = a->out_depth; bp.out_alpha = a->out_alpha;
 	if ((st = launch_blend_fwd(bp, stream)) != GSR_OK) return st;
 	PROF_FWD(8);
 	t_prof.fwd_done = t_prof.on == 1;
@@ -574,6 +576,7 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	// lazy rows' catch-up has advanced a step counter)
 	if (a->color_view_ready_stream && a->dL_dcolor_view && a->color_view_ready_stream == stream_) return GSR_ERR_INVALID_ARG;
 	if (a->packed_view && a->dL_dcolor_view && (a->packed_capacity_rows < 0 || (a->packed_capacity_rows & 3))) return GSR_ERR_INVALID_ARG;
+	const bool depth = a->dL_ddepth || a->dL_dalpha;   // the depth / alpha maps' gradients (gsr.h)
 	hipStream_t stream = (hipStream_t)stream_;
 	const int P = a->P, W = a->width, H = a->height, R = a->R;
 	const int grid_x = div_up(W, TILE), grid_y = div_up(H, TILE), tiles = grid_x * grid_y;
@@ -695,6 +698,8 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 		bp.W = W; bp.H = H; bp.grid_x = grid_x; bp.tiles = tiles;
 		bp.deal = make_tile_deal(tiles, grid_x, xcd_deal_mode(tiles));
 		bp.half_tiles = blend_bwd_half_tiles(tiles) ? 1 : 0;
+		bp.depth = reinterpret_cast<const float*>(g.depth_key);
+		bp.dL_ddepth = a->dL_ddepth; bp.dL_dalpha = a->dL_dalpha;
 		if ((st = launch_blend_bwd(bp, stream)) != GSR_OK) return fail(st);
 	}
 	PROF_BWD(2);
@@ -736,6 +741,7 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 		if (lazy) { pb.lazy_row_step = la.row_step; pb.lazy_step = la.step; }
 	}
 	pb.geom = geom;
+	pb.depth = (depth && R > 0) ? 1 : 0;
 	pb.notify_stream = nullptr; pb.notify_event = nullptr;
 	if (a->color_view_ready_stream && a->dL_dcolor_view) {
 		if ((st = t_sync.init_notify()) != GSR_OK) return fail(st);

@@ -90,6 +90,11 @@ struct BlendFwdParams {
 	int W, H, grid_x, tiles;
 	TileDeal deal;          // blend.h: the workgroup -> XCD deal of the tiles
 	int forward_only;       // GSR_FORWARD_ONLY: final_T, n_contrib and contrib are not written (and may be null)
+	// depth and alpha maps (gsr_forward_args.out_depth / out_alpha; both null = the colour-only kernel): depth[p] = sum z alpha T,
+	// alpha[p] = 1 - T_final, z = the view-space depth of the Gaussian (the float bits of GeometryState::depth_key)
+	const float* depth;     // [P] z per Gaussian: read only when out_depth or out_alpha is set
+	float* out_depth;       // [H,W] nullable
+	float* out_alpha;       // [H,W] nullable
 };
 int launch_blend_fwd(const BlendFwdParams& p, hipStream_t stream);
 
@@ -108,6 +113,11 @@ struct BlendBwdParams {
 	int W, H, grid_x, tiles;
 	TileDeal deal;          // blend.h: the workgroup -> XCD deal of the tiles
 	int half_tiles;         // 1: one wave per 16x8 half tile, two pixels per lane; 0: one wave per 8x8 quad (blend_bwd.hip)
+	// upstream gradients of the depth and alpha maps (gsr_backward_args.dL_ddepth / dL_dalpha; both null = the colour-only
+	// kernel; one null = zeros): with either set, slot word [9] receives sum alpha T dL_ddepth, the gradient of the entry's z
+	const float* depth;     // [P] z per Gaussian (GeometryState::depth_key as floats)
+	const float* dL_ddepth; // [H,W] nullable
+	const float* dL_dalpha; // [H,W] nullable
 };
 int launch_blend_bwd(const BlendBwdParams& p, hipStream_t stream);
 
@@ -183,6 +193,9 @@ struct PreprocessBwdParams {
 	// gsr_pack_view_plan -- preprocess_bwd_kernel writes the seen rows and the header next to dL_dcolor_view; null = off
 	uint32_t* packed_msg;
 	int packed_capacity;      // rows the message has room for
+	// the backward blend left dL/dz, z = the view-space depth, in slot word [9] (gsr_backward_args.dL_ddepth / dL_dalpha): it joins
+	// dL_dtz, the gradient of the view-space z of the mean
+	int depth;
 };
 int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream);
 // does the backward preprocess take the two-kernel path of the reference's SH layout (preprocess_bwd_kernel<true> +

@@ -7,19 +7,21 @@
 // arrays -- densification appends the children of split Gaussians consecutively -- no wave of the backward preprocess inherits
 // their work.
 //   a[0..2] dL_dcolor   a[3], a[4] sum w dx, sum w dy   a[5..7] sum w dx dx, w dx dy, w dy dy   a[8] sum w
+//   a[9] dL/dz (the depth / alpha maps' backward, blend_bwd.hip: DEPTH) -- carried by the forms over float[10] / DEPTH only
 #pragma once
 #include "state.h"
 #include "wave64.h"
 
 namespace gsr {
 
-// U touched slots of a run in one trip: the loads first, the sums in slot order
-template <int U>
-__device__ __forceinline__ void sum_slots_trip(const float4* src, unsigned long long& live, float (&a)[9])
+// U touched slots of a run in one trip: the loads first, the sums in slot order.  N = 10: word [9] too (one 8-byte load)
+template <int U, int N>
+__device__ __forceinline__ void sum_slots_trip(const float4* src, unsigned long long& live, float (&a)[N])
 {
+	static_assert(N == 9 || N == 10, "nine sums, or ten with dL/dz");
 	int idx[U];
 	float4 x[U], y[U];
-	float z[U];
+	float z[U], zd[U];
 #pragma unroll
 	for (int j = 0; j < U; j++) {
 		idx[j] = __ffsll((long long)live) - 1;
@@ -29,13 +31,20 @@ __device__ __forceinline__ void sum_slots_trip(const float4* src, unsigned long 
 	for (int j = 0; j < U; j++) {
 		x[j] = src[SLOT_F4 * (size_t)idx[j]];
 		y[j] = src[SLOT_F4 * (size_t)idx[j] + 1];
-		z[j] = src[SLOT_F4 * (size_t)idx[j] + 2].x;
+		if constexpr (N == 10) {
+			const float2 t = *reinterpret_cast<const float2*>(src + SLOT_F4 * (size_t)idx[j] + 2);
+			z[j] = t.x;
+			zd[j] = t.y;
+		} else {
+			z[j] = src[SLOT_F4 * (size_t)idx[j] + 2].x;
+		}
 	}
 #pragma unroll
 	for (int j = 0; j < U; j++) {
 		a[0] += x[j].x; a[1] += x[j].y; a[2] += x[j].z; a[3] += x[j].w;
 		a[4] += y[j].x; a[5] += y[j].y; a[6] += y[j].z; a[7] += y[j].w;
 		a[8] += z[j];
+		if constexpr (N == 10) a[9] += zd[j];
 	}
 }
 
@@ -48,12 +57,13 @@ __device__ __forceinline__ uint32_t squeeze_flags16(const uint8_t* p)
 	       ((((f.w * 0x01020408u) >> 24) & 0xFu) << 12);
 }
 
+template <int N>
 __device__ __forceinline__ void wave_sum_partial_runs(uint32_t cnt, uint32_t first, const float* __restrict__ partials,
-                                                      const uint8_t* __restrict__ touched, float (&a)[9])
+                                                      const uint8_t* __restrict__ touched, float (&a)[N])
 {
 	const float4* part4 = reinterpret_cast<const float4*>(partials);
 #pragma unroll
-	for (int c = 0; c < 9; c++) a[c] = 0.f;
+	for (int c = 0; c < N; c++) a[c] = 0.f;
 	if (cnt != 0u && cnt <= LONG_RUN) {
 		// the run's flags, 16 bytes per load, squeezed to one bit per slot: the loops below then run over the TOUCHED slots
 		// only (~1 in 5) and their loads do not wait for one another (a byte-flag test per slot serialises on memory latency)
@@ -75,19 +85,23 @@ __device__ __forceinline__ void wave_sum_partial_runs(uint32_t cnt, uint32_t fir
 		a[0] = x.x; a[1] = x.y; a[2] = x.z; a[3] = x.w;
 		a[4] = y.x; a[5] = y.y; a[6] = y.z; a[7] = y.w;
 		a[8] = z;
+		if constexpr (N == 10) a[9] = part4[SLOT_F4 * (size_t)first + 2].y;
 	}
 }
 
 // One wave per listed run: sum its touched slots in a fixed order, store the total in the run's first slot and flag it.  Lane l owns
 // the k = ceil(cnt / 64) CONSECUTIVE slots [l k, (l + 1) k): 16-byte flag loads, then only the touched slots, four per trip.
 // (Rounds 2-5 also carried two lane-strided forms behind GSR_LRS_MODE; this one measured fastest -- 20 -> 14 us at C3 -- and stayed.)
+// DEPTH: word [9] (dL/dz) too, summed by a tenth full-wave reduction.
+template <bool DEPTH>
 __device__ __forceinline__ void wave_sum_long_run(uint32_t first, uint32_t cnt, float* __restrict__ partials, uint8_t* __restrict__ touched)
 {
+	constexpr int N = DEPTH ? 10 : 9;
 	const int l = lane_id();
 	float4* part4 = reinterpret_cast<float4*>(partials);
-	float v[9];
+	float v[N];
 #pragma unroll
-	for (int c = 0; c < 9; c++) v[c] = 0.f;
+	for (int c = 0; c < N; c++) v[c] = 0.f;
 	bool any = false;
 	const uint32_t k = (cnt + 63u) >> 6;
 	const uint32_t lo = (uint32_t)l * k, hi = min(cnt, lo + k);
@@ -105,11 +119,15 @@ __device__ __forceinline__ void wave_sum_long_run(uint32_t first, uint32_t cnt, 
 		while (live) sum_slots_trip<1>(src, live, v);
 	}
 	const bool some = wave_ballot(any) != 0ull;
-	wave_reduce9_f32(v);  // totals in lane 63; every lane has read its slots by now (the reduction is a rendezvous)
+	float v9 = 0.f;
+	if constexpr (DEPTH) v9 = wave_sum_f32_lane63(v[9]);
+	float (&v_nine)[9] = *reinterpret_cast<float (*)[9]>(&v[0]);
+	wave_reduce9_f32(v_nine);  // totals in lane 63; every lane has read its slots by now (the reduction is a rendezvous)
 	if (l == 63) {
 		part4[SLOT_F4 * (size_t)first] = make_float4(v[0], v[1], v[2], v[3]);
 		part4[SLOT_F4 * (size_t)first + 1] = make_float4(v[4], v[5], v[6], v[7]);
-		reinterpret_cast<float*>(part4 + SLOT_F4 * (size_t)first + 2)[0] = v[8];
+		if constexpr (DEPTH) *reinterpret_cast<float2*>(part4 + SLOT_F4 * (size_t)first + 2) = make_float2(v[8], v9);
+		else reinterpret_cast<float*>(part4 + SLOT_F4 * (size_t)first + 2)[0] = v[8];
 		touched[first] = some ? 1 : 0;
 	}
 }

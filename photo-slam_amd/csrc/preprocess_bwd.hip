@@ -225,7 +225,9 @@ __device__ __forceinline__ void pack_view_row(const PreprocessBwdParams& p, int 
 // follows and adds the SH term; otherwise the SH backward happens here with per-lane scalar row access.
 // PACKED: the view's packed message is written next to dL_dcolor_view (gsr_backward_args.packed_view) -- an instantiation of its
 // own: as a run-time branch it cost the kernel of the single-GPU step 8 us (181 -> 189 us at C3, profiles/r04_v) with the option off.
-template <bool ROWS_OK, bool PACKED = false>
+// DEPTH: the backward blend left dL/dz (the depth / alpha maps) in slot word [9]; it joins dL_dtz below (an instantiation of its own,
+// so that the colour-only kernel is the same code as without the feature).
+template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false>
 __global__ void __launch_bounds__(PRB_THREADS)
 preprocess_bwd_kernel(const PreprocessBwdParams p)
 {
@@ -241,12 +243,14 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 	// ------------------------------------------------------------------ gradients of the blend stage (partials.h)
 	// the per-instance slots of this Gaussian's tiles are summed here, in registers: colour 0..2, mean2D moments 3..4,
 	// conic moments 5..7, opacity 8 never round-trip through HBM
-	float a[9];
+	float a[DEPTH ? 10 : 9];
 	{
 		const uint32_t cnt = (vis && p.partials) ? p.tiles_touched[idx] : 0u;
 		const uint32_t first = cnt ? __float_as_uint(p.rec[3 * (size_t)idx + 2].w) : 0u;
 		wave_sum_partial_runs(cnt, first, p.partials, p.touched, a);   // every lane of the wave takes part
 	}
+	float dL_dz = 0.f;   // DEPTH: the gradient of the view-space z of the mean (the depth the lists are sorted by)
+	if constexpr (DEPTH) dL_dz = a[9];
 	float* out_sh = (p.dL_dsh && !p.dL_dcolor_view && !p.adam_exp_avg && in_range) ? p.dL_dsh + (size_t)idx * M3 : nullptr;
 
 	// Culled Gaussians take the same store instructions as visible ones, with zeros (the reference leaves the
@@ -443,7 +447,8 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		const float tz3 = tz2 * tz;
 		const float dL_dtx = x_grad_mul * -h_x * tz2 * dL_dJ02;
 		const float dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
-		const float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * tx) * tz3 * dL_dJ02 + (2 * h_y * ty) * tz3 * dL_dJ12;
+		float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * tx) * tz3 * dL_dJ02 + (2 * h_y * ty) * tz3 * dL_dJ12;
+		if constexpr (DEPTH) dL_dtz += dL_dz;   // z = tz0: the depth map's term
 		// transformVec4x3Transpose, auxiliary.h:89-97
 		gmx = V[0] * dL_dtx + V[1] * dL_dty + V[2] * dL_dtz;
 		gmy = V[4] * dL_dtx + V[5] * dL_dty + V[6] * dL_dtz;
@@ -675,6 +680,7 @@ int launch_sh_adam_lazy(int P, const int* radii, const LazyAdam& a, hipStream_t 
 // The runs of more than LONG_RUN instance slots (partials.h): one wave per run, a fixed grid that strides over the list the
 // forward pass left (its length lives on the device).
 constexpr int LRS_BLOCKS = 1024;   // (one listed run per wave at C3: 512 -> 1 024 workgroups: 18.6 -> 14.1 us; more: equal)
+template <bool DEPTH>
 __global__ void __launch_bounds__(256)
 long_run_sums_kernel(const PreprocessBwdParams p)
 {
@@ -686,13 +692,14 @@ long_run_sums_kernel(const PreprocessBwdParams p)
 		const uint32_t g = p.long_runs[(size_t)list * p.long_capacity + e];
 		const uint32_t cnt = p.tiles_touched[g];
 		const uint32_t first = __float_as_uint(p.rec[3 * (size_t)g + 2].w);
-		wave_sum_long_run(first, cnt, p.partials, p.touched);
+		wave_sum_long_run<DEPTH>(first, cnt, p.partials, p.touched);
 	}
 }
 
 int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 {
-	if (p.partials) GSR_LAUNCH(long_run_sums_kernel, LRS_BLOCKS, 256, stream, p);
+	if (p.partials && p.depth) GSR_LAUNCH(long_run_sums_kernel<true>, LRS_BLOCKS, 256, stream, p);
+	else if (p.partials) GSR_LAUNCH(long_run_sums_kernel<false>, LRS_BLOCKS, 256, stream, p);
 	const bool factored = p.dL_dcolor_view != nullptr;
 	const bool adam = p.adam_exp_avg != nullptr;
 	const bool rows_ok = sh_rows_path(p.shs, p.M, p.D, factored, adam, p.dL_dsh);   // (includes 0 <= D <= 3)
@@ -702,7 +709,9 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 		return GSR_ERR_UNSUPPORTED;   // the fused geometry step lives in the two-kernel path of the reference's SH layout
 	const int grid = div_up(p.P, PRB_THREADS);
 	if (rows_ok && p.D >= 0 && p.D <= 3) {
-		if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<true, true>), grid, PRB_THREADS, stream, p);
+		if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, true, true>), grid, PRB_THREADS, stream, p);
+		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<true, true>), grid, PRB_THREADS, stream, p);
+		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, false, true>), grid, PRB_THREADS, stream, p);
 		else GSR_LAUNCH(preprocess_bwd_kernel<true>, grid, PRB_THREADS, stream, p);
 		GSR_CHECK_LAUNCH();
 		if (p.notify_stream && p.notify_event) {   // dL_dcolor_view is complete: whoever gathers it need not wait for the SH kernel
@@ -729,7 +738,9 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 			GSR_SHB(0);
 #undef GSR_SHB
 	} else {
-		if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<false, true>), grid, PRB_THREADS, stream, p);
+		if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, true, true>), grid, PRB_THREADS, stream, p);
+		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<false, true>), grid, PRB_THREADS, stream, p);
+		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, false, true>), grid, PRB_THREADS, stream, p);
 		else GSR_LAUNCH(preprocess_bwd_kernel<false>, grid, PRB_THREADS, stream, p);
 		if (p.notify_stream && p.notify_event) {
 			GSR_HIP(hipEventRecord((hipEvent_t)p.notify_event, stream));

@@ -649,3 +649,65 @@ int gsr_densify_stats(int P, const float* dL_dmean2D, const int* radii, float* x
 }
 
 }  // extern "C"
+
+// ---- depth L1 loss of an RGB-D keyframe (gsr_depth_l1_loss): pass 1 writes the gradient and one partial sum per workgroup (a
+// fixed grid over a fixed element order), pass 2 -- one workgroup -- sums the partials in index order: the same bits every run.
+namespace gsr {
+constexpr int DL_THREADS = 256;
+constexpr int DL_MAX_BLOCKS = 1024;
+static inline int depth_loss_blocks(size_t n) { return (int)(n / (DL_THREADS * 8) + 1 < (size_t)DL_MAX_BLOCKS ? n / (DL_THREADS * 8) + 1 : DL_MAX_BLOCKS); }
+
+__global__ void __launch_bounds__(DL_THREADS)
+depth_l1_partial_kernel(const float* __restrict__ depth, const float* __restrict__ gt, size_t n, float min_depth, float max_depth,
+                        float scale, float* __restrict__ grad, float* __restrict__ partial)
+{
+	__shared__ float s4[4];
+	const size_t stride = (size_t)gridDim.x * DL_THREADS;
+	float acc = 0.f;
+	for (size_t i = (size_t)blockIdx.x * DL_THREADS + threadIdx.x; i < n; i += stride) {
+		const float d = depth[i], g = gt[i];
+		const bool valid = g > min_depth && g < max_depth;
+		const float diff = d - g;
+		const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
+		if (valid) acc += fabsf(diff);
+		grad[i] = valid ? sgn * scale : 0.f;
+	}
+	const float s = block_sum_256(acc, s4);
+	if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(DL_THREADS)
+depth_l1_final_kernel(const float* __restrict__ partial, int nblocks, float scale, float* __restrict__ loss)
+{
+	__shared__ float s4[4];
+	float a = 0.f;
+	for (int i = (int)threadIdx.x; i < nblocks; i += DL_THREADS) a += partial[i];
+	const float s = block_sum_256(a, s4);
+	if (threadIdx.x == 0) loss[0] = s * scale;
+}
+}  // namespace gsr
+extern "C" {
+
+size_t gsr_depth_loss_scratch_bytes(int width, int height)
+{
+	if (width <= 0 || height <= 0) return 0;
+	return (size_t)depth_loss_blocks((size_t)width * height) * sizeof(float);
+}
+
+int gsr_depth_l1_loss(const float* depth, const float* gt_depth, int width, int height, float min_depth, float max_depth,
+                      float weight, float* grad_depth, float* loss, char* scratch, void* stream_)
+{
+	if (!depth || !gt_depth || !grad_depth || !loss || !scratch || width <= 0 || height <= 0) return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	const size_t n = (size_t)width * height;
+	const int blocks = depth_loss_blocks(n);
+	// d loss / d depth of the valid pixels: weight / (H W) times the sign, the factor autograd forms for weight * sum / (H W)
+	const float scale = (1.0f / (float)n) * weight;
+	float* partial = reinterpret_cast<float*>(scratch);
+	GSR_LAUNCH(depth_l1_partial_kernel, blocks, DL_THREADS, stream, depth, gt_depth, n, min_depth, max_depth, scale, grad_depth, partial);
+	GSR_LAUNCH(depth_l1_final_kernel, 1, DL_THREADS, stream, partial, blocks, scale, loss);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+}  // extern "C"

@@ -29,6 +29,57 @@ using ::hipemu::mask_select_f32;
 using ::hipemu::mask_select_u32;
 using ::hipemu::mask_select0_f32;
 #define GSR_OPAQUE_F32(x) asm volatile("" : "+x"(x))
+// twins of the DPP forms below, the same adds in the same order (xor-partner shuffles)
+static inline float wave_xor_add_f32(float v, int mask)
+{
+	uint32_t b;
+	memcpy(&b, &v, 4);
+	b = wave_shfl_u32(b, ::hipemu::lane() ^ mask);
+	float o;
+	memcpy(&o, &b, 4);
+	return v + o;
+}
+static inline float wave_row_sum16_f32(float v)
+{
+	v = wave_xor_add_f32(v, 1);
+	v = wave_xor_add_f32(v, 2);
+	v = wave_xor_add_f32(v, 7);
+	return wave_xor_add_f32(v, 15);
+}
+static inline float wave_sum_f32_lane63(float v)
+{
+	v = wave_row_sum16_f32(v);
+	float r[4];
+	for (int k = 0; k < 4; k++) r[k] = wave_readlane_f32(v, 16 * k + 15);
+	return (r[3] + r[2]) + (r[1] + r[0]);   // (valid in every lane)
+}
+// wave_reduce9_swap_f32 plus the row sums of a tenth value.  The ninth and tenth travel in ONE 64-bit exchange, so that the twin
+// takes the same number of rendezvous as hipemu's nine-value form -- the emulator switches waves at every rendezvous, and the
+// order of the waves' LDS adds (and with it the last bits of the nine sums) stays that of the nine-value kernel.
+static inline void wave_reduce10_swap_f32(const float (&v)[10], float& packed, float& ninth_row, float& tenth_row)
+{
+	float t[9];
+	for (int c = 0; c < 9; c++) t[c] = v[c];
+	uint32_t b8, b9;
+	memcpy(&b8, &v[8], 4);
+	memcpy(&b9, &v[9], 4);
+	const uint64_t* s = ::hipemu::wave_exchange((uint64_t)b8 | ((uint64_t)b9 << 32));
+	float r8 = 0.f, r9 = 0.f;
+	for (int i = 0; i < 16; i++) {
+		const uint64_t w = s[(::hipemu::lane() & ~15) + i];
+		const uint32_t lo = (uint32_t)w, hi = (uint32_t)(w >> 32);
+		float f8, f9;
+		memcpy(&f8, &lo, 4);
+		memcpy(&f9, &hi, 4);
+		r8 += f8;
+		r9 += f9;
+	}
+	::hipemu::wave_sync();
+	wave_reduce9_f32(t);
+	packed = t[wave_swap9_component(::hipemu::lane())];
+	ninth_row = r8;
+	tenth_row = r9;
+}
 static inline float4 load_stream_f4(const float4* p) { return *p; }
 static inline void store_stream_f4(float4* p, const float4 v) { *p = v; }
 #define GSR_SCHED_BARRIER() ((void)0)
@@ -156,6 +207,17 @@ __device__ __forceinline__ float wave_sum_f32_lane63(float v)
 	return v;
 }
 
+// Sum over the lane's row of 16 lanes, valid in every lane of the row (4 DPP adds: the ninth value's part of
+// wave_reduce9_swap_f32 below, for one more value that is reduced like it).
+__device__ __forceinline__ float wave_row_sum16_f32(float v)
+{
+	v += dpp_f32<DPP_QUAD_PERM_1032>(0.f, v);
+	v += dpp_f32<DPP_QUAD_PERM_2301>(0.f, v);
+	v += dpp_f32<DPP_ROW_HALF_MIRROR>(0.f, v);
+	v += dpp_f32<DPP_ROW_MIRROR>(0.f, v);
+	return v;
+}
+
 // Nine independent full-wave sums at once (the 9 per-Gaussian gradient components of the
 // backward blend); results valid in lane 63.  Interleaving the chains hides DPP latency.
 __device__ __forceinline__ void wave_reduce9_f32(float (&v)[9])
@@ -227,6 +289,12 @@ __device__ __forceinline__ void wave_reduce9_swap_f32(const float (&v)[9], float
 	n += dpp_f32<DPP_ROW_HALF_MIRROR>(0.f, n);
 	n += dpp_f32<DPP_ROW_MIRROR>(0.f, n);
 	ninth_row = n;
+}
+// ... and a tenth value reduced like the ninth: its row sums of 16 (the depth map's dL/dz, blend_bwd.hip: 4 more DPP adds)
+__device__ __forceinline__ void wave_reduce10_swap_f32(const float (&v)[10], float& packed, float& ninth_row, float& tenth_row)
+{
+	wave_reduce9_swap_f32(*reinterpret_cast<const float(*)[9]>(&v[0]), packed, ninth_row);
+	tenth_row = wave_row_sum16_f32(v[9]);
 }
 // the value whose total `packed` holds in this lane
 __device__ __forceinline__ int wave_swap9_component(int lane)

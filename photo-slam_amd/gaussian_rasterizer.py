@@ -49,6 +49,53 @@ class GaussianRasterizationSettings:
     # renderFromPose).  GaussianRasterizer.forward also takes that path by itself under torch.no_grad() and when no input
     # requires grad; the outputs then carry no grad_fn.
     forward_only_: bool = False
+    # extension: GaussianRasterizer.forward also renders the depth map sum z alpha T and the alpha map 1 - T_final (include/gsr.h:
+    # gsr_forward_args.out_depth / out_alpha) and returns (color, radii, depth, alpha); both maps are differentiable
+    render_depth_: bool = False
+
+
+def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth=None, alpha=None):
+    """the forward of both autograd Functions (depth / alpha: [H,W] tensors the maps are rendered into, or None)"""
+    num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansCUDA(
+        s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
+        s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
+        s.campos_, s.prefiltered_, s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0), s.sh_adam_,   # sh_adam_: lazy mode brings visible rows up to date first
+        s.workspace_, out_depth=depth, out_alpha=alpha)
+    ctx.set_materialize_grads(False)   # (no zero tensor for the unused gradient of `radii`)
+    ctx.num_rendered = num_rendered
+    ctx.raster_settings = s
+    ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
+                          binningBuffer, imgBuffer)
+    ctx.mark_non_differentiable(radii)
+    return color, radii
+
+
+def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None):
+    """the backward of both autograd Functions: any subset of the image gradients (None = that image took no part in the loss;
+    a missing colour gradient next to a map's is zeros)"""
+    if grad_out_color is None and grad_depth is None and grad_alpha is None:   # (set_materialize_grads(False)): no gradients
+        return (None,) * 9
+    s = ctx.raster_settings
+    colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = \
+        ctx.saved_tensors
+    if grad_out_color is None:
+        grad_out_color = torch.zeros((3, int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
+    cont = lambda t: None if t is None else t.contiguous().float()
+    (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+     dL_drotations) = rp.RasterizeGaussiansBackwardCUDA(
+        s.bg_, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier_, cov3Ds_precomp, s.viewmatrix_,
+        s.projmatrix_, s.tanfovx_, s.tanfovy_, grad_out_color, sh, s.sh_degree_, s.campos_, geomBuffer,
+        ctx.num_rendered, binningBuffer, imgBuffer, s.raw_params_, s.sh_grad_view_,
+        # view-factored mode: the SH step follows the exchange (gsr_sh_adam_from_views); sh_adam_ -- its lazy form -- served
+        # the forward pass (rows this view sees caught up) and lets backward run this step's slice of the rotating
+        # catch-up next to the blend kernel
+        s.sh_adam_ if (s.sh_grad_view_ is None or (s.sh_adam_ or {}).get("row_step") is not None) else None, s.view_stats_,
+        s.geom_adam_, s.training_outputs_only_, dL_ddepth=cont(grad_depth), dL_dalpha=cont(grad_alpha))
+    # order of src/gaussian_rasterizer.cpp:159-179
+    def g(t, like):   # (None where an extension took the gradient's place)
+        return t if like.numel() and t is not None else None
+    return (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity,
+            g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
 
 
 class GaussianRasterizerFunction(torch.autograd.Function):
@@ -56,54 +103,49 @@ class GaussianRasterizerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        s = raster_settings
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansCUDA(
-            s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
-            s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
-            s.campos_, s.prefiltered_, s.raw_params_ | (8 if s.cull_empty_tiles_ else 0), s.sh_adam_,   # sh_adam_: lazy mode brings visible rows up to date first
-            s.workspace_)
-        ctx.set_materialize_grads(False)   # (no zero tensor for the unused gradient of `radii`)
-        ctx.num_rendered = num_rendered
-        ctx.raster_settings = s
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
-        return color, radii
+        return _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
-        if grad_out_color is None:   # the image took no part in the loss (set_materialize_grads(False)): no gradients
-            return (None,) * 9
-        s = ctx.raster_settings
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = \
-            ctx.saved_tensors
-        (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-         dL_drotations) = rp.RasterizeGaussiansBackwardCUDA(
-            s.bg_, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier_, cov3Ds_precomp, s.viewmatrix_,
-            s.projmatrix_, s.tanfovx_, s.tanfovy_, grad_out_color, sh, s.sh_degree_, s.campos_, geomBuffer,
-            ctx.num_rendered, binningBuffer, imgBuffer, s.raw_params_, s.sh_grad_view_,
-            # view-factored mode: the SH step follows the exchange (gsr_sh_adam_from_views); sh_adam_ -- its lazy form -- served
-            # the forward pass (rows this view sees caught up) and lets backward run this step's slice of the rotating
-            # catch-up next to the blend kernel
-            s.sh_adam_ if (s.sh_grad_view_ is None or (s.sh_adam_ or {}).get("row_step") is not None) else None, s.view_stats_,
-            s.geom_adam_, s.training_outputs_only_)
-        # order of src/gaussian_rasterizer.cpp:159-179
-        def g(t, like):   # (None where an extension took the gradient's place)
-            return t if like.numel() and t is not None else None
-        return (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity,
-                g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
+        return _backward(ctx, grad_out_color)
+
+
+class GaussianRasterizerDepthFunction(torch.autograd.Function):
+    """GaussianRasterizerFunction with the depth and alpha maps (settings.render_depth_): returns (color, radii, depth, alpha).
+    Backward takes any subset of the three image gradients (a missing colour gradient is zeros, a missing depth / alpha gradient
+    is left out of the call: gsr_backward_args.dL_ddepth / dL_dalpha)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        s = raster_settings
+        depth = torch.zeros((int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
+        alpha = torch.zeros_like(depth)
+        color, radii = _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth, alpha)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth, grad_alpha):
+        return _backward(ctx, grad_out_color, grad_depth, grad_alpha)
 
 
 def _rasterize_forward_only(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s):
     """The forward pass alone (GSR_FORWARD_ONLY): RasterizeGaussiansCUDA directly, no autograd node, no buffers kept.  Only the
-    lazy form of sh_adam_ concerns a forward pass (its rows are then read, not written)."""
+    lazy form of sh_adam_ concerns a forward pass (its rows are then read, not written).  With s.render_depth_ the depth and alpha
+    maps are rendered too: (color, radii, depth, alpha)."""
     lazy = s.sh_adam_ if s.sh_adam_ is not None and s.sh_adam_.get("row_step") is not None else None
+    depth = alpha = None
+    if s.render_depth_:
+        depth = torch.zeros((int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
+        alpha = torch.zeros_like(depth)
     with torch.no_grad():
         _, color, radii, _, _, _ = rp.RasterizeGaussiansCUDA(
             s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
             s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
             s.campos_, s.prefiltered_,
-            s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0) | capi.FORWARD_ONLY, lazy, s.workspace_)
+            s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0) | capi.FORWARD_ONLY, lazy, s.workspace_,
+            out_depth=depth, out_alpha=alpha)
+    if s.render_depth_:
+        return color, radii, depth, alpha
     return color, radii
 
 
@@ -145,6 +187,9 @@ class GaussianRasterizer(torch.nn.Module):
                 t is not None and t.requires_grad
                 for t in (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)):
             return _rasterize_forward_only(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, s)
+        if s.render_depth_:   # (color, radii, depth, alpha)
+            return GaussianRasterizerDepthFunction.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                         cov3D_precomp, s)
         color, radii = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                           cov3D_precomp, self.raster_settings_)
         return color, radii

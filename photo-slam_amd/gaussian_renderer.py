@@ -36,8 +36,10 @@ class GaussianRenderer:
     @staticmethod
     def render(viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color=None,
                scaling_modifier=1.0, use_override_color=False, fuse_activations=True, sh_grad_view=None, sh_adam=None, view_stats=None,
-               geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None, forward_only=False):
-        """returns (render, viewspace_points, visibility_filter, radii)
+               geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None, forward_only=False,
+               render_depth=False):
+        """returns (render, viewspace_points, visibility_filter, radii), with render_depth (render, viewspace_points,
+        visibility_filter, radii, depth, alpha)
 
         fuse_activations (extension; False = the reference data flow): hand the raw opacity / scaling / rotation
         leaves to the rasterizer, which applies sigmoid / exp / normalize in preprocess and their chain rule in the
@@ -52,7 +54,11 @@ class GaussianRenderer:
         forward_only (extension): no backward pass follows (a viewer's or an evaluation render; implied under torch.no_grad()) --
         the rasterizer prepares nothing for one (GSR_FORWARD_ONLY), screenspace_points is a plain tensor, and on a model whose SH
         rows are stepped lazily the rows are read as they are and caught up in registers only: the model is neither flushed nor
-        changed, and its lazy state survives for the next train step."""
+        changed, and its lazy state survives for the next train step.
+
+        render_depth (extension): the depth map sum z alpha T and the alpha map 1 - T_final ([H, W] each, include/gsr.h:
+        gsr_forward_args.out_depth / out_alpha) are appended to the tuple; both are differentiable (a depth or alpha loss
+        reaches the positions, opacities, scales and rotations)."""
         env = os.environ.get("GSR_CULL_EMPTY_TILES")
         if env:
             cull_empty_tiles = env == "1"
@@ -85,7 +91,8 @@ class GaussianRenderer:
             viewpoint_camera.camera_center_, False, raw,
             sh_grad_view if sh_in_rasterizer else None, sh_adam if sh_in_rasterizer else None, view_stats,
             geom_adam if raw == 7 else None, bool((geom_adam is not None or training_outputs_only) and raw == 7),
-            cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace, forward_only_=forward_only)
+            cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace, forward_only_=forward_only,
+            render_depth_=bool(render_depth))
         rasterizer = GaussianRasterizer(raster_settings)
         means3D = pc.getXYZ()
         means2D = screenspace_points
@@ -113,7 +120,10 @@ class GaussianRenderer:
         else:
             shs, has_shs = pc.getFeatures(), True
         has_sr = not pipe.compute_cov3D_
-        rendered_image, radii = rasterizer(means3D, means2D, opacity, has_shs, has_color_precomp, has_sr, has_sr,
-                                           pipe.compute_cov3D_, shs, colors_precomp, scales, rotations, cov3D_precomp)
+        out = rasterizer(means3D, means2D, opacity, has_shs, has_color_precomp, has_sr, has_sr,
+                         pipe.compute_cov3D_, shs, colors_precomp, scales, rotations, cov3D_precomp)
+        rendered_image, radii = out[0], out[1]
         # (visibility_filter is one more launch: with the fused geometry step its consumers are fused too -- None then)
+        if render_depth:
+            return rendered_image, screenspace_points, (None if slim else radii > 0), radii, out[2], out[3]
         return rendered_image, screenspace_points, (None if slim else radii > 0), radii

@@ -11,8 +11,10 @@
 
 #include <array>
 #include <cmath>
+#include <limits>
 #include <map>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -202,7 +204,15 @@ public:
 	TrainStep& operator=(const TrainStep&) = delete;
 	// forward + backward only (gradients left on the leaves, statistics gathered): lets a data-parallel
 	// driver all-reduce before finishOneIteration()
-	torch::Tensor renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask);
+	torch::Tensor renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask)
+	{
+		return renderAndBackward(kf, gt_image, mask, torch::Tensor());
+	}
+	// ... with the keyframe's [H,W] sensor depth (an RGB-D session's img_auxiliary_undist_): with depth_loss_weight_ != 0 the depth
+	// L1 loss (loss_utils::depth_l1 over depth_min_ < gt < depth_max_) joins the RGB loss before the one backward pass; undefined
+	// gt_depth or weight 0 = the RGB loss alone
+	torch::Tensor renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
+	                                torch::Tensor gt_depth);
 	void finishOneIteration();
 	// finishOneIteration() in three pieces for the overlapped data-parallel step (bench.py): statistics, then Adam per
 	// group as the reductions complete, then the gradient reset
@@ -220,6 +230,26 @@ public:
 		finishOneIteration();
 		return loss;
 	}
+	// an RGB-D keyframe: the depth loss of renderAndBackward(kf, gt_image, mask, gt_depth) (not with a process group: throws
+	// when the weight is non-zero)
+	torch::Tensor trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
+	                                   torch::Tensor gt_depth)
+	{
+		if (process_group_) {
+			if (usesDepthLoss(gt_depth))
+				throw std::runtime_error("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)");
+			return trainForOneIterationDataParallel(kf, gt_image, mask);
+		}
+		auto loss = renderAndBackward(kf, gt_image, mask, gt_depth);
+		finishOneIteration();
+		return loss;
+	}
+	// The depth loss of RGB-D keyframes: depth_loss_weight_ * the L1 distance of the rendered depth map (sum z alpha T) to the
+	// sensor's over the pixels with depth_min_ < gt < depth_max_ (RGBD.min_depth / RGBD.max_depth), divided by H W.  0 = off.
+	float depth_loss_weight_ = 0.0f;
+	float depth_min_ = 0.0f;
+	float depth_max_ = std::numeric_limits<float>::infinity();
+	bool usesDepthLoss(const torch::Tensor& gt_depth) const { return gt_depth.defined() && depth_loss_weight_ != 0.0f; }
 	// Keyframe batches, one keyframe per rank: with a process group set, trainForOneIteration() is the
 	// data-parallel step -- render + backward of THIS rank's keyframe, the gradient exchange over c10d (RCCL on the GPU boxes:
 	// ViewFactoredExchange by default, the plain GradientReduction otherwise; host/include/keyframe_batch_exchange.h), the
@@ -278,6 +308,8 @@ public:
 	// overwrite the buffers that forward saved -- with lazily stepped SH rows read as they are: no flush, no counter advanced,
 	// nothing of the model touched.  Returns the [3,H,W] image.
 	torch::Tensor renderView(std::shared_ptr<GaussianKeyframe> kf);
+	// ... with the depth and alpha maps: (image, depth, alpha), [H,W] each (GaussianRenderer::renderWithDepth)
+	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf);
 	RasterWorkspace view_workspace_;
 	bool early_gather_ = true;        // the exchange's all-gather waits for the colour gradients only, not for the whole backward pass
 	// The view-factored exchange in its PACKED form (include/gsr.h: gsr_pack_color_view): every rank sends only the rows its

@@ -94,6 +94,10 @@ struct GaussianRasterizationExtensions {
 	// the reference's GaussianMapper::renderFromPose.  GaussianRasterizer(Ex)::forward also takes that path by itself when grad
 	// mode is off or no input requires grad; the outputs then carry no grad_fn.
 	bool forward_only_ = false;
+	// the depth map sum z alpha T and the alpha map 1 - T_final (include/gsr.h: gsr_forward_args.out_depth / out_alpha) as two
+	// more outputs of GaussianRasterizerFunctionEx -- (color, radii, depth, alpha), both maps differentiable; its backward takes
+	// any subset of the three image gradients.  Set by GaussianRasterizerEx::forwardWithDepth (forward() renders no maps).
+	bool render_depth_ = false;
 };
 
 class GaussianRasterizerFunctionEx : public torch::autograd::Function<GaussianRasterizerFunctionEx> {
@@ -119,5 +123,11 @@ public:
 	                                                 bool has_rotations, bool has_cov3D_precomp, torch::Tensor shs,
 	                                                 torch::Tensor colors_precomp, torch::Tensor scales,
 	                                                 torch::Tensor rotations, torch::Tensor cov3D_precomp);
+	// forward() with the depth and alpha maps: (color, radii, depth, alpha), [H,W] each (extensions_.render_depth_); under
+	// NoGradGuard / forward_only_ / no input requiring grad the forward-only path renders the same maps
+	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> forwardWithDepth(
+	    torch::Tensor means3D, torch::Tensor means2D, torch::Tensor opacities, bool has_shs, bool has_colors_precomp,
+	    bool has_scales, bool has_rotations, bool has_cov3D_precomp, torch::Tensor shs, torch::Tensor colors_precomp,
+	    torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3D_precomp);
 	GaussianRasterizationExtensions extensions_;
 };

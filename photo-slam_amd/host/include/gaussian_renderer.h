@@ -83,6 +83,43 @@ public:
 	    RasterWorkspace* workspace = nullptr /* extension: GaussianRasterizationExtensions::workspace_ */,
 	    bool forward_only = false /* extension: GaussianRasterizationExtensions::forward_only_ (implied when grad mode is off) */)
 	{
+		auto r = render_impl(false, viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color, scaling_modifier,
+		                     use_override_color, fuse_activations, sh_grad_view, sh_adam, view_stats, geom_adam, cull_empty_tiles,
+		                     workspace, forward_only);
+		return std::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r));
+	}
+
+	// render() with the depth map sum z alpha T and the alpha map 1 - T_final ([H,W] each; include/gsr.h:
+	// gsr_forward_args.out_depth / out_alpha) appended: (render, viewspace_points, visibility_filter, radii, depth, alpha).  Both
+	// maps are differentiable: a depth or alpha loss reaches the positions, opacities, scales and rotations.
+	template <class Keyframe, class Model>
+	static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> renderWithDepth(
+	    std::shared_ptr<Keyframe> viewpoint_camera, int image_height, int image_width, std::shared_ptr<Model> pc,
+	    GaussianPipelineParams& pipe, torch::Tensor& bg_color, torch::Tensor& override_color,
+	    float scaling_modifier = 1.0f, bool use_override_color = false, bool fuse_activations = false,
+	    torch::Tensor sh_grad_view = torch::Tensor() /* extension: GaussianRasterizationExtensions::sh_grad_view_ */,
+	    ShAdamStep sh_adam = ShAdamStep() /* extension: GaussianRasterizationExtensions::sh_adam_ */,
+	    std::vector<torch::Tensor> view_stats = {} /* extension: GaussianRasterizationExtensions::view_stats_ */,
+	    GeomAdamStep geom_adam = GeomAdamStep() /* extension: GaussianRasterizationExtensions::geom_adam_ */,
+	    bool cull_empty_tiles = false /* extension: GaussianRasterizationExtensions::cull_empty_tiles_ */,
+	    RasterWorkspace* workspace = nullptr /* extension: GaussianRasterizationExtensions::workspace_ */,
+	    bool forward_only = false /* extension: GaussianRasterizationExtensions::forward_only_ (implied when grad mode is off) */)
+	{
+		return render_impl(true, viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color, scaling_modifier,
+		                   use_override_color, fuse_activations, sh_grad_view, sh_adam, view_stats, geom_adam, cull_empty_tiles,
+		                   workspace, forward_only);
+	}
+
+private:
+	// the body of both: with_depth selects GaussianRasterizerEx::forwardWithDepth (depth and alpha undefined otherwise)
+	template <class Keyframe, class Model>
+	static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> render_impl(
+	    bool with_depth, std::shared_ptr<Keyframe> viewpoint_camera, int image_height, int image_width, std::shared_ptr<Model> pc,
+	    GaussianPipelineParams& pipe, torch::Tensor& bg_color, torch::Tensor& override_color, float scaling_modifier,
+	    bool use_override_color, bool fuse_activations, torch::Tensor sh_grad_view, ShAdamStep sh_adam,
+	    std::vector<torch::Tensor> view_stats, GeomAdamStep geom_adam, bool cull_empty_tiles, RasterWorkspace* workspace,
+	    bool forward_only)
+	{
 		// forward_only (extension): no backward pass follows (a viewer's or an evaluation render) -- the rasterizer prepares
 		// nothing for one (GSR_FORWARD_ONLY), screenspace_points is a plain tensor, and on a model whose SH rows are stepped lazily
 		// the rows are read as they are and caught up in registers only: the model is neither flushed nor changed
@@ -162,14 +199,19 @@ public:
 			shs = lazy_rows ? lazy_shs : pc->getFeatures();
 			has_shs = true;
 		}
-		auto result = rasterizer.forward(means3D, screenspace_points, opacity, has_shs, has_color_precomp, has_scales,
-		                                 has_rotations, has_cov3D_precomp, shs, colors_precomp, scales, rotations,
-		                                 cov3D_precomp);
-		auto rendered_image = std::get<0>(result);
-		auto radii = std::get<1>(result);
+		torch::Tensor rendered_image, radii, depth, alpha;
+		if (with_depth) {
+			std::tie(rendered_image, radii, depth, alpha) =
+			    rasterizer.forwardWithDepth(means3D, screenspace_points, opacity, has_shs, has_color_precomp, has_scales,
+			                                has_rotations, has_cov3D_precomp, shs, colors_precomp, scales, rotations, cov3D_precomp);
+		} else {
+			std::tie(rendered_image, radii) =
+			    rasterizer.forward(means3D, screenspace_points, opacity, has_shs, has_color_precomp, has_scales, has_rotations,
+			                       has_cov3D_precomp, shs, colors_precomp, scales, rotations, cov3D_precomp);
+		}
 		// (visibility_filter = radii > 0 is one more launch: a caller that fused everything that consumes it -- the statistics,
 		// geom_adam.training_outputs_only -- gets an undefined tensor and derives it from radii if it ever wants it)
 		return std::make_tuple(rendered_image, screenspace_points,
-		                       geom_adam.training_outputs_only ? torch::Tensor() : (radii > 0), radii);
+		                       geom_adam.training_outputs_only ? torch::Tensor() : (radii > 0), radii, depth, alpha);
 	}
 };

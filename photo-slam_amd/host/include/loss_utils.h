@@ -52,5 +52,9 @@ torch::Tensor ssim(
 //   (1 - lambda_dssim) * l1_loss(rendered * mask, gt) + lambda_dssim * (1 - ssim(rendered * mask, gt))
 // mask: undefined / empty = all ones.  is_root: the caller promises to call backward() on this very value.
 torch::Tensor fused_l1_ssim(torch::Tensor rendered, torch::Tensor gt, torch::Tensor mask, float lambda_dssim, bool is_root = false);
+// (extension) the depth L1 loss of an RGB-D keyframe (csrc/train_ops.hip, gsr_depth_l1_loss; deterministic):
+//   weight * sum over the pixels with min_depth < gt_depth < max_depth of |depth - gt_depth|, divided by H W
+// depth, gt_depth: [H,W] float32 on one device; differentiable in depth.
+torch::Tensor depth_l1(torch::Tensor depth, torch::Tensor gt_depth, float weight, float min_depth, float max_depth);
 
 }

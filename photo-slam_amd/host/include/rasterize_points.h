@@ -71,6 +71,16 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
     const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
     const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
     const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace = nullptr);
+// ... with the depth and alpha maps (gsr_forward_args.out_depth / out_alpha): caller-allocated contiguous float32 [H,W] tensors on
+// the device of means3D, written for every pixel; undefined = not rendered.  depth = sum z alpha T, alpha = 1 - T_final.
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
+    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
+    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
+    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
+    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+    const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace,
+    const torch::Tensor& out_depth, const torch::Tensor& out_alpha);
 
 // Extension, optimizer-in-backward for xyz / opacity / scaling / rotation (gsr_geom_adam of include/gsr.h): when param is
 // filled (four entries each, in that order), backward applies this Adam step to the four tensors IN PLACE instead of computing
@@ -125,6 +135,20 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
                                const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                                const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
                                const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam);
+// ... with the upstream gradients of the depth and alpha maps (gsr_backward_args.dL_ddepth / dL_dalpha): [H,W] each, either
+// undefined (zeros); the forward pass need not have rendered the maps
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor>
+RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
+                               const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
+                               const float scale_modifier, const torch::Tensor& cov3D_precomp,
+                               const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx,
+                               const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
+                               const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
+                               const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                               const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
+                               const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam,
+                               const torch::Tensor& dL_ddepth, const torch::Tensor& dL_dalpha);
 
 // gsr_sh_grad_from_views (include/gsr.h): the [P,M,3] SH gradient of a keyframe batch from the gathered
 // [n_views,P,3] dL_dcolor_view tensors and the [n_views,3] camera centres; scale = 1/n_views for the batch mean

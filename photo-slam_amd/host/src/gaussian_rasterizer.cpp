@@ -20,11 +20,16 @@ torch::autograd::tensor_list forward_impl(torch::autograd::AutogradContext* ctx,
                                           torch::Tensor rotations, torch::Tensor cov3Ds_precomp,
                                           const GaussianRasterizationSettings& s, const GaussianRasterizationExtensions& e)
 {
+	torch::Tensor depth, alpha;   // (render_depth_: the two maps, written for every pixel)
+	if (e.render_depth_) {
+		depth = torch::zeros({s.image_height_, s.image_width_}, means3D.options().dtype(torch::kFloat32));
+		alpha = torch::zeros({s.image_height_, s.image_width_}, means3D.options().dtype(torch::kFloat32));
+	}
 	auto r = RasterizeGaussiansCUDA(s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_,
 	                                cov3Ds_precomp, s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_,
 	                                s.image_height_, s.image_width_, sh, s.sh_degree_, s.campos_, s.prefiltered_,
 	                                e.raw_params_ | (e.cull_empty_tiles_ ? 8 /* GSR_CULL_EMPTY_TILES, include/gsr.h */ : 0),
-	                                e.sh_adam_ /* lazy mode: visible rows are brought up to date first */, e.workspace_);
+	                                e.sh_adam_ /* lazy mode: visible rows are brought up to date first */, e.workspace_, depth, alpha);
 	// (no zero tensor for the unused gradient of `radii`: autograd would otherwise fill P ints per backward)
 	ctx->set_materialize_grads(false);
 	ctx->saved_data["num_rendered"] = std::get<0>(r);
@@ -33,6 +38,7 @@ torch::autograd::tensor_list forward_impl(torch::autograd::AutogradContext* ctx,
 	ctx->saved_data["tanfovy"] = static_cast<double>(s.tanfovy_);
 	ctx->saved_data["sh_degree"] = s.sh_degree_;
 	ctx->saved_data["raw_params"] = e.raw_params_;
+	if (e.render_depth_) ctx->saved_data["image_hw"] = std::vector<int64_t>{s.image_height_, s.image_width_};
 	if (e.sh_grad_view_.defined()) ctx->saved_data["sh_grad_view"] = e.sh_grad_view_;
 	if (e.sh_adam_.color_view_ready_stream)
 		ctx->saved_data["color_view_ready_stream"] = static_cast<int64_t>(reinterpret_cast<intptr_t>(e.sh_adam_.color_view_ready_stream));
@@ -68,6 +74,7 @@ torch::autograd::tensor_list forward_impl(torch::autograd::AutogradContext* ctx,
 	ctx->save_for_backward({s.bg_, s.viewmatrix_, s.projmatrix_, s.campos_, colors_precomp, means3D, scales, rotations,
 	                        cov3Ds_precomp, radii, sh, std::get<3>(r), std::get<4>(r), std::get<5>(r)});
 	ctx->mark_non_differentiable({radii});
+	if (e.render_depth_) return {color, radii, depth, alpha};
 	return {color, radii};
 }
 
@@ -75,10 +82,20 @@ torch::autograd::tensor_list forward_impl(torch::autograd::AutogradContext* ctx,
 torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx, torch::autograd::tensor_list grad_outputs,
                                            int n_extra)
 {
-	if (!grad_outputs[0].defined()) {   // the image took no part in the loss (set_materialize_grads(false)): no gradients
+	// render_depth_: (color, radii, depth, alpha) -- the gradients of the two maps, either undefined (not in the loss)
+	const torch::Tensor dL_ddepth = grad_outputs.size() > 2 ? grad_outputs[2] : torch::Tensor();
+	const torch::Tensor dL_dalpha = grad_outputs.size() > 3 ? grad_outputs[3] : torch::Tensor();
+	// no image took part in the loss (set_materialize_grads(false)): no gradients
+	if (!grad_outputs[0].defined() && !dL_ddepth.defined() && !dL_dalpha.defined()) {
 		torch::autograd::tensor_list none(static_cast<size_t>(8 + n_extra));
 		return none;
 	}
+	torch::Tensor dL_dcolor = grad_outputs[0];
+	if (!dL_dcolor.defined()) {   // (a loss on the maps alone: the colour gradient is zeros)
+		const auto hw = ctx->saved_data["image_hw"].toIntVector();
+		dL_dcolor = torch::zeros({3, hw[0], hw[1]}, dL_ddepth.defined() ? dL_ddepth.options() : dL_dalpha.options());
+	}
+	auto map_grad = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
 	const int num_rendered = static_cast<int>(ctx->saved_data["num_rendered"].toInt());
 	const float scale_modifier = static_cast<float>(ctx->saved_data["scale_modifier"].toDouble());
 	const float tanfovx = static_cast<float>(ctx->saved_data["tanfovx"].toDouble());
@@ -125,13 +142,13 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 	auto v = ctx->get_saved_variables();
 	auto g = RasterizeGaussiansBackwardCUDA(v[0] /*bg*/, v[5] /*means3D*/, v[9] /*radii*/, v[4] /*colors_precomp*/,
 	                                        v[6] /*scales*/, v[7] /*rotations*/, scale_modifier, v[8] /*cov3Ds*/,
-	                                        v[1] /*view*/, v[2] /*proj*/, tanfovx, tanfovy, grad_outputs[0], v[10] /*sh*/,
+	                                        v[1] /*view*/, v[2] /*proj*/, tanfovx, tanfovy, dL_dcolor, v[10] /*sh*/,
 	                                        sh_degree, v[3] /*campos*/, v[11], num_rendered, v[12], v[13], raw_params,
 	                                        sh_grad_view,
 	                                        // view-factored mode: the SH step follows the exchange (gsr_sh_adam_from_views);
 	                                        // sh_adam_ -- its lazy form -- served the forward pass (rows this view sees caught up)
 	                                        // and lets backward run this step's slice of the rotating catch-up
-	                                        bwd_adam, view_stats, geom_adam);
+	                                        bwd_adam, view_stats, geom_adam, map_grad(dL_ddepth), map_grad(dL_dalpha));
 	// gradient order of the forward inputs (src/gaussian_rasterizer.cpp:159-179); absent optionals get none
 	auto opt = [](const torch::Tensor& grad, const torch::Tensor& input) {
 		return (input.defined() && input.numel() != 0 && grad.defined()) ? grad : torch::Tensor();
@@ -178,11 +195,14 @@ bool no_backward(const std::initializer_list<const torch::Tensor*> inputs)
 
 // The forward pass alone (GSR_FORWARD_ONLY): RasterizeGaussiansCUDA directly with the bit, no autograd node, no buffers kept.
 // Only the lazy form of sh_adam_ concerns a forward pass (its rows are then read, not written).
+// depth / alpha: defined = the maps are rendered into them (render_depth_)
 std::tuple<torch::Tensor, torch::Tensor> forward_only_impl(const torch::Tensor& means3D, const torch::Tensor& sh,
                                                            const torch::Tensor& colors_precomp, const torch::Tensor& opacities,
                                                            const torch::Tensor& scales, const torch::Tensor& rotations,
                                                            const torch::Tensor& cov3Ds_precomp, const GaussianRasterizationSettings& s,
-                                                           const GaussianRasterizationExtensions& e)
+                                                           const GaussianRasterizationExtensions& e,
+                                                           const torch::Tensor& depth = torch::Tensor(),
+                                                           const torch::Tensor& alpha = torch::Tensor())
 {
 	torch::NoGradGuard no_grad;
 	const ShAdamStep lazy = e.sh_adam_.row_step.defined() ? e.sh_adam_ : ShAdamStep();
@@ -190,7 +210,7 @@ std::tuple<torch::Tensor, torch::Tensor> forward_only_impl(const torch::Tensor& 
 	                                cov3Ds_precomp, s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_,
 	                                s.image_height_, s.image_width_, sh, s.sh_degree_, s.campos_, s.prefiltered_,
 	                                e.raw_params_ | (e.cull_empty_tiles_ ? GSR_CULL_EMPTY_TILES : 0) | GSR_FORWARD_ONLY, lazy,
-	                                e.workspace_);
+	                                e.workspace_, depth, alpha);
 	return std::make_tuple(std::get<1>(r), std::get<2>(r));
 }
 
@@ -257,4 +277,27 @@ std::tuple<torch::Tensor, torch::Tensor> GaussianRasterizerEx::forward(
 	auto result = GaussianRasterizerFunctionEx::apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
 	                                                  cov3D_precomp, raster_settings_, extensions_);
 	return std::make_tuple(result[0], result[1]);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> GaussianRasterizerEx::forwardWithDepth(
+    torch::Tensor means3D, torch::Tensor means2D, torch::Tensor opacities, bool has_shs, bool has_colors_precomp,
+    bool has_scales, bool has_rotations, bool has_cov3D_precomp, torch::Tensor shs, torch::Tensor colors_precomp,
+    torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3D_precomp)
+{
+	validate_and_fill(means3D, has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp,
+	                  scales, rotations, cov3D_precomp);
+	GaussianRasterizationExtensions e = extensions_;
+	e.render_depth_ = true;
+	if (e.forward_only_ ||
+	    no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp})) {
+		const auto opts = means3D.options().dtype(torch::kFloat32);
+		auto depth = torch::zeros({raster_settings_.image_height_, raster_settings_.image_width_}, opts);
+		auto alpha = torch::zeros({raster_settings_.image_height_, raster_settings_.image_width_}, opts);
+		auto r = forward_only_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings_, e,
+		                           depth, alpha);
+		return std::make_tuple(std::get<0>(r), std::get<1>(r), depth, alpha);
+	}
+	auto result = GaussianRasterizerFunctionEx::apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+	                                                  cov3D_precomp, raster_settings_, e);
+	return std::make_tuple(result[0], result[1], result[2], result[3]);
 }

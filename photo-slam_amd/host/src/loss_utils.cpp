@@ -54,6 +54,32 @@ public:
 	}
 };
 
+class DepthL1Function : public torch::autograd::Function<DepthL1Function> {
+public:
+	static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth, torch::Tensor gt_depth, double weight,
+	                             double min_depth, double max_depth)
+	{
+		auto d = depth.contiguous(), g = gt_depth.contiguous();
+		if (d.dim() != 2 || g.sizes() != d.sizes() || d.scalar_type() != torch::kFloat32 || g.scalar_type() != torch::kFloat32)
+			throw std::runtime_error("depth_l1: depth and gt_depth must be float32 [H, W] tensors of the same shape");
+		const int H = static_cast<int>(d.size(0)), W = static_cast<int>(d.size(1));
+		auto grad = torch::empty_like(d);
+		auto loss = torch::empty({1}, d.options());
+		auto scratch = torch::empty({static_cast<int64_t>(gsr_depth_loss_scratch_bytes(W, H))}, d.options().dtype(torch::kByte));
+		check(gsr_depth_l1_loss(d.data_ptr<float>(), g.data_ptr<float>(), W, H, static_cast<float>(min_depth),
+		                        static_cast<float>(max_depth), static_cast<float>(weight), grad.data_ptr<float>(),
+		                        loss.data_ptr<float>(), reinterpret_cast<char*>(scratch.data_ptr()), stream_of(d)),
+		      "gsr_depth_l1_loss");
+		ctx->save_for_backward({grad});
+		return loss[0];
+	}
+	static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::tensor_list go)
+	{
+		auto grad = ctx->get_saved_variables()[0];
+		return {grad * go[0], torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor()};
+	}
+};
+
 // what the kernels cover: one float32 [3,H,W] (or [1,3,H,W]) image pair on one device, the target without a gradient
 bool fused_applies(const torch::Tensor& a, const torch::Tensor& b)
 {
@@ -78,6 +104,12 @@ torch::Tensor fused_l1_ssim(torch::Tensor rendered, torch::Tensor gt, torch::Ten
 {
 	if (!mask.defined()) mask = torch::empty({0}, gt.options());   // (autograd::Function::apply needs every tensor argument defined)
 	return FusedL1SSIMFunction::apply(rendered, gt, mask, static_cast<double>(lambda_dssim), is_root);
+}
+
+torch::Tensor depth_l1(torch::Tensor depth, torch::Tensor gt_depth, float weight, float min_depth, float max_depth)
+{
+	return DepthL1Function::apply(depth, gt_depth, static_cast<double>(weight), static_cast<double>(min_depth),
+	                              static_cast<double>(max_depth));
 }
 
 torch::Tensor l1_loss(torch::Tensor &network_output, torch::Tensor &gt)

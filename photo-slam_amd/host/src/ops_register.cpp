@@ -159,6 +159,13 @@ torch::Tensor trainer_render_and_backward(int64_t h, torch::Tensor view, torch::
 {
 	return get(h)->renderAndBackward(make_kf(view, proj, campos, fovx, fovy, H, W), gt, mask).detach();
 }
+// ... for an RGB-D keyframe: the depth loss (depth_loss_weight / depth_min / depth_max of trainer_set_options) joins the RGB loss
+torch::Tensor trainer_render_and_backward_depth(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx,
+                                                double fovy, int64_t H, int64_t W, torch::Tensor gt, torch::Tensor mask,
+                                                torch::Tensor gt_depth)
+{
+	return get(h)->renderAndBackward(make_kf(view, proj, campos, fovx, fovy, H, W), gt, mask, gt_depth).detach();
+}
 // GaussianRenderer::render on the trainer's model with the pipeline flags of GaussianPipelineParams (convert_SHs_,
 // compute_cov3D_: src/gaussian_renderer.cpp:78-113): (image, radii); the image is attached to the model's leaves
 std::tuple<torch::Tensor, torch::Tensor> trainer_render(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos,
@@ -179,6 +186,13 @@ torch::Tensor trainer_render_view(int64_t h, torch::Tensor view, torch::Tensor p
                                   int64_t H, int64_t W)
 {
 	return get(h)->renderView(make_kf(view, proj, campos, fovx, fovy, H, W));
+}
+// TrainStep::renderViewWithDepth: (image, depth, alpha) of a forward-only render into the second workspace
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> trainer_render_view_depth(int64_t h, torch::Tensor view, torch::Tensor proj,
+                                                                                  torch::Tensor campos, double fovx, double fovy,
+                                                                                  int64_t H, int64_t W)
+{
+	return get(h)->renderViewWithDepth(make_kf(view, proj, campos, fovx, fovy, H, W));
 }
 void trainer_finish(int64_t h) { get(h)->finishOneIteration(); }
 void trainer_finish_begin(int64_t h) { get(h)->finishBegin(); }
@@ -207,6 +221,9 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "fused_geom_adam") t->fused_geom_adam_ = v != 0.0;
 		else if (k == "active_sh_degree") t->gaussians_->active_sh_degree_ = std::min((int)v, t->gaussians_->max_sh_degree_);
 		else if (k == "cull_empty_tiles") t->cull_empty_tiles_ = v != 0.0;
+		else if (k == "depth_loss_weight") t->depth_loss_weight_ = static_cast<float>(v);
+		else if (k == "depth_min") t->depth_min_ = static_cast<float>(v);
+		else if (k == "depth_max") t->depth_max_ = static_cast<float>(v);
 		else if (k == "persistent_workspace") t->persistent_workspace_ = v != 0.0;
 		else if (k == "early_gather") t->early_gather_ = v != 0.0;
 		else if (k == "packed_exchange") t->packed_exchange_ = v != 0.0;
@@ -450,6 +467,8 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("trainer_render_and_backward", &trainer_render_and_backward);
 	m.def("trainer_render", &trainer_render);
 	m.def("trainer_render_view", &trainer_render_view);
+	m.def("trainer_render_and_backward_depth", &trainer_render_and_backward_depth);
+	m.def("trainer_render_view_depth", &trainer_render_view_depth);
 	m.def("trainer_finish", &trainer_finish);
 	m.def("trainer_finish_begin", &trainer_finish_begin);
 	m.def("trainer_adam_group", &trainer_adam_group);

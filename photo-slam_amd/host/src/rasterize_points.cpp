@@ -105,6 +105,16 @@ void fill_sh_adam(const ShAdamStep& s, float* param, gsr_sh_adam& adam, gsr_sh_a
 	}
 }
 
+// pointer of an [H,W] float32 map argument (out_depth / out_alpha / dL_ddepth / dL_dalpha); undefined = nullptr
+float* map_ptr(const torch::Tensor& t, const torch::Tensor& means3D, int H, int W, const char* name)
+{
+	if (!t.defined()) return nullptr;
+	if (t.dim() != 2 || t.size(0) != H || t.size(1) != W || t.scalar_type() != torch::kFloat32 || !t.is_contiguous() ||
+	    t.device() != means3D.device())
+		throw std::runtime_error(std::string(name) + " must be a contiguous float32 (H, W) tensor on the device of means3D");
+	return const_cast<float*>(t.data_ptr<float>());
+}
+
 }  // namespace
 
 // the reference's exact parameter lists (include/rasterize_points.h:18-37, :39-60): same mangled names
@@ -157,6 +167,20 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
     const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
     const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
     const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace)
+{
+	return RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+	                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+	                              prefiltered, raw_params, sh_adam, workspace, torch::Tensor(), torch::Tensor());
+}
+
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
+    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
+    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
+    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
+    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+    const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace,
+    const torch::Tensor& out_depth, const torch::Tensor& out_alpha)
 {
 	if (means3D.ndimension() != 2 || means3D.size(1) != 3) {
 		AT_ERROR("means3D must have dimensions (num_points, 3)");
@@ -211,6 +235,8 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
 		a.raw_params = raw_params;
 		a.out_color = out_color.data_ptr<float>();
 		a.radii = radii.data_ptr<int>();
+		a.out_depth = map_ptr(out_depth, means3D, H, W, "out_depth");
+		a.out_alpha = map_ptr(out_alpha, means3D, H, W, "out_alpha");
 		gsr_sh_adam adam{};
 		gsr_sh_adam_lazy lazy{};
 		if (sh_adam.row_step.defined()) {   // lazy SH Adam: the forward pass brings visible rows up to date (in place)
@@ -255,6 +281,25 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
                                const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                                const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
                                const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam)
+{
+	return RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+	                                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer,
+	                                      R, binningBuffer, imageBuffer, raw_params, dL_dcolor_view, sh_adam, view_stats, geom_adam,
+	                                      torch::Tensor(), torch::Tensor());
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor>
+RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
+                               const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
+                               const float scale_modifier, const torch::Tensor& cov3D_precomp,
+                               const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx,
+                               const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
+                               const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
+                               const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                               const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
+                               const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam,
+                               const torch::Tensor& dL_ddepth, const torch::Tensor& dL_dalpha)
 {
 	const int P = static_cast<int>(means3D.size(0));
 	const int H = static_cast<int>(dL_dout_color.size(1));
@@ -346,6 +391,8 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 		a.binning_buffer = bin_c.numel() ? reinterpret_cast<char*>(bin_c.data_ptr()) : nullptr;
 		a.image_buffer = reinterpret_cast<char*>(img_c.data_ptr());
 		a.dL_dpix = dpix.ptr;
+		a.dL_ddepth = map_ptr(dL_ddepth, means3D, H, W, "dL_ddepth");
+		a.dL_dalpha = map_ptr(dL_dalpha, means3D, H, W, "dL_dalpha");
 		a.dL_dmean2D = dL_dmeans2D.defined() ? dL_dmeans2D.data_ptr<float>() : nullptr;
 		a.dL_dconic = nullptr;  // internal to the reference's wrapper (rasterize_points.cu:152)
 		a.dL_dopacity = dL_dopacity.defined() ? dL_dopacity.data_ptr<float>() : nullptr;

@@ -191,8 +191,23 @@ torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf)
 	return std::get<0>(pkg);
 }
 
-torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf)
 {
+	torch::NoGradGuard no_grad;
+	torch::Tensor override_color;
+	auto pkg = GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_,
+	                                             override_color, 1.0f, false, /*fuse_activations=*/true, torch::Tensor(), ShAdamStep(),
+	                                             {}, GeomAdamStep(), cull_empty_tiles_,
+	                                             persistent_workspace_ ? &view_workspace_ : nullptr, /*forward_only=*/true);
+	return std::make_tuple(std::get<0>(pkg), std::get<4>(pkg), std::get<5>(pkg));
+}
+
+torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
+                                           torch::Tensor gt_depth)
+{
+	const bool use_depth = usesDepthLoss(gt_depth);
+	if (use_depth && process_group_)
+		throw std::runtime_error("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)");
 	auto& g = gaussians_;
 	iteration_++;
 	// the position learning rate follows the iteration (src/gaussian_mapper.cpp:672-674) or -- a SLAM session -- the number of
@@ -344,9 +359,19 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	std::vector<torch::Tensor> view_stats;
 	if (iteration_ < o.densify_until_iter_) view_stats = {g->xyz_gradient_accum_, g->denom_, g->max_radii2D_};
 	g->in_lazy_step_ = lazy;
-	auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, g, pipe, background_, override_color,
-	                                    1.0f, false, /*fuse_activations=*/true, sh_grad_view_, sh_adam, view_stats, geom_adam,
-	                                    cull_empty_tiles_, persistent_workspace_ ? &workspace_ : nullptr);
+	// (with the depth loss: the same render with the depth and alpha maps appended, GaussianRenderer::renderWithDepth)
+	auto pkg = use_depth ? GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, g, pipe, background_,
+	                                                         override_color, 1.0f, false, /*fuse_activations=*/true, sh_grad_view_,
+	                                                         sh_adam, view_stats, geom_adam, cull_empty_tiles_,
+	                                                         persistent_workspace_ ? &workspace_ : nullptr)
+	                     : [&] {
+		                       auto p4 = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, g, pipe, background_,
+		                                                          override_color, 1.0f, false, /*fuse_activations=*/true, sh_grad_view_,
+		                                                          sh_adam, view_stats, geom_adam, cull_empty_tiles_,
+		                                                          persistent_workspace_ ? &workspace_ : nullptr);
+		                       return std::make_tuple(std::get<0>(p4), std::get<1>(p4), std::get<2>(p4), std::get<3>(p4),
+		                                              torch::Tensor(), torch::Tensor());
+	                       }();
 	g->in_lazy_step_ = false;
 	if (factored_exchange_ && packed_this_step_) beginCountExchange();   // (the forward pass has left this view's visible count)
 	if (prepacked_this_step_) planPackedView(std::get<3>(pkg));
@@ -376,6 +401,8 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		if (it->second.ones) eff_mask = torch::empty({0}, mask.options());   // (an empty mask = none: FusedL1SSIMFunction::forward)
 	}
 	auto loss = fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
+	// (the sum's backward hands both terms the root's exact 1: is_root stays valid)
+	if (use_depth) loss = loss + loss_utils::depth_l1(std::get<4>(pkg), gt_depth, depth_loss_weight_, depth_min_, depth_max_);
 	// the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward()
 	if (!root_grad_.defined() || root_grad_.device() != loss.device()) root_grad_ = torch::ones_like(loss).detach();
 	loss.backward(root_grad_);

@@ -93,3 +93,38 @@ def fused_l1_ssim_loss(rendered, gt, mask, lambda_dssim, is_root=False):
     """is_root: the caller promises to call .backward() on this very value (upstream gradient exactly 1, as the train step
     does): backward then hands the stored gradient on without the [3,H,W] multiply by one."""
     return _FusedL1SSIM.apply(rendered, gt, mask, lambda_dssim, is_root)
+
+
+# Depth L1 loss of an RGB-D keyframe (csrc/train_ops.hip, gsr_depth_l1_loss):
+#   loss = weight * sum_{min_depth < gt < max_depth} |depth - gt| / (H W)
+# with its gradient w.r.t. the rendered depth map, deterministic (two launches).
+class _DepthL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, gt_depth, weight, min_depth, max_depth):
+        lib = _rp._lib()
+        _rp._check_device(lib, depth, gt_depth)
+        d = depth.contiguous().float()
+        g = gt_depth.contiguous().float()
+        if d.dim() != 2 or g.shape != d.shape:
+            raise RuntimeError("depth and gt_depth must be [H, W] tensors of the same shape")
+        H, W = d.shape
+        grad = torch.empty_like(d)
+        loss = torch.empty(1, dtype=torch.float32, device=d.device)
+        scratch = torch.empty(int(lib.gsr_depth_loss_scratch_bytes(W, H)), dtype=torch.uint8, device=d.device)
+        st = lib.gsr_depth_l1_loss(d.data_ptr(), g.data_ptr(), W, H, float(min_depth), float(max_depth), float(weight),
+                                   grad.data_ptr(), loss.data_ptr(), scratch.data_ptr(), _rp._stream_ptr(d))
+        from . import capi
+        capi.check(lib, st, "gsr_depth_l1_loss")
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (grad,) = ctx.saved_tensors
+        return grad * grad_out, None, None, None, None
+
+
+def depth_l1_loss(depth, gt_depth, weight, min_depth, max_depth):
+    """weight * sum over the pixels with min_depth < gt_depth < max_depth of |depth - gt_depth|, divided by H W (a scalar
+    tensor; differentiable in depth)"""
+    return _DepthL1.apply(depth, gt_depth, weight, min_depth, max_depth)

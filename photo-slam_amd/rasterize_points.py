@@ -98,14 +98,17 @@ class RasterWorkspace:
 
 def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                            viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                           prefiltered, raw_params=0, sh_adam=None, workspace=None):
+                           prefiltered, raw_params=0, sh_adam=None, workspace=None, out_depth=None, out_alpha=None):
     """raw_params (extension, default 0 = reference contract): GSR_RAW_* mask -- opacity / scales / rotations are the
     model's raw parameters and are activated in-kernel (include/gsr.h).  With capi.FORWARD_ONLY in it the call renders the same
     image and radii without preparing anything for a backward pass: the returned buffers are then NOT valid input to
     RasterizeGaussiansBackwardCUDA (include/gsr.h: GSR_FORWARD_ONLY).
     sh_adam (extension, default None): the dict RasterizeGaussiansBackwardCUDA takes; only its lazy mode (row_step set,
     gsr_sh_adam_lazy) concerns the forward pass: visible rows that lag behind take their missed zero-gradient steps first
-    (forward-only: in registers only -- nothing of the Adam state is written)."""
+    (forward-only: in registers only -- nothing of the Adam state is written).
+    out_depth / out_alpha (extension, default None): caller-allocated contiguous float32 [H, W] tensors on the device of means3D
+    that receive the depth map sum z alpha T and the alpha map 1 - T_final (include/gsr.h: gsr_forward_args.out_depth); either
+    may be given alone.  The return tuple is the same."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # AT_ERROR, rasterize_points.cu:57-59
     lib = _lib()
@@ -136,6 +139,8 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
             setattr(a, name, p)
         a.out_color = out_color.data_ptr()
         a.radii = radii.data_ptr()
+        a.out_depth = _image_arg(out_depth, H, W, dev, "out_depth")
+        a.out_alpha = _image_arg(out_alpha, H, W, dev, "out_alpha")
         if sh_adam is not None and sh_adam.get("row_step") is not None:
             if sh is None or not sh.is_contiguous() or sh.dtype != torch.float32:
                 raise RuntimeError("lazy sh_adam needs a contiguous float32 sh tensor (it is updated in place)")
@@ -155,10 +160,20 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
     return rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer
 
 
+def _image_arg(t, H, W, dev, name):
+    """pointer of a [H, W] float32 map argument (out_depth / out_alpha / dL_ddepth / dL_dalpha), None for None"""
+    if t is None:
+        return None
+    if t.shape != (H, W) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+        raise RuntimeError(f"{name} must be a contiguous float32 ({H}, {W}) tensor on the device of means3D")
+    return t.data_ptr()
+
+
 def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                    viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                    geomBuffer, R, binningBuffer, imageBuffer, raw_params=0, dL_dcolor_view=None, sh_adam=None,
-                                   view_stats=None, geom_adam=None, training_outputs_only=False, packed_view=None):
+                                   view_stats=None, geom_adam=None, training_outputs_only=False, packed_view=None,
+                                   dL_ddepth=None, dL_dalpha=None):
     """dL_dcolor_view (extension, default None = reference contract): a [P,3] float tensor that receives the clamp-masked
     colour gradient; dL_dsh is then NOT computed and None is returned in its place (view-factored gradient exchange,
     shGradFromViews below).
@@ -173,7 +188,9 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
     not computed and None is returned in their places.
     training_outputs_only (extension): dL_dmeans2D and dL_dcov3D are not written either (None returned) -- for a caller that
     fuses the densification statistics (view_stats: the only consumer of dL_dmeans2D in a train step) and optimises scales /
-    rotations (no cov3D_precomp)."""
+    rotations (no cov3D_precomp).
+    dL_ddepth / dL_dalpha (extension, default None): [H, W] upstream gradients of the forward pass's out_depth / out_alpha
+    (gsr_backward_args.dL_ddepth / dL_dalpha); either may be None.  The forward pass need not have rendered the maps."""
     lib = _lib()
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
@@ -237,6 +254,8 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
             adam, adam_keep = capi.make_sh_adam(sh, sh_adam)
             a.sh_adam = C.pointer(adam)
         a.dL_dcolor_view = dL_dcolor_view.data_ptr() if factored else None
+        a.dL_ddepth = _image_arg(dL_ddepth, H, W, dev, "dL_ddepth")
+        a.dL_dalpha = _image_arg(dL_dalpha, H, W, dev, "dL_dalpha")
         if packed_view is not None:
             # (message, capacity_rows): a message packViewPlan() prepared -- backward writes its rows and header (gsr_backward_args.packed_view)
             msg, cap = packed_view

@@ -238,17 +238,27 @@ class TrainStep:
         # (TrainStep::fused_geom_adam_ of the C++ host), on the same iterations
         self.fused_geom_adam_ = fused_geom_adam
         self.ema_loss_for_log_ = 0.0
+        # RGB-D keyframes: trainForOneIteration(..., gt_depth) adds depth_loss_weight_ * the L1 distance of the rendered depth map
+        # to the sensor's over the pixels with depth_min_ < gt < depth_max_ (RGBD.min_depth / RGBD.max_depth), divided by H W
+        # (loss_utils.depth_l1_loss).  0 = the RGB loss alone, gt_depth ignored.
+        self.depth_loss_weight_ = 0.0
+        self.depth_min_ = 0.0
+        self.depth_max_ = float("inf")
 
-    def render_view(self, viewpoint_cam):
+    def render_view(self, viewpoint_cam, with_depth=False):
         """A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe):
         forward-only (GSR_FORWARD_ONLY), into the trainer's second workspace, with lazily stepped SH rows read as they are --
-        no flush, no counter advanced, nothing of the model or the training workspace touched.  Returns the [3,H,W] image."""
+        no flush, no counter advanced, nothing of the model or the training workspace touched.  Returns the [3,H,W] image;
+        with_depth: (image, depth, alpha), the [H,W] depth map sum z alpha T and alpha map 1 - T_final."""
         with torch.no_grad():
-            image, _, _, _ = GaussianRenderer.render(
+            out = GaussianRenderer.render(
                 viewpoint_cam, viewpoint_cam.image_height_, viewpoint_cam.image_width_, self.gaussians_, self.pipe_,
                 self.background_, cull_empty_tiles=self.cull_empty_tiles_,
-                workspace=self.view_workspace_ if self.persistent_workspace_ else None, forward_only=True)
-        return image
+                workspace=self.view_workspace_ if self.persistent_workspace_ else None, forward_only=True,
+                render_depth=bool(with_depth))
+        if with_depth:
+            return out[0], out[4], out[5]
+        return out[0]
 
     def _effective_mask(self, mask):
         """rendered * mask with a mask of ones is the identity (src/gaussian_mapper.cpp:692-693; most keyframes carry a full
@@ -268,9 +278,14 @@ class TrainStep:
                 entry = cache[id(mask)] = (weakref.ref(mask), mask._version, bool((mask == 1).all().item()))
         return None if entry[2] else mask
 
-    def trainForOneIteration(self, viewpoint_cam, gt_image, mask, sync_loss=True, position_lr_step=None):
+    def trainForOneIteration(self, viewpoint_cam, gt_image, mask, sync_loss=True, position_lr_step=None, gt_depth=None):
         """position_lr_step: the step of the position learning-rate schedule -- None = the iteration (src/gaussian_mapper.cpp:672-674,
-        the COLMAP flavour); a SLAM session passes the keyframe's use count (:663-671, capped at position_lr_max_steps_)."""
+        the COLMAP flavour); a SLAM session passes the keyframe's use count (:663-671, capped at position_lr_max_steps_).
+        gt_depth: the keyframe's [H,W] sensor depth (an RGB-D session's img_auxiliary_undist_); with depth_loss_weight_ != 0 the
+        depth L1 loss joins the RGB loss before the one backward pass (its gradient reaches the positions through the depth map)."""
+        use_depth = gt_depth is not None and self.depth_loss_weight_ != 0.0
+        if use_depth and self.world_size_ > 1:
+            raise RuntimeError("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)")
         g, opt = self.gaussians_, self.opt_
         self.iteration_ += 1
         it = self.iteration_
@@ -314,15 +329,19 @@ class TrainStep:
         fwd_adam = sh_adam if sh_adam is not None else sh_adam_views
         g._in_lazy_step = fwd_adam is not None and fwd_adam.get("row_step") is not None
         try:
-            rendered_image, viewspace_point_tensor, visibility_filter, radii = GaussianRenderer.render(
+            out = GaussianRenderer.render(
                 viewpoint_cam, viewpoint_cam.image_height_, viewpoint_cam.image_width_, g, self.pipe_, self.background_,
                 sh_grad_view=sh_view, sh_adam=fwd_adam, view_stats=view_stats, geom_adam=geom_adam,
                 training_outputs_only=True,   # the statistics are fused (or over): nobody reads the viewspace gradient
-                cull_empty_tiles=self.cull_empty_tiles_, workspace=self.workspace_ if self.persistent_workspace_ else None)
+                cull_empty_tiles=self.cull_empty_tiles_, workspace=self.workspace_ if self.persistent_workspace_ else None,
+                render_depth=use_depth)
+            rendered_image, viewspace_point_tensor, visibility_filter, radii = out[:4]
         finally:
             g._in_lazy_step = False
         # :692-698  masked L1 + lambda * (1 - SSIM), fused with its gradient (csrc/train_ops.hip)
         loss = loss_utils.fused_l1_ssim_loss(rendered_image, gt_image, self._effective_mask(mask), opt.lambda_dssim_, is_root=True)
+        if use_depth:   # (the sum's backward hands both terms the root's exact 1: is_root stays valid)
+            loss = loss + loss_utils.depth_l1_loss(out[4], gt_depth, self.depth_loss_weight_, self.depth_min_, self.depth_max_)
         # :699 (the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward())
         if getattr(self, "_root_grad", None) is None or self._root_grad.device != loss.device:
             self._root_grad = torch.ones_like(loss).detach()
