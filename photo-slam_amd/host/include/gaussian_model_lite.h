@@ -7,8 +7,6 @@
 #include <torch/torch.h>
 #include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
 
-#include "rasterize_points.h"   // RasterWorkspace
-
 #include <array>
 #include <cmath>
 #include <limits>
@@ -19,7 +17,7 @@
 #include <tuple>
 #include <vector>
 
-#include "rasterize_points.h"   // ShAdamStep
+#include "gaussian_rasterizer.h"   // GaussianRasterizationExtensions; rasterize_points.h: ShAdamStep, RasterWorkspace
 
 struct GaussianOptimizationParams {  // include/gaussian_parameters.h:61-96 defaults
 	int iterations_ = 30000;
@@ -133,6 +131,13 @@ public:
 	// or rewrites features_ or its moments outside the fused train step calls it first (getFeatures(), params(), the dense
 	// optimizer step, densify / prune, savePly, the data-parallel exchange).
 	void syncFeatures();
+	// The Adam state of the SH tensor (groups_[1], the learning rates scaled by lr_scale_) as the ShAdamStep the rasterizer and
+	// the shAdam* functions take (rasterize_points.h); step = the group's counter in every form:
+	//   Eager      the step the counter names, every row
+	//   Lazy       the same step with the lazy rows' state (row_step, window, the history of the earlier steps' rates)
+	//   LazyTaken  the counter's step has been taken: its rates are the newest entry of the history (what shAdamFlush wants)
+	enum class ShStep { Eager, Lazy, LazyTaken };
+	ShAdamStep featuresAdamStep(ShStep which) const;
 	torch::Tensor features_row_step_;                            // [P] int32 or undefined (= every row is up to date)
 	std::vector<std::pair<double, double>> features_lr_hist_;    // (lr, lr_tail) of the Adam steps since the state exists, newest first
 	int features_lazy_window_ = 0;
@@ -311,6 +316,7 @@ public:
 	// ... with the depth and alpha maps: (image, depth, alpha), [H,W] each (GaussianRenderer::renderWithDepth)
 	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf);
 	RasterWorkspace view_workspace_;
+	GaussianRasterizationExtensions viewExtensions();   // what the two calls above hand to GaussianRenderer
 	bool early_gather_ = true;        // the exchange's all-gather waits for the colour gradients only, not for the whole backward pass
 	// The view-factored exchange in its PACKED form (include/gsr.h: gsr_pack_color_view): every rank sends only the rows its
 	// view sees -- 11.7 MB instead of 24 MB per rank and link at 2 M Gaussians.  The ranks agree on the message capacity by

@@ -84,6 +84,14 @@ struct GaussianRasterizationExtensions {
 	// optimizer-in-backward for xyz / opacity / scaling / rotation (rasterize_points.h): fill param to enable; those four then
 	// get no gradient from autograd
 	GeomAdamStep geom_adam_;
+	// dL_dmeans2D and dL_dcov3D are not written either (means2D and cov3Ds_precomp get no gradient) -- for a caller that fuses
+	// the densification statistics (view_stats_)
+	bool training_outputs_only_ = false;
+	// with sh_grad_view_ only (rasterize_points.h: RasterBackwardExtensions): the hipStream_t that waits for the point inside
+	// backward at which sh_grad_view_ is complete, and the packed message backward writes next to it
+	void* color_view_ready_stream_ = nullptr;
+	torch::Tensor packed_view_;
+	int64_t packed_capacity_ = 0;
 	// GSR_CULL_EMPTY_TILES (include/gsr.h): instances of tiles in which no pixel can blend the Gaussian are dropped in front of
 	// the tile sort -- the same image and the same gradients from shorter internal lists
 	bool cull_empty_tiles_ = false;

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <memory>
+#include <stdexcept>
 #include <tuple>
 
 #include "gaussian_rasterizer.h"
@@ -41,18 +42,11 @@ auto lazy_view(Model& m, ShAdamStep& s, torch::Tensor& shs, int)
     -> decltype((void)m.features_row_step_, (void)m.features_lr_hist_, (void)m.in_lazy_step_, (void)m.groups_, bool())
 {
 	if (!m.features_row_step_.defined() || m.groups_.size() < 2) return false;
-	const auto& grp = m.groups_[1];
-	s = ShAdamStep();
-	s.exp_avg = grp.exp_avg;
-	s.exp_avg_sq = grp.exp_avg_sq;
-	s.step = grp.step + 1;
-	s.lr = m.features_lr_hist_.empty() ? grp.lr * m.lr_scale_ : m.features_lr_hist_[0].first;
-	s.lr_tail = m.features_lr_hist_.empty() ? grp.lr_tail * m.lr_scale_ : m.features_lr_hist_[0].second;
-	s.row_step = m.features_row_step_;
-	s.window = m.features_lazy_window_;
-	for (const auto& h : m.features_lr_hist_) {
-		s.lr_past.push_back(h.first);
-		s.lr_tail_past.push_back(h.second);
+	s = m.featuresAdamStep(Model::ShStep::Lazy);
+	s.step++;   // (the counter names the last step taken; the next one is only described, not taken: its rates = lr_past[0])
+	if (!m.features_lr_hist_.empty()) {
+		s.lr = m.features_lr_hist_[0].first;
+		s.lr_tail = m.features_lr_hist_[0].second;
 	}
 	const bool was = m.in_lazy_step_;
 	m.in_lazy_step_ = true;
@@ -69,23 +63,21 @@ bool lazy_view(Model&, ShAdamStep&, torch::Tensor&, long)
 
 class GaussianRenderer {
 public:
-	// returns (render, viewspace_points, visibility_filter, radii)
+	// returns (render, viewspace_points, visibility_filter, radii).  The reference's parameters, then this repository's
+	// extensions as ONE struct (gaussian_rasterizer.h; the default = the reference's data flow).  What the pipeline flags rule
+	// out is masked here: with compute_cov3D_ the rasterizer sees a covariance, not the raw leaves (raw_params_ and geom_adam_
+	// are cleared), with convert_SHs_ or override colours it sees no SH tensor (sh_grad_view_ and sh_adam_ are cleared).
+	// raw_params_ == 7 hands the raw opacity_/scaling_/rotation_ leaves to the rasterizer, which applies sigmoid / exp /
+	// normalize and their chain rule in-kernel (include/gsr.h raw_params); render_depth_ is renderWithDepth's to set.
 	template <class Keyframe, class Model>
 	static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> render(
 	    std::shared_ptr<Keyframe> viewpoint_camera, int image_height, int image_width, std::shared_ptr<Model> pc,
 	    GaussianPipelineParams& pipe, torch::Tensor& bg_color, torch::Tensor& override_color,
-	    float scaling_modifier = 1.0f, bool use_override_color = false, bool fuse_activations = false,
-	    torch::Tensor sh_grad_view = torch::Tensor() /* extension: GaussianRasterizationExtensions::sh_grad_view_ */,
-	    ShAdamStep sh_adam = ShAdamStep() /* extension: GaussianRasterizationExtensions::sh_adam_ */,
-	    std::vector<torch::Tensor> view_stats = {} /* extension: GaussianRasterizationExtensions::view_stats_ */,
-	    GeomAdamStep geom_adam = GeomAdamStep() /* extension: GaussianRasterizationExtensions::geom_adam_ */,
-	    bool cull_empty_tiles = false /* extension: GaussianRasterizationExtensions::cull_empty_tiles_ */,
-	    RasterWorkspace* workspace = nullptr /* extension: GaussianRasterizationExtensions::workspace_ */,
-	    bool forward_only = false /* extension: GaussianRasterizationExtensions::forward_only_ (implied when grad mode is off) */)
+	    float scaling_modifier = 1.0f, bool use_override_color = false,
+	    const GaussianRasterizationExtensions& extensions = GaussianRasterizationExtensions())
 	{
 		auto r = render_impl(false, viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color, scaling_modifier,
-		                     use_override_color, fuse_activations, sh_grad_view, sh_adam, view_stats, geom_adam, cull_empty_tiles,
-		                     workspace, forward_only);
+		                     use_override_color, extensions);
 		return std::make_tuple(std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r));
 	}
 
@@ -96,18 +88,11 @@ public:
 	static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> renderWithDepth(
 	    std::shared_ptr<Keyframe> viewpoint_camera, int image_height, int image_width, std::shared_ptr<Model> pc,
 	    GaussianPipelineParams& pipe, torch::Tensor& bg_color, torch::Tensor& override_color,
-	    float scaling_modifier = 1.0f, bool use_override_color = false, bool fuse_activations = false,
-	    torch::Tensor sh_grad_view = torch::Tensor() /* extension: GaussianRasterizationExtensions::sh_grad_view_ */,
-	    ShAdamStep sh_adam = ShAdamStep() /* extension: GaussianRasterizationExtensions::sh_adam_ */,
-	    std::vector<torch::Tensor> view_stats = {} /* extension: GaussianRasterizationExtensions::view_stats_ */,
-	    GeomAdamStep geom_adam = GeomAdamStep() /* extension: GaussianRasterizationExtensions::geom_adam_ */,
-	    bool cull_empty_tiles = false /* extension: GaussianRasterizationExtensions::cull_empty_tiles_ */,
-	    RasterWorkspace* workspace = nullptr /* extension: GaussianRasterizationExtensions::workspace_ */,
-	    bool forward_only = false /* extension: GaussianRasterizationExtensions::forward_only_ (implied when grad mode is off) */)
+	    float scaling_modifier = 1.0f, bool use_override_color = false,
+	    const GaussianRasterizationExtensions& extensions = GaussianRasterizationExtensions())
 	{
 		return render_impl(true, viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color, scaling_modifier,
-		                   use_override_color, fuse_activations, sh_grad_view, sh_adam, view_stats, geom_adam, cull_empty_tiles,
-		                   workspace, forward_only);
+		                   use_override_color, extensions);
 	}
 
 private:
@@ -116,26 +101,23 @@ private:
 	static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> render_impl(
 	    bool with_depth, std::shared_ptr<Keyframe> viewpoint_camera, int image_height, int image_width, std::shared_ptr<Model> pc,
 	    GaussianPipelineParams& pipe, torch::Tensor& bg_color, torch::Tensor& override_color, float scaling_modifier,
-	    bool use_override_color, bool fuse_activations, torch::Tensor sh_grad_view, ShAdamStep sh_adam,
-	    std::vector<torch::Tensor> view_stats, GeomAdamStep geom_adam, bool cull_empty_tiles, RasterWorkspace* workspace,
-	    bool forward_only)
+	    bool use_override_color, const GaussianRasterizationExtensions& extensions)
 	{
-		// forward_only (extension): no backward pass follows (a viewer's or an evaluation render) -- the rasterizer prepares
+		GaussianRasterizationExtensions ext = extensions;   // (the rasterizer's: masked below)
+		// forward_only_: no backward pass follows (a viewer's or an evaluation render) -- the rasterizer prepares
 		// nothing for one (GSR_FORWARD_ONLY), screenspace_points is a plain tensor, and on a model whose SH rows are stepped lazily
 		// the rows are read as they are and caught up in registers only: the model is neither flushed nor changed
-		forward_only = forward_only || !torch::GradMode::is_enabled();
-		// fuse_activations (extension): hand the raw opacity_/scaling_/rotation_ leaves to the rasterizer, which applies
-		// sigmoid / exp / normalize and their chain rule in-kernel (include/gsr.h raw_params)
+		ext.forward_only_ = ext.forward_only_ || !torch::GradMode::is_enabled();
 		// dummy input whose gradient is dL/dmean2D (the densification statistic)
-		// (with geom_adam.training_outputs_only nobody reads its gradient and the rasterizer never reads its values: the 12 P
+		// (with training_outputs_only_ nobody reads its gradient and the rasterizer never reads its values: the 12 P
 		// bytes are then not even zero-filled)
+		const bool training_outputs_only = extensions.training_outputs_only_;
 		torch::Tensor screenspace_points;
-		if (forward_only) {
+		if (ext.forward_only_) {
 			screenspace_points = torch::zeros_like(pc->getXYZ(), torch::TensorOptions().requires_grad(false));
 		} else {
-			screenspace_points = geom_adam.training_outputs_only
-			                         ? torch::empty_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true))
-			                         : torch::zeros_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true));
+			screenspace_points = training_outputs_only ? torch::empty_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true))
+			                                           : torch::zeros_like(pc->getXYZ(), torch::TensorOptions().requires_grad(true));
 			screenspace_points.retain_grad();
 		}
 
@@ -145,28 +127,29 @@ private:
 		                                              scaling_modifier, viewpoint_camera->world_view_transform_,
 		                                              viewpoint_camera->full_proj_transform_, pc->active_sh_degree_,
 		                                              viewpoint_camera->camera_center_, false);
+		if (ext.raw_params_ != 0 && ext.raw_params_ != 7)
+			throw std::runtime_error("GaussianRenderer::render: raw_params_ must be 0 (activations in torch) or 7 (all three in the rasterizer)");
+		if (pipe.compute_cov3D_) ext.raw_params_ = 0;
+		ext.render_depth_ = with_depth;
 		// SH evaluated in torch (convert_SHs_) or colours given: the rasterizer sees no SH tensor, so the SH extensions are off
 		const bool sh_in_rasterizer = !use_override_color && !pipe.convert_SHs_;
-		GaussianRasterizationExtensions ext;
-		ext.raw_params_ = (fuse_activations && !pipe.compute_cov3D_) ? 7 : 0;
-		if (sh_in_rasterizer) ext.sh_grad_view_ = sh_grad_view;
-		if (sh_in_rasterizer) ext.sh_adam_ = sh_adam;
-		ext.view_stats_ = view_stats;
-		ext.workspace_ = workspace;
-		ext.forward_only_ = forward_only;
+		if (!sh_in_rasterizer) {
+			ext.sh_grad_view_ = torch::Tensor();
+			ext.sh_adam_ = ShAdamStep();
+		}
 		torch::Tensor lazy_shs;
 		bool lazy_rows = false;
-		if (forward_only && sh_in_rasterizer && !sh_adam.row_step.defined()) {
-			ShAdamStep view_adam;
-			lazy_rows = gsr_renderer_detail::lazy_view(*pc, view_adam, lazy_shs, 0);
-			if (lazy_rows) ext.sh_adam_ = view_adam;
-		}
+		if (ext.forward_only_ && sh_in_rasterizer && !ext.sh_adam_.row_step.defined())
+			lazy_rows = gsr_renderer_detail::lazy_view(*pc, ext.sh_adam_, lazy_shs, 0);
 		// (the same image and gradients either way; off by default: measured a wash, DESIGN.md section 10.  The caller's
-		// argument decides; the environment variable GSR_CULL_EMPTY_TILES=0/1, when set, overrides it -- an A/B handle)
+		// cull_empty_tiles_ decides; the environment variable GSR_CULL_EMPTY_TILES=0/1, when set, overrides it -- an A/B handle)
 		static const int cull_env = [] { const char* e = std::getenv("GSR_CULL_EMPTY_TILES"); return (e && *e) ? (e[0] == '1' ? 1 : 0) : -1; }();
-		ext.cull_empty_tiles_ = cull_env >= 0 ? cull_env != 0 : cull_empty_tiles;
+		if (cull_env >= 0) ext.cull_empty_tiles_ = cull_env != 0;
 		// the fused geometry step needs the raw leaves in the rasterizer (it steps opacity_ / scaling_ / rotation_ themselves)
-		if (ext.raw_params_ == 7 && !pipe.compute_cov3D_) ext.geom_adam_ = geom_adam;
+		if (ext.raw_params_ != 7) {
+			ext.geom_adam_ = GeomAdamStep();
+			ext.training_outputs_only_ = false;
+		}
 		GaussianRasterizerEx rasterizer(raster_settings, ext);
 
 		auto means3D = pc->getXYZ();
@@ -210,8 +193,8 @@ private:
 			                       has_cov3D_precomp, shs, colors_precomp, scales, rotations, cov3D_precomp);
 		}
 		// (visibility_filter = radii > 0 is one more launch: a caller that fused everything that consumes it -- the statistics,
-		// geom_adam.training_outputs_only -- gets an undefined tensor and derives it from radii if it ever wants it)
-		return std::make_tuple(rendered_image, screenspace_points,
-		                       geom_adam.training_outputs_only ? torch::Tensor() : (radii > 0), radii, depth, alpha);
+		// training_outputs_only_ -- gets an undefined tensor and derives it from radii if it ever wants it)
+		return std::make_tuple(rendered_image, screenspace_points, training_outputs_only ? torch::Tensor() : (radii > 0), radii, depth,
+		                       alpha);
 	}
 };

@@ -1,8 +1,9 @@
 // rasterize_points.h -- LibTorch boundary of the MI355X rasterizer.  RasterizeGaussiansCUDA, RasterizeGaussiansBackwardCUDA and
 // markVisible are declared with EXACTLY the parameter lists of the reference's include/rasterize_points.h:18-65: the
 // same mangled symbols, so an object compiled against the reference header links against libphotoslam_host.so
-// (tests/test_reference_link.py does that).  The extensions of this repository are separate OVERLOADS with extra
-// parameters (only the last one, the workspace of the longest overload, has a default).  On a ROCm build of LibTorch torch::kCUDA *is* the HIP device.
+// (tests/test_reference_link.py does that).  The extensions of this repository are ONE more overload per direction: the
+// reference's parameter list plus a struct (RasterForwardExtensions / RasterBackwardExtensions) whose default-constructed
+// value is the reference contract.  On a ROCm build of LibTorch torch::kCUDA *is* the HIP device.
 // Implementation: src/rasterize_points.cpp on top of the C-ABI in include/gsr.h (libgsr_hip.so).
 #pragma once
 #include <torch/torch.h>
@@ -13,7 +14,7 @@
 // Extension, optimizer-in-backward for the SH tensor (gsr_sh_adam of include/gsr.h): when exp_avg is defined, backward applies
 // this Adam step to `sh` IN PLACE instead of computing dL_dsh (which then comes back undefined).
 // Lazy mode (gsr_sh_adam_lazy): with row_step defined the rows of culled Gaussians take their zero-gradient steps later,
-// several at a time -- the SAME struct then goes to the forward overload below (rows that become visible are brought up to
+// several at a time -- the SAME struct then goes to the forward pass (rows that become visible are brought up to
 // date before they are evaluated) and to backward, and shAdamFlush must run before anything else touches sh or the moments.
 struct ShAdamStep {
 	torch::Tensor exp_avg, exp_avg_sq;   // [P,16,3], contiguous
@@ -22,36 +23,22 @@ struct ShAdamStep {
 	torch::Tensor row_step;              // lazy mode: [P] int32, the Adam steps each row has taken; undefined = eager
 	int window = 0;                      // lazy mode: 2 .. GSR_SH_LAZY_WINDOW
 	std::vector<double> lr_past, lr_tail_past;   // lazy mode: [k-1] = the learning rates of step (step - k)
-	// view-factored mode only (gsr_backward_args.color_view_ready_stream; consulted by backward, with or without the fields
-	// above): a hipStream_t that is made to wait for the point inside backward at which dL_dcolor_view is complete -- the
-	// exchange issues its all-gather there and overlaps the last kernel of the pass
-	void* color_view_ready_stream = nullptr;
-	// view-factored mode, packed exchange (gsr_backward_args.packed_view): an int32 message whose mask / prefix sections
-	// packViewPlan() fills between the forward and the backward pass; backward writes rows and header next to dL_dcolor_view
-	torch::Tensor packed_view;
-	int64_t packed_capacity = 0;
 	// scheduling of the optimizer work the library forks next to its own kernels (gsr_sh_adam: zero = the measured-best
 	// arrangement; the environment variables GSR_SH_ADAM_SIDE_STREAM / GSR_LAZY_SLICE_EARLY / GSR_SH_ADAM_SIDE_BLOCKS override)
 	bool no_side_stream = false, lazy_slice_late = false;
 	int side_blocks = 0;
 };
 
-// (num_rendered, out_color[3,H,W], radii[P] i32, geomBuffer u8, binningBuffer u8, imgBuffer u8)
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
-    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
-    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
-    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
-    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
-    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
-    const bool prefiltered);
-// overload with the extension parameter raw_params: GSR_RAW_* mask, see include/gsr.h
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
-    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
-    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
-    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
-    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
-    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
-    const bool prefiltered, const int raw_params);
+// Extension, optimizer-in-backward for xyz / opacity / scaling / rotation (gsr_geom_adam of include/gsr.h): when param is
+// filled (four entries each, in that order), backward applies this Adam step to the four tensors IN PLACE instead of computing
+// their gradients (which then come back undefined).  Needs raw_params == 7 and scales / rotations (no cov3D_precomp).
+struct GeomAdamStep {
+	std::vector<torch::Tensor> param, exp_avg, exp_avg_sq;   // xyz [P,3], opacity [P,1], scaling [P,3], rotation [P,4]
+	std::vector<double> lr;
+	std::vector<int64_t> step;
+	double beta1 = 0.9, beta2 = 0.999, eps = 1e-15;
+};
+
 // Persistent scratch for a caller that renders iteration after iteration (TrainStep): the three byte buffers of the rasterizer
 // (the reference allocates them per call, src/rasterize_points.cu:71-76, and returns them).  They grow with 50 % headroom and
 // never shrink.  The binning buffer's size follows the instance count, which changes with every step of a training run: per-call
@@ -62,38 +49,59 @@ struct RasterWorkspace {
 	torch::Tensor geom, binning, img;
 };
 
-// ... and the lazy SH Adam state (only consulted when sh_adam.row_step is defined; `sh` is then updated in place); workspace:
-// nullptr = fresh buffers per call, as the reference
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
-    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
-    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
-    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
-    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
-    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
-    const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace = nullptr);
-// ... with the depth and alpha maps (gsr_forward_args.out_depth / out_alpha): caller-allocated contiguous float32 [H,W] tensors on
-// the device of means3D, written for every pixel; undefined = not rendered.  depth = sum z alpha T, alpha = 1 - T_final.
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
-    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
-    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
-    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
-    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
-    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
-    const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace,
-    const torch::Tensor& out_depth, const torch::Tensor& out_alpha);
-
-// Extension, optimizer-in-backward for xyz / opacity / scaling / rotation (gsr_geom_adam of include/gsr.h): when param is
-// filled (four entries each, in that order), backward applies this Adam step to the four tensors IN PLACE instead of computing
-// their gradients (which then come back undefined).  Needs raw_params == 7 and scales / rotations (no cov3D_precomp).
-// training_outputs_only: dL_dmeans2D and dL_dcov3D are not written either (undefined) -- for a caller that fuses the
-// densification statistics (view_stats).
-struct GeomAdamStep {
-	std::vector<torch::Tensor> param, exp_avg, exp_avg_sq;   // xyz [P,3], opacity [P,1], scaling [P,3], rotation [P,4]
-	std::vector<double> lr;
-	std::vector<int64_t> step;
-	double beta1 = 0.9, beta2 = 0.999, eps = 1e-15;
-	bool training_outputs_only = false;
+// What this repository adds to the reference's forward parameter list.  The pointers are read during the call only.
+struct RasterForwardExtensions {
+	int raw_params = 0;   // GSR_RAW_* mask, see include/gsr.h
+	// the lazy SH Adam state (only consulted when its row_step is defined; `sh` is then updated in place)
+	const ShAdamStep* sh_adam = nullptr;
+	RasterWorkspace* workspace = nullptr;   // nullptr = fresh buffers per call, as the reference
+	// the depth and alpha maps (gsr_forward_args.out_depth / out_alpha): caller-allocated contiguous float32 [H,W] tensors on
+	// the device of means3D, written for every pixel; undefined = not rendered.  depth = sum z alpha T, alpha = 1 - T_final.
+	torch::Tensor out_depth, out_alpha;
 };
+
+// ... and to the reference's backward parameter list
+struct RasterBackwardExtensions {
+	int raw_params = 0;
+	// a [P,3] float tensor that receives the clamp-masked colour gradient; dL_dsh is then NOT computed and comes back undefined
+	// (gsr_backward_args.dL_dcolor_view); undefined = off
+	torch::Tensor dL_dcolor_view;
+	const ShAdamStep* sh_adam = nullptr;   // nullptr or exp_avg undefined = off
+	// {xyz_gradient_accum, denom, max_radii2D} (P floats each), updated in place with this view's densification statistics
+	// (gsr_backward_args.stat_*); nullptr or empty = off
+	const std::vector<torch::Tensor>* view_stats = nullptr;
+	const GeomAdamStep* geom_adam = nullptr;   // nullptr or param empty = off
+	// dL_dmeans2D and dL_dcov3D are not written (undefined) -- for a caller that fuses the densification statistics (view_stats)
+	bool training_outputs_only = false;
+	// the upstream gradients of the depth and alpha maps (gsr_backward_args.dL_ddepth / dL_dalpha): [H,W] each, either
+	// undefined (zeros); the forward pass need not have rendered the maps
+	torch::Tensor dL_ddepth, dL_dalpha;
+	// view-factored mode only (gsr_backward_args.color_view_ready_stream): a hipStream_t that is made to wait for the point
+	// inside backward at which dL_dcolor_view is complete -- the exchange issues its all-gather there and overlaps the last
+	// kernel of the pass
+	void* color_view_ready_stream = nullptr;
+	// view-factored mode, packed exchange (gsr_backward_args.packed_view): an int32 message whose mask / prefix sections
+	// packViewPlan() fills between the forward and the backward pass; backward writes rows and header next to dL_dcolor_view
+	torch::Tensor packed_view;
+	int64_t packed_capacity = 0;
+};
+
+// (num_rendered, out_color[3,H,W], radii[P] i32, geomBuffer u8, binningBuffer u8, imgBuffer u8)
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
+    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
+    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
+    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
+    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+    const bool prefiltered);
+// ... with the extensions
+std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
+    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
+    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
+    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
+    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+    const bool prefiltered, const RasterForwardExtensions& ext);
 
 // (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
@@ -105,7 +113,7 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
                                const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
                                const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
                                const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer);
-// overload with the extension parameters (all four, no defaults)
+// ... with the extensions
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
            torch::Tensor>
 RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
@@ -115,40 +123,7 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
                                const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
                                const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
                                const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                               const int raw_params,
-                               /* a [P,3] float tensor that receives the clamp-masked colour gradient; dL_dsh is then NOT
-                                  computed and comes back undefined (gsr_backward_args.dL_dcolor_view); undefined = off */
-                               const torch::Tensor& dL_dcolor_view,
-                               const ShAdamStep& sh_adam,
-                               /* {xyz_gradient_accum, denom, max_radii2D} (P floats each), updated in place with this
-                                  view's densification statistics (gsr_backward_args.stat_*); empty = off */
-                               const std::vector<torch::Tensor>& view_stats);
-// ... and the fused geometry step (GeomAdamStep above)
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-           torch::Tensor>
-RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
-                               const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
-                               const float scale_modifier, const torch::Tensor& cov3D_precomp,
-                               const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx,
-                               const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
-                               const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
-                               const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                               const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
-                               const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam);
-// ... with the upstream gradients of the depth and alpha maps (gsr_backward_args.dL_ddepth / dL_dalpha): [H,W] each, either
-// undefined (zeros); the forward pass need not have rendered the maps
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-           torch::Tensor>
-RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
-                               const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
-                               const float scale_modifier, const torch::Tensor& cov3D_precomp,
-                               const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx,
-                               const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
-                               const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
-                               const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                               const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
-                               const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam,
-                               const torch::Tensor& dL_ddepth, const torch::Tensor& dL_dalpha);
+                               const RasterBackwardExtensions& ext);
 
 // gsr_sh_grad_from_views (include/gsr.h): the [P,M,3] SH gradient of a keyframe batch from the gathered
 // [n_views,P,3] dL_dcolor_view tensors and the [n_views,3] camera centres; scale = 1/n_views for the batch mean
@@ -172,7 +147,7 @@ void checkPackedViews(const torch::Tensor& messages, int64_t msg_stride, int64_t
 void packColorView(const torch::Tensor& dL_dcolor_view, const torch::Tensor& campos, int64_t capacity, torch::Tensor& message,
                    torch::Tensor& scratch);
 // gsr_pack_view_plan: the mask and prefix sections of a view's message from the forward pass's radii (CURRENT stream); the
-// backward pass writes rows and header itself when ShAdamStep::packed_view names the message
+// backward pass writes rows and header itself when RasterBackwardExtensions::packed_view names the message
 void packViewPlan(const torch::Tensor& radii, int64_t capacity, torch::Tensor& message, torch::Tensor& scratch);
 torch::Tensor shGradFromPackedViews(const torch::Tensor& means3D, const torch::Tensor& messages, int64_t msg_stride, int64_t n_views,
                                     const int degree, const int M, const float scale);

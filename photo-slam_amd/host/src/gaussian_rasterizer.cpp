@@ -14,60 +14,55 @@ torch::Tensor GaussianRasterizer::markVisibleGaussians(torch::Tensor& positions)
 
 namespace {
 
-// shared by GaussianRasterizerFunction (the reference's contract: no extensions) and GaussianRasterizerFunctionEx
+// What backward needs besides the saved tensors: the settings and the extensions of the call, kept whole
+// (ctx->saved_data["state"]) -- backward_impl reads whatever field it wants, no field is packed or unpacked by name
+struct SavedState : torch::CustomClassHolder {
+	SavedState(GaussianRasterizationSettings&& s, GaussianRasterizationExtensions&& e) : settings(std::move(s)), extensions(std::move(e)) {}
+	GaussianRasterizationSettings settings;
+	GaussianRasterizationExtensions extensions;
+	int num_rendered = 0;
+};
+
+// RasterizeGaussiansCUDA as both paths below call it.  more_raw_params: GSR_FORWARD_ONLY or 0; depth / alpha: defined = the
+// maps are rendered into them (render_depth_).  Only the lazy form of sh_adam_ concerns a forward pass (visible rows are
+// brought up to date first; forward-only: read at their caught-up values, not written) -- RasterizeGaussiansCUDA looks at no other.
+auto rasterize_forward(const torch::Tensor& means3D, const torch::Tensor& sh, const torch::Tensor& colors_precomp,
+                       const torch::Tensor& opacities, const torch::Tensor& scales, const torch::Tensor& rotations,
+                       const torch::Tensor& cov3Ds_precomp, const GaussianRasterizationSettings& s,
+                       const GaussianRasterizationExtensions& e, int more_raw_params, const torch::Tensor& depth,
+                       const torch::Tensor& alpha)
+{
+	RasterForwardExtensions f;
+	f.raw_params = e.raw_params_ | (e.cull_empty_tiles_ ? GSR_CULL_EMPTY_TILES : 0) | more_raw_params;
+	f.sh_adam = &e.sh_adam_;
+	f.workspace = e.workspace_;
+	f.out_depth = depth;
+	f.out_alpha = alpha;
+	return RasterizeGaussiansCUDA(s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
+	                              s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh,
+	                              s.sh_degree_, s.campos_, s.prefiltered_, f);
+}
+
+// shared by GaussianRasterizerFunction (the reference's contract: no extensions) and GaussianRasterizerFunctionEx; the node
+// takes the two structs over (moved, not copied again)
 torch::autograd::tensor_list forward_impl(torch::autograd::AutogradContext* ctx, torch::Tensor means3D, torch::Tensor sh,
                                           torch::Tensor colors_precomp, torch::Tensor opacities, torch::Tensor scales,
                                           torch::Tensor rotations, torch::Tensor cov3Ds_precomp,
-                                          const GaussianRasterizationSettings& s, const GaussianRasterizationExtensions& e)
+                                          GaussianRasterizationSettings&& settings, GaussianRasterizationExtensions&& extensions)
 {
+	auto state = c10::make_intrusive<SavedState>(std::move(settings), std::move(extensions));
+	const GaussianRasterizationSettings& s = state->settings;
+	const GaussianRasterizationExtensions& e = state->extensions;
 	torch::Tensor depth, alpha;   // (render_depth_: the two maps, written for every pixel)
 	if (e.render_depth_) {
 		depth = torch::zeros({s.image_height_, s.image_width_}, means3D.options().dtype(torch::kFloat32));
 		alpha = torch::zeros({s.image_height_, s.image_width_}, means3D.options().dtype(torch::kFloat32));
 	}
-	auto r = RasterizeGaussiansCUDA(s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_,
-	                                cov3Ds_precomp, s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_,
-	                                s.image_height_, s.image_width_, sh, s.sh_degree_, s.campos_, s.prefiltered_,
-	                                e.raw_params_ | (e.cull_empty_tiles_ ? 8 /* GSR_CULL_EMPTY_TILES, include/gsr.h */ : 0),
-	                                e.sh_adam_ /* lazy mode: visible rows are brought up to date first */, e.workspace_, depth, alpha);
+	auto r = rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, e, 0, depth, alpha);
+	state->num_rendered = std::get<0>(r);
 	// (no zero tensor for the unused gradient of `radii`: autograd would otherwise fill P ints per backward)
 	ctx->set_materialize_grads(false);
-	ctx->saved_data["num_rendered"] = std::get<0>(r);
-	ctx->saved_data["scale_modifier"] = static_cast<double>(s.scale_modifier_);
-	ctx->saved_data["tanfovx"] = static_cast<double>(s.tanfovx_);
-	ctx->saved_data["tanfovy"] = static_cast<double>(s.tanfovy_);
-	ctx->saved_data["sh_degree"] = s.sh_degree_;
-	ctx->saved_data["raw_params"] = e.raw_params_;
-	if (e.render_depth_) ctx->saved_data["image_hw"] = std::vector<int64_t>{s.image_height_, s.image_width_};
-	if (e.sh_grad_view_.defined()) ctx->saved_data["sh_grad_view"] = e.sh_grad_view_;
-	if (e.sh_adam_.color_view_ready_stream)
-		ctx->saved_data["color_view_ready_stream"] = static_cast<int64_t>(reinterpret_cast<intptr_t>(e.sh_adam_.color_view_ready_stream));
-	if (e.sh_adam_.packed_view.defined()) {
-		ctx->saved_data["packed_view"] = e.sh_adam_.packed_view;
-		ctx->saved_data["packed_capacity"] = e.sh_adam_.packed_capacity;
-	}
-	if (!e.view_stats_.empty()) ctx->saved_data["view_stats"] = e.view_stats_;
-	if (e.sh_adam_.exp_avg.defined()) {
-		ctx->saved_data["sh_adam_m"] = e.sh_adam_.exp_avg;
-		ctx->saved_data["sh_adam_v"] = e.sh_adam_.exp_avg_sq;
-		ctx->saved_data["sh_adam_h"] = std::vector<double>{e.sh_adam_.lr, e.sh_adam_.lr_tail, e.sh_adam_.beta1, e.sh_adam_.beta2,
-		                                                   e.sh_adam_.eps, static_cast<double>(e.sh_adam_.step)};
-		if (e.sh_adam_.row_step.defined()) {   // lazy mode
-			ctx->saved_data["sh_adam_row_step"] = e.sh_adam_.row_step;
-			ctx->saved_data["sh_adam_window"] = e.sh_adam_.window;
-			ctx->saved_data["sh_adam_lr_past"] = e.sh_adam_.lr_past;
-			ctx->saved_data["sh_adam_lr_tail_past"] = e.sh_adam_.lr_tail_past;
-		}
-	}
-	if (!e.geom_adam_.param.empty() || e.geom_adam_.training_outputs_only) {
-		const auto& ga = e.geom_adam_;
-		ctx->saved_data["geom_adam_p"] = ga.param;
-		ctx->saved_data["geom_adam_m"] = ga.exp_avg;
-		ctx->saved_data["geom_adam_v"] = ga.exp_avg_sq;
-		ctx->saved_data["geom_adam_lr"] = ga.lr;
-		ctx->saved_data["geom_adam_step"] = ga.step;
-		ctx->saved_data["geom_adam_h"] = std::vector<double>{ga.beta1, ga.beta2, ga.eps, ga.training_outputs_only ? 1.0 : 0.0};
-	}
+	ctx->saved_data["state"] = c10::IValue::make_capsule(state);
 	auto color = std::get<1>(r);
 	auto radii = std::get<2>(r);
 	// same 14 tensors, same order as the reference (src/gaussian_rasterizer.cpp:87-100)
@@ -90,70 +85,37 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 		torch::autograd::tensor_list none(static_cast<size_t>(8 + n_extra));
 		return none;
 	}
+	const auto state = c10::static_intrusive_pointer_cast<SavedState>(ctx->saved_data["state"].toCapsule());
+	const GaussianRasterizationSettings& s = state->settings;
+	const GaussianRasterizationExtensions& e = state->extensions;
 	torch::Tensor dL_dcolor = grad_outputs[0];
-	if (!dL_dcolor.defined()) {   // (a loss on the maps alone: the colour gradient is zeros)
-		const auto hw = ctx->saved_data["image_hw"].toIntVector();
-		dL_dcolor = torch::zeros({3, hw[0], hw[1]}, dL_ddepth.defined() ? dL_ddepth.options() : dL_dalpha.options());
-	}
+	if (!dL_dcolor.defined())   // (a loss on the maps alone: the colour gradient is zeros)
+		dL_dcolor = torch::zeros({3, s.image_height_, s.image_width_}, dL_ddepth.defined() ? dL_ddepth.options() : dL_dalpha.options());
 	auto map_grad = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
-	const int num_rendered = static_cast<int>(ctx->saved_data["num_rendered"].toInt());
-	const float scale_modifier = static_cast<float>(ctx->saved_data["scale_modifier"].toDouble());
-	const float tanfovx = static_cast<float>(ctx->saved_data["tanfovx"].toDouble());
-	const float tanfovy = static_cast<float>(ctx->saved_data["tanfovy"].toDouble());
-	const int sh_degree = static_cast<int>(ctx->saved_data["sh_degree"].toInt());
-	const int raw_params = static_cast<int>(ctx->saved_data["raw_params"].toInt());
-	torch::Tensor sh_grad_view;
-	if (ctx->saved_data.count("sh_grad_view")) sh_grad_view = ctx->saved_data["sh_grad_view"].toTensor();
-	ShAdamStep sh_adam;
-	if (ctx->saved_data.count("sh_adam_m")) {
-		sh_adam.exp_avg = ctx->saved_data["sh_adam_m"].toTensor();
-		sh_adam.exp_avg_sq = ctx->saved_data["sh_adam_v"].toTensor();
-		const auto h = ctx->saved_data["sh_adam_h"].toDoubleVector();
-		sh_adam.lr = h[0]; sh_adam.lr_tail = h[1];
-		sh_adam.beta1 = h[2]; sh_adam.beta2 = h[3];
-		sh_adam.eps = h[4]; sh_adam.step = static_cast<int>(h[5]);
-		if (ctx->saved_data.count("sh_adam_row_step")) {
-			sh_adam.row_step = ctx->saved_data["sh_adam_row_step"].toTensor();
-			sh_adam.window = static_cast<int>(ctx->saved_data["sh_adam_window"].toInt());
-			sh_adam.lr_past = ctx->saved_data["sh_adam_lr_past"].toDoubleVector();
-			sh_adam.lr_tail_past = ctx->saved_data["sh_adam_lr_tail_past"].toDoubleVector();
-		}
-	}
-	std::vector<torch::Tensor> view_stats;
-	if (ctx->saved_data.count("view_stats")) view_stats = ctx->saved_data["view_stats"].toTensorVector();
-	GeomAdamStep geom_adam;
-	if (ctx->saved_data.count("geom_adam_h")) {
-		geom_adam.param = ctx->saved_data["geom_adam_p"].toTensorVector();
-		geom_adam.exp_avg = ctx->saved_data["geom_adam_m"].toTensorVector();
-		geom_adam.exp_avg_sq = ctx->saved_data["geom_adam_v"].toTensorVector();
-		geom_adam.lr = ctx->saved_data["geom_adam_lr"].toDoubleVector();
-		geom_adam.step = ctx->saved_data["geom_adam_step"].toIntVector();
-		const auto h = ctx->saved_data["geom_adam_h"].toDoubleVector();
-		geom_adam.beta1 = h[0]; geom_adam.beta2 = h[1]; geom_adam.eps = h[2];
-		geom_adam.training_outputs_only = h[3] != 0.0;
-	}
-	ShAdamStep bwd_adam = (sh_grad_view.defined() && !sh_adam.row_step.defined()) ? ShAdamStep() : sh_adam;
-	if (ctx->saved_data.count("color_view_ready_stream"))
-		bwd_adam.color_view_ready_stream = reinterpret_cast<void*>(static_cast<intptr_t>(ctx->saved_data["color_view_ready_stream"].toInt()));
-	if (ctx->saved_data.count("packed_view")) {
-		bwd_adam.packed_view = ctx->saved_data["packed_view"].toTensor();
-		bwd_adam.packed_capacity = ctx->saved_data["packed_capacity"].toInt();
-	}
+	RasterBackwardExtensions b;
+	b.raw_params = e.raw_params_;
+	b.dL_dcolor_view = e.sh_grad_view_;
+	// view-factored mode: the SH step follows the exchange (gsr_sh_adam_from_views); sh_adam_ -- its lazy form only -- served
+	// the forward pass (rows this view sees caught up) and lets backward run this step's slice of the rotating catch-up
+	if (!e.sh_grad_view_.defined() || e.sh_adam_.row_step.defined()) b.sh_adam = &e.sh_adam_;
+	b.view_stats = &e.view_stats_;
+	b.geom_adam = &e.geom_adam_;
+	b.training_outputs_only = e.training_outputs_only_;
+	b.dL_ddepth = map_grad(dL_ddepth);
+	b.dL_dalpha = map_grad(dL_dalpha);
+	b.color_view_ready_stream = e.color_view_ready_stream_;
+	b.packed_view = e.packed_view_;
+	b.packed_capacity = e.packed_capacity_;
 	auto v = ctx->get_saved_variables();
 	auto g = RasterizeGaussiansBackwardCUDA(v[0] /*bg*/, v[5] /*means3D*/, v[9] /*radii*/, v[4] /*colors_precomp*/,
-	                                        v[6] /*scales*/, v[7] /*rotations*/, scale_modifier, v[8] /*cov3Ds*/,
-	                                        v[1] /*view*/, v[2] /*proj*/, tanfovx, tanfovy, dL_dcolor, v[10] /*sh*/,
-	                                        sh_degree, v[3] /*campos*/, v[11], num_rendered, v[12], v[13], raw_params,
-	                                        sh_grad_view,
-	                                        // view-factored mode: the SH step follows the exchange (gsr_sh_adam_from_views);
-	                                        // sh_adam_ -- its lazy form -- served the forward pass (rows this view sees caught up)
-	                                        // and lets backward run this step's slice of the rotating catch-up
-	                                        bwd_adam, view_stats, geom_adam, map_grad(dL_ddepth), map_grad(dL_dalpha));
+	                                        v[6] /*scales*/, v[7] /*rotations*/, s.scale_modifier_, v[8] /*cov3Ds*/,
+	                                        v[1] /*view*/, v[2] /*proj*/, s.tanfovx_, s.tanfovy_, dL_dcolor, v[10] /*sh*/,
+	                                        s.sh_degree_, v[3] /*campos*/, v[11], state->num_rendered, v[12], v[13], b);
 	// gradient order of the forward inputs (src/gaussian_rasterizer.cpp:159-179); absent optionals get none
 	auto opt = [](const torch::Tensor& grad, const torch::Tensor& input) {
 		return (input.defined() && input.numel() != 0 && grad.defined()) ? grad : torch::Tensor();
 	};
-	// (undefined where an extension took the gradient's place: fused optimizer steps, training_outputs_only)
+	// (undefined where an extension took the gradient's place: fused optimizer steps, training_outputs_only_)
 	torch::autograd::tensor_list out = {std::get<3>(g) /*means3D*/,
 	                                    std::get<0>(g) /*means2D*/,
 	                                    opt(std::get<5>(g), v[10]) /*sh*/,
@@ -193,25 +155,43 @@ bool no_backward(const std::initializer_list<const torch::Tensor*> inputs)
 	return true;
 }
 
-// The forward pass alone (GSR_FORWARD_ONLY): RasterizeGaussiansCUDA directly with the bit, no autograd node, no buffers kept.
-// Only the lazy form of sh_adam_ concerns a forward pass (its rows are then read, not written).
-// depth / alpha: defined = the maps are rendered into them (render_depth_)
-std::tuple<torch::Tensor, torch::Tensor> forward_only_impl(const torch::Tensor& means3D, const torch::Tensor& sh,
-                                                           const torch::Tensor& colors_precomp, const torch::Tensor& opacities,
-                                                           const torch::Tensor& scales, const torch::Tensor& rotations,
-                                                           const torch::Tensor& cov3Ds_precomp, const GaussianRasterizationSettings& s,
-                                                           const GaussianRasterizationExtensions& e,
-                                                           const torch::Tensor& depth = torch::Tensor(),
-                                                           const torch::Tensor& alpha = torch::Tensor())
+// The body of GaussianRasterizer::forward, GaussianRasterizerEx::forward and forwardWithDepth.  ext == nullptr: the reference's
+// rasterizer (its own autograd node, GaussianRasterizerFunction).  (color, radii, depth, alpha): the maps only with_depth.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> rasterizer_forward(
+    GaussianRasterizationSettings& s, const GaussianRasterizationExtensions* ext, bool with_depth, torch::Tensor means3D,
+    torch::Tensor means2D, torch::Tensor opacities, bool has_shs, bool has_colors_precomp, bool has_scales, bool has_rotations,
+    bool has_cov3D_precomp, torch::Tensor shs, torch::Tensor colors_precomp, torch::Tensor scales, torch::Tensor rotations,
+    torch::Tensor cov3D_precomp)
 {
-	torch::NoGradGuard no_grad;
-	const ShAdamStep lazy = e.sh_adam_.row_step.defined() ? e.sh_adam_ : ShAdamStep();
-	auto r = RasterizeGaussiansCUDA(s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_,
-	                                cov3Ds_precomp, s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_,
-	                                s.image_height_, s.image_width_, sh, s.sh_degree_, s.campos_, s.prefiltered_,
-	                                e.raw_params_ | (e.cull_empty_tiles_ ? GSR_CULL_EMPTY_TILES : 0) | GSR_FORWARD_ONLY, lazy,
-	                                e.workspace_, depth, alpha);
-	return std::make_tuple(std::get<1>(r), std::get<2>(r));
+	validate_and_fill(means3D, has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp,
+	                  scales, rotations, cov3D_precomp);
+	static const GaussianRasterizationExtensions none;
+	const GaussianRasterizationExtensions& e = ext ? *ext : none;
+	// forward_only_, or a render no backward pass can follow (NoGradGuard, or nothing to differentiate): the forward pass alone
+	// (GSR_FORWARD_ONLY) -- RasterizeGaussiansCUDA directly with the bit, no autograd node, no buffers kept
+	if (e.forward_only_ ||
+	    no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp})) {
+		torch::NoGradGuard no_grad;
+		torch::Tensor depth, alpha;
+		if (with_depth) {
+			const auto opts = means3D.options().dtype(torch::kFloat32);
+			depth = torch::zeros({s.image_height_, s.image_width_}, opts);
+			alpha = torch::zeros({s.image_height_, s.image_width_}, opts);
+		}
+		auto r = rasterize_forward(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, s, e, GSR_FORWARD_ONLY,
+		                           depth, alpha);
+		return std::make_tuple(std::get<1>(r), std::get<2>(r), depth, alpha);
+	}
+	if (!ext) {
+		auto result = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, s);
+		return std::make_tuple(result[0], result[1], torch::Tensor(), torch::Tensor());
+	}
+	GaussianRasterizationExtensions node_ext = e;   // the one copy of a forward pass: the autograd node takes it over
+	if (with_depth) node_ext.render_depth_ = true;
+	auto result = GaussianRasterizerFunctionEx::apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+	                                                  cov3D_precomp, s, std::move(node_ext));
+	if (!with_depth) return std::make_tuple(result[0], result[1], torch::Tensor(), torch::Tensor());
+	return std::make_tuple(result[0], result[1], result[2], result[3]);
 }
 
 }  // namespace
@@ -222,7 +202,7 @@ torch::autograd::tensor_list GaussianRasterizerFunction::forward(
     torch::Tensor cov3Ds_precomp, GaussianRasterizationSettings s)
 {
 	(void)means2D;  // only its gradient slot matters
-	return forward_impl(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s,
+	return forward_impl(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, std::move(s),
 	                    GaussianRasterizationExtensions());
 }
 
@@ -238,7 +218,7 @@ torch::autograd::tensor_list GaussianRasterizerFunctionEx::forward(
     torch::Tensor cov3Ds_precomp, GaussianRasterizationSettings s, GaussianRasterizationExtensions e)
 {
 	(void)means2D;
-	return forward_impl(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, e);
+	return forward_impl(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, std::move(s), std::move(e));
 }
 
 torch::autograd::tensor_list GaussianRasterizerFunctionEx::backward(torch::autograd::AutogradContext* ctx,
@@ -252,15 +232,9 @@ std::tuple<torch::Tensor, torch::Tensor> GaussianRasterizer::forward(
     bool has_scales, bool has_rotations, bool has_cov3D_precomp, torch::Tensor shs, torch::Tensor colors_precomp,
     torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3D_precomp)
 {
-	validate_and_fill(means3D, has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp,
-	                  scales, rotations, cov3D_precomp);
-	// (a render no backward pass can follow -- NoGradGuard, or nothing to differentiate: the forward pass alone)
-	if (no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp}))
-		return forward_only_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings_,
-		                         GaussianRasterizationExtensions());
-	auto result = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-	                                 raster_settings_);
-	return std::make_tuple(result[0], result[1]);
+	auto r = rasterizer_forward(raster_settings_, nullptr, false, means3D, means2D, opacities, has_shs, has_colors_precomp, has_scales,
+	                            has_rotations, has_cov3D_precomp, shs, colors_precomp, scales, rotations, cov3D_precomp);
+	return std::make_tuple(std::get<0>(r), std::get<1>(r));
 }
 
 std::tuple<torch::Tensor, torch::Tensor> GaussianRasterizerEx::forward(
@@ -268,15 +242,9 @@ std::tuple<torch::Tensor, torch::Tensor> GaussianRasterizerEx::forward(
     bool has_scales, bool has_rotations, bool has_cov3D_precomp, torch::Tensor shs, torch::Tensor colors_precomp,
     torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3D_precomp)
 {
-	validate_and_fill(means3D, has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp,
-	                  scales, rotations, cov3D_precomp);
-	if (extensions_.forward_only_ ||
-	    no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp}))
-		return forward_only_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings_,
-		                         extensions_);
-	auto result = GaussianRasterizerFunctionEx::apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-	                                                  cov3D_precomp, raster_settings_, extensions_);
-	return std::make_tuple(result[0], result[1]);
+	auto r = rasterizer_forward(raster_settings_, &extensions_, false, means3D, means2D, opacities, has_shs, has_colors_precomp,
+	                            has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp, scales, rotations, cov3D_precomp);
+	return std::make_tuple(std::get<0>(r), std::get<1>(r));
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> GaussianRasterizerEx::forwardWithDepth(
@@ -284,20 +252,6 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> GaussianR
     bool has_scales, bool has_rotations, bool has_cov3D_precomp, torch::Tensor shs, torch::Tensor colors_precomp,
     torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3D_precomp)
 {
-	validate_and_fill(means3D, has_shs, has_colors_precomp, has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp,
-	                  scales, rotations, cov3D_precomp);
-	GaussianRasterizationExtensions e = extensions_;
-	e.render_depth_ = true;
-	if (e.forward_only_ ||
-	    no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp})) {
-		const auto opts = means3D.options().dtype(torch::kFloat32);
-		auto depth = torch::zeros({raster_settings_.image_height_, raster_settings_.image_width_}, opts);
-		auto alpha = torch::zeros({raster_settings_.image_height_, raster_settings_.image_width_}, opts);
-		auto r = forward_only_impl(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings_, e,
-		                           depth, alpha);
-		return std::make_tuple(std::get<0>(r), std::get<1>(r), depth, alpha);
-	}
-	auto result = GaussianRasterizerFunctionEx::apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-	                                                  cov3D_precomp, raster_settings_, e);
-	return std::make_tuple(result[0], result[1], result[2], result[3]);
+	return rasterizer_forward(raster_settings_, &extensions_, true, means3D, means2D, opacities, has_shs, has_colors_precomp,
+	                          has_scales, has_rotations, has_cov3D_precomp, shs, colors_precomp, scales, rotations, cov3D_precomp);
 }

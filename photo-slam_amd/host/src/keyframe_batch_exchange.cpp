@@ -184,7 +184,7 @@ ViewFactoredExchange::ViewFactoredExchange(c10::intrusive_ptr<c10d::ProcessGroup
 	p.capacity = pk.capacity;
 	p.messages = gathered_;
 	auto issue = [&]() {
-		// (four launches on the current stream -- or none: the backward pass wrote the message itself, ShAdamStep::packed_view)
+		// (four launches on the current stream -- or none: the backward pass wrote the message itself, GaussianRasterizationExtensions::packed_view_)
 		if (!pk.prepacked) packColorView(pk.color_view, camera_center.detach().reshape({3}), pk.capacity, send, pk.scratch);
 		p.work = pg_->_allgather_base(gathered_, send);
 	};
@@ -334,7 +334,7 @@ void TrainStep::beginCountExchange()
 
 // The mask and prefix sections of this view's message from the radii the forward pass has just left (gsr_forward returns
 // behind preprocess_fwd: they are complete) -- three small launches on the gather stream, next to the forward blend; the compute
-// stream waits for them in front of the backward pass, which writes rows and header (ShAdamStep::packed_view).
+// stream waits for them in front of the backward pass, which writes rows and header (GaussianRasterizationExtensions::packed_view_).
 void TrainStep::planPackedView(const torch::Tensor& radii)
 {
 	torch::NoGradGuard ng;

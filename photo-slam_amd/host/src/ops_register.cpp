@@ -177,8 +177,10 @@ std::tuple<torch::Tensor, torch::Tensor> trainer_render(int64_t h, torch::Tensor
 	pipe.convert_SHs_ = convert_SHs;
 	pipe.compute_cov3D_ = compute_cov3D;
 	torch::Tensor override_color;
+	GaussianRasterizationExtensions ext;
+	ext.raw_params_ = fuse_activations ? 7 : 0;
 	auto pkg = GaussianRenderer::render(make_kf(view, proj, campos, fovx, fovy, H, W), (int)H, (int)W, t->gaussians_, pipe,
-	                                    t->background_, override_color, 1.0f, false, fuse_activations);
+	                                    t->background_, override_color, 1.0f, false, ext);
 	return std::make_tuple(std::get<0>(pkg), std::get<3>(pkg));
 }
 // TrainStep::renderView: a forward-only render of the current model into the trainer's second workspace (the image, detached)

@@ -128,7 +128,7 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
 {
 	return RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
 	                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-	                              prefiltered, /*raw_params=*/0);
+	                              prefiltered, RasterForwardExtensions());
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
@@ -143,8 +143,7 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 {
 	return RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
 	                                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-	                                      geomBuffer, R, binningBuffer, imageBuffer, /*raw_params=*/0, torch::Tensor(),
-	                                      ShAdamStep(), std::vector<torch::Tensor>());
+	                                      geomBuffer, R, binningBuffer, imageBuffer, RasterBackwardExtensions());
 }
 
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
@@ -153,35 +152,9 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
     const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
     const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
     const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
-    const bool prefiltered, const int raw_params)
+    const bool prefiltered, const RasterForwardExtensions& ext)
 {
-	return RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-	                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-	                              prefiltered, raw_params, ShAdamStep());
-}
-
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
-    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
-    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
-    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
-    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
-    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
-    const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace)
-{
-	return RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-	                              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-	                              prefiltered, raw_params, sh_adam, workspace, torch::Tensor(), torch::Tensor());
-}
-
-std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
-    const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
-    const torch::Tensor& opacity, const torch::Tensor& scales, const torch::Tensor& rotations,
-    const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
-    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy, const int image_height,
-    const int image_width, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
-    const bool prefiltered, const int raw_params, const ShAdamStep& sh_adam, RasterWorkspace* workspace,
-    const torch::Tensor& out_depth, const torch::Tensor& out_alpha)
-{
+	RasterWorkspace* const workspace = ext.workspace;
 	if (means3D.ndimension() != 2 || means3D.size(1) != 3) {
 		AT_ERROR("means3D must have dimensions (num_points, 3)");
 	}
@@ -232,14 +205,15 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
 		a.tan_fovx = tan_fovx;
 		a.tan_fovy = tan_fovy;
 		a.prefiltered = prefiltered ? 1 : 0;
-		a.raw_params = raw_params;
+		a.raw_params = ext.raw_params;
 		a.out_color = out_color.data_ptr<float>();
 		a.radii = radii.data_ptr<int>();
-		a.out_depth = map_ptr(out_depth, means3D, H, W, "out_depth");
-		a.out_alpha = map_ptr(out_alpha, means3D, H, W, "out_alpha");
+		a.out_depth = map_ptr(ext.out_depth, means3D, H, W, "out_depth");
+		a.out_alpha = map_ptr(ext.out_alpha, means3D, H, W, "out_alpha");
 		gsr_sh_adam adam{};
 		gsr_sh_adam_lazy lazy{};
-		if (sh_adam.row_step.defined()) {   // lazy SH Adam: the forward pass brings visible rows up to date (in place)
+		if (ext.sh_adam && ext.sh_adam->row_step.defined()) {   // lazy SH Adam: the forward pass brings visible rows up to date (in place)
+			const ShAdamStep& sh_adam = *ext.sh_adam;
 			if (!sh_adam.exp_avg.defined() || !sh.defined() || sh.scalar_type() != torch::kFloat32 || !sh.is_contiguous() ||
 			    !sh_adam.exp_avg.is_contiguous() || !sh_adam.exp_avg_sq.is_contiguous() || sh_adam.exp_avg.sizes() != sh.sizes() ||
 			    sh_adam.exp_avg_sq.sizes() != sh.sizes())
@@ -261,46 +235,16 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
                                const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
                                const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
                                const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                               const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
-                               const std::vector<torch::Tensor>& view_stats)
+                               const RasterBackwardExtensions& ext)
 {
-	return RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-	                                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-	                                      geomBuffer, R, binningBuffer, imageBuffer, raw_params, dL_dcolor_view, sh_adam, view_stats,
-	                                      GeomAdamStep());
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-           torch::Tensor>
-RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
-                               const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
-                               const float scale_modifier, const torch::Tensor& cov3D_precomp,
-                               const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx,
-                               const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
-                               const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
-                               const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                               const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
-                               const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam)
-{
-	return RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
-	                                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer,
-	                                      R, binningBuffer, imageBuffer, raw_params, dL_dcolor_view, sh_adam, view_stats, geom_adam,
-	                                      torch::Tensor(), torch::Tensor());
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-           torch::Tensor>
-RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
-                               const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
-                               const float scale_modifier, const torch::Tensor& cov3D_precomp,
-                               const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx,
-                               const float tan_fovy, const torch::Tensor& dL_dout_color, const torch::Tensor& sh,
-                               const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer,
-                               const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                               const int raw_params, const torch::Tensor& dL_dcolor_view, const ShAdamStep& sh_adam,
-                               const std::vector<torch::Tensor>& view_stats, const GeomAdamStep& geom_adam,
-                               const torch::Tensor& dL_ddepth, const torch::Tensor& dL_dalpha)
-{
+	// (an absent extension reads as its default-constructed value: off)
+	static const ShAdamStep no_sh_adam;
+	static const GeomAdamStep no_geom_adam;
+	static const std::vector<torch::Tensor> no_view_stats;
+	const ShAdamStep& sh_adam = ext.sh_adam ? *ext.sh_adam : no_sh_adam;
+	const GeomAdamStep& geom_adam = ext.geom_adam ? *ext.geom_adam : no_geom_adam;
+	const std::vector<torch::Tensor>& view_stats = ext.view_stats ? *ext.view_stats : no_view_stats;
+	const torch::Tensor& dL_dcolor_view = ext.dL_dcolor_view;
 	const int P = static_cast<int>(means3D.size(0));
 	const int H = static_cast<int>(dL_dout_color.size(1));
 	const int W = static_cast<int>(dL_dout_color.size(2));
@@ -324,7 +268,7 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 				    t->sizes() != geom_adam.param[i].sizes() || t->size(0) != P)
 					throw std::runtime_error("geom_adam tensors must be contiguous float32 [num_points, ...] on the device of means3D");
 	}
-	const bool slim = geom_adam.training_outputs_only;
+	const bool slim = ext.training_outputs_only;
 	if (slim && !has_scales) throw std::runtime_error("training_outputs_only needs scales / rotations (dL_dcov3D is not written)");
 	torch::Tensor dL_drotations, dL_dmeans3D, dL_dscales, dL_dopacity;
 	if (geom) {
@@ -391,8 +335,8 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 		a.binning_buffer = bin_c.numel() ? reinterpret_cast<char*>(bin_c.data_ptr()) : nullptr;
 		a.image_buffer = reinterpret_cast<char*>(img_c.data_ptr());
 		a.dL_dpix = dpix.ptr;
-		a.dL_ddepth = map_ptr(dL_ddepth, means3D, H, W, "dL_ddepth");
-		a.dL_dalpha = map_ptr(dL_dalpha, means3D, H, W, "dL_dalpha");
+		a.dL_ddepth = map_ptr(ext.dL_ddepth, means3D, H, W, "dL_ddepth");
+		a.dL_dalpha = map_ptr(ext.dL_dalpha, means3D, H, W, "dL_dalpha");
 		a.dL_dmean2D = dL_dmeans2D.defined() ? dL_dmeans2D.data_ptr<float>() : nullptr;
 		a.dL_dconic = nullptr;  // internal to the reference's wrapper (rasterize_points.cu:152)
 		a.dL_dopacity = dL_dopacity.defined() ? dL_dopacity.data_ptr<float>() : nullptr;
@@ -417,19 +361,19 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 			a.sh_adam = &adam;
 		}
 		a.dL_dcolor_view = factored ? dL_dcolor_view.data_ptr<float>() : nullptr;
-		a.color_view_ready_stream = factored ? sh_adam.color_view_ready_stream : nullptr;
-		if (factored && sh_adam.packed_view.defined()) {
-			const auto& m = sh_adam.packed_view;
+		a.color_view_ready_stream = factored ? ext.color_view_ready_stream : nullptr;
+		if (factored && ext.packed_view.defined()) {
+			const auto& m = ext.packed_view;
 			if (m.scalar_type() != torch::kInt32 || !m.is_contiguous() || m.device() != means3D.device() ||
-			    m.numel() < packedViewWords(P, sh_adam.packed_capacity))
+			    m.numel() < packedViewWords(P, ext.packed_capacity))
 				throw std::runtime_error("RasterizeGaussiansBackwardCUDA: packed_view must be a contiguous int32 message of "
 				                         "packedViewWords(P, packed_capacity) words on the device of means3D");
 			a.packed_view = reinterpret_cast<uint32_t*>(m.data_ptr<int32_t>());
-			a.packed_capacity_rows = static_cast<int>(sh_adam.packed_capacity);
+			a.packed_capacity_rows = static_cast<int>(ext.packed_capacity);
 		}
 		a.dL_dscale = (has_scales && !geom) ? dL_dscales.data_ptr<float>() : nullptr;
 		a.dL_drot = (has_scales && !geom) ? dL_drotations.data_ptr<float>() : nullptr;
-		a.raw_params = raw_params;
+		a.raw_params = ext.raw_params;
 		gsr_geom_adam ga{};
 		if (geom) {
 			gsr_adam_tensor* ts[4] = {&ga.xyz, &ga.opacity, &ga.scaling, &ga.rotation};

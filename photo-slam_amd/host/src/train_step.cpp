@@ -121,26 +121,34 @@ float GaussianModel::updateLearningRate(int step)
 	return lr;
 }
 
+ShAdamStep GaussianModel::featuresAdamStep(ShStep which) const
+{
+	const AdamGroup& grp = groups_.at(1);
+	const bool taken = which == ShStep::LazyTaken;
+	ShAdamStep s;
+	s.exp_avg = grp.exp_avg;
+	s.exp_avg_sq = grp.exp_avg_sq;
+	s.step = grp.step;
+	s.lr = taken ? features_lr_hist_.at(0).first : grp.lr * lr_scale_;
+	s.lr_tail = taken ? features_lr_hist_.at(0).second : grp.lr_tail * lr_scale_;
+	if (which == ShStep::Eager) return s;
+	s.row_step = features_row_step_;
+	s.window = features_lazy_window_;
+	for (size_t k = taken ? 1 : 0; k < features_lr_hist_.size(); k++) {
+		s.lr_past.push_back(features_lr_hist_[k].first);
+		s.lr_tail_past.push_back(features_lr_hist_[k].second);
+	}
+	return s;
+}
+
 void GaussianModel::syncFeatures()
 {
 	if (!features_row_step_.defined()) return;
 	torch::NoGradGuard ng;
-	auto row_step = features_row_step_;
-	features_row_step_ = torch::Tensor();   // (first: the calls below may come back here)
-	if (!features_lr_hist_.empty() && groups_.size() > 1) {
-		auto& grp = groups_[1];
-		ShAdamStep s;
-		s.exp_avg = grp.exp_avg;
-		s.exp_avg_sq = grp.exp_avg_sq;
-		s.step = grp.step;   // the steps the tensor has taken; the newest entry of the history belongs to it
-		s.lr = features_lr_hist_[0].first;
-		s.lr_tail = features_lr_hist_[0].second;
-		s.row_step = row_step;
-		s.window = features_lazy_window_;
-		for (size_t k = 1; k < features_lr_hist_.size(); k++) {
-			s.lr_past.push_back(features_lr_hist_[k].first);
-			s.lr_tail_past.push_back(features_lr_hist_[k].second);
-		}
+	const bool behind = !features_lr_hist_.empty() && groups_.size() > 1;
+	const ShAdamStep s = behind ? featuresAdamStep(ShStep::LazyTaken) : ShAdamStep();
+	features_row_step_ = torch::Tensor();   // (before the flush: the calls below may come back here)
+	if (behind) {
 		auto sh = features_.detach();
 		shAdamFlush(sh, s);
 	}
@@ -181,13 +189,23 @@ void GaussianModel::addDensificationStats(torch::Tensor& viewspace_point_tensor,
 	denom_.index_put_({update_filter}, denom_.index({update_filter}) + 1);
 }
 
+// a viewer's render: the raw leaves in the rasterizer, forward-only, into the second workspace
+GaussianRasterizationExtensions TrainStep::viewExtensions()
+{
+	GaussianRasterizationExtensions ext;
+	ext.raw_params_ = 7;
+	ext.cull_empty_tiles_ = cull_empty_tiles_;
+	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
+	ext.forward_only_ = true;
+	return ext;
+}
+
 torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf)
 {
 	torch::NoGradGuard no_grad;
 	torch::Tensor override_color;
 	auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_, override_color, 1.0f,
-	                                    false, /*fuse_activations=*/true, torch::Tensor(), ShAdamStep(), {}, GeomAdamStep(),
-	                                    cull_empty_tiles_, persistent_workspace_ ? &view_workspace_ : nullptr, /*forward_only=*/true);
+	                                    false, viewExtensions());
 	return std::get<0>(pkg);
 }
 
@@ -196,9 +214,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::renderViewWit
 	torch::NoGradGuard no_grad;
 	torch::Tensor override_color;
 	auto pkg = GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_,
-	                                             override_color, 1.0f, false, /*fuse_activations=*/true, torch::Tensor(), ShAdamStep(),
-	                                             {}, GeomAdamStep(), cull_empty_tiles_,
-	                                             persistent_workspace_ ? &view_workspace_ : nullptr, /*forward_only=*/true);
+	                                             override_color, 1.0f, false, viewExtensions());
 	return std::make_tuple(std::get<0>(pkg), std::get<4>(pkg), std::get<5>(pkg));
 }
 
@@ -247,7 +263,13 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		sh_gathered_ = torch::Tensor();
 		packed_this_step_ = false;
 	}
-	ShAdamStep sh_adam;
+	// the extensions of this step's render: the raw leaves in the rasterizer, and what the blocks below switch on
+	GaussianRasterizationExtensions ext;
+	ext.raw_params_ = 7;
+	ext.sh_grad_view_ = sh_grad_view_;
+	ext.cull_empty_tiles_ = cull_empty_tiles_;
+	ext.workspace_ = persistent_workspace_ ? &workspace_ : nullptr;
+	ShAdamStep& sh_adam = ext.sh_adam_;
 	const auto& o = g->opt_;
 	const bool rebuilds = densifyDue();
 	bool lazy = false;
@@ -266,19 +288,7 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 			g->features_lr_hist_.clear();
 		}
 		grp.step++;   // the step happens inside backward; optimizerStepGroup(1) then finds no gradient
-		sh_adam.exp_avg = grp.exp_avg;
-		sh_adam.exp_avg_sq = grp.exp_avg_sq;
-		sh_adam.lr = grp.lr * g->lr_scale_;
-		sh_adam.lr_tail = grp.lr_tail * g->lr_scale_;
-		sh_adam.step = grp.step;
-		if (lazy) {
-			sh_adam.row_step = g->features_row_step_;
-			sh_adam.window = g->features_lazy_window_;
-			for (const auto& h : g->features_lr_hist_) {
-				sh_adam.lr_past.push_back(h.first);
-				sh_adam.lr_tail_past.push_back(h.second);
-			}
-		}
+		sh_adam = g->featuresAdamStep(lazy ? GaussianModel::ShStep::Lazy : GaussianModel::ShStep::Eager);
 	}
 	// Data-parallel step with the view-factored exchange: the SH rows step AFTER the exchange (stepFeaturesFromViews), and lazily
 	// there too -- a row no view of the batch lights takes a zero-gradient step, i.e. it may take it later.  The forward pass
@@ -297,17 +307,7 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 			g->features_lr_hist_.clear();
 		}
 		grp.step++;   // the step happens in stepFeaturesFromViews(); optimizerStepGroup(1) finds no gradient
-		sh_adam.exp_avg = grp.exp_avg;
-		sh_adam.exp_avg_sq = grp.exp_avg_sq;
-		sh_adam.lr = grp.lr * g->lr_scale_;
-		sh_adam.lr_tail = grp.lr_tail * g->lr_scale_;
-		sh_adam.step = grp.step;
-		sh_adam.row_step = g->features_row_step_;
-		sh_adam.window = g->features_lazy_window_;
-		for (const auto& h : g->features_lr_hist_) {
-			sh_adam.lr_past.push_back(h.first);
-			sh_adam.lr_tail_past.push_back(h.second);
-		}
+		sh_adam = g->featuresAdamStep(GaussianModel::ShStep::Lazy);
 		views_adam_ = sh_adam;
 		views_adam_pending_ = true;
 	}
@@ -320,7 +320,7 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	if (early_gather && factored_exchange_ && process_group_ && g->xyz_.is_cuda()) {
 		// the exchange's gather waits for the colour gradients only, not for the whole backward pass (keyframe_batch_exchange.cpp)
 		if (!gather_stream_) gather_stream_ = c10::hip::getStreamFromPool(/*isHighPriority=*/false, g->xyz_.device().index()).stream();
-		sh_adam.color_view_ready_stream = gather_stream_;
+		ext.color_view_ready_stream_ = gather_stream_;
 		gather_stream_in_use_ = true;
 	}
 #endif
@@ -331,10 +331,10 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	static const int pack_env = [] { const char* e = getenv("GSR_PACK_IN_BACKWARD"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }();
 	prepacked_this_step_ = packed_this_step_ && (pack_env >= 0 ? pack_env != 0 : pack_in_backward_);
 	if (prepacked_this_step_) {
-		sh_adam.packed_view = sh_packed_send_;
-		sh_adam.packed_capacity = (g->xyz_.size(0) + 3) / 4 * 4;
+		ext.packed_view_ = sh_packed_send_;
+		ext.packed_capacity_ = (g->xyz_.size(0) + 3) / 4 * 4;
 	}
-	GeomAdamStep geom_adam;
+	GeomAdamStep& geom_adam = ext.geom_adam_;
 	// (an iteration that resets the opacity replaces that leaf AFTER backward: the reference's optimizer step then skips it -- no
 	// gradient -- while a step fused into backward would already have been taken: src/gaussian_mapper.cpp:732-735)
 	const bool resets = densify_ && iteration_ < o.densify_until_iter_ && o.opacity_reset_interval_ &&
@@ -353,22 +353,17 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		}
 	}
 	// the statistics are fused (or over) in every mode of this step: nobody reads the viewspace gradient or dL_dcov3D
-	geom_adam.training_outputs_only = true;
+	ext.training_outputs_only_ = true;
 	// the densification statistics of this view (:714-719) are added by the backward kernel that holds dL_dmean2D in
 	// registers
-	std::vector<torch::Tensor> view_stats;
-	if (iteration_ < o.densify_until_iter_) view_stats = {g->xyz_gradient_accum_, g->denom_, g->max_radii2D_};
+	if (iteration_ < o.densify_until_iter_) ext.view_stats_ = {g->xyz_gradient_accum_, g->denom_, g->max_radii2D_};
 	g->in_lazy_step_ = lazy;
 	// (with the depth loss: the same render with the depth and alpha maps appended, GaussianRenderer::renderWithDepth)
 	auto pkg = use_depth ? GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, g, pipe, background_,
-	                                                         override_color, 1.0f, false, /*fuse_activations=*/true, sh_grad_view_,
-	                                                         sh_adam, view_stats, geom_adam, cull_empty_tiles_,
-	                                                         persistent_workspace_ ? &workspace_ : nullptr)
+	                                                         override_color, 1.0f, false, ext)
 	                     : [&] {
 		                       auto p4 = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, g, pipe, background_,
-		                                                          override_color, 1.0f, false, /*fuse_activations=*/true, sh_grad_view_,
-		                                                          sh_adam, view_stats, geom_adam, cull_empty_tiles_,
-		                                                          persistent_workspace_ ? &workspace_ : nullptr);
+		                                                          override_color, 1.0f, false, ext);
 		                       return std::make_tuple(std::get<0>(p4), std::get<1>(p4), std::get<2>(p4), std::get<3>(p4),
 		                                              torch::Tensor(), torch::Tensor());
 	                       }();
@@ -466,12 +461,9 @@ void TrainStep::stepFeaturesFromViews(torch::Tensor campos_views, torch::Tensor 
 	}
 	auto& grp = g->groups_[1];
 	if (first_part) grp.step++;
-	ShAdamStep a;
-	a.exp_avg = grp.exp_avg.narrow(0, row0, n);
-	a.exp_avg_sq = grp.exp_avg_sq.narrow(0, row0, n);
-	a.lr = grp.lr * g->lr_scale_;
-	a.lr_tail = grp.lr_tail * g->lr_scale_;
-	a.step = grp.step;
+	ShAdamStep a = g->featuresAdamStep(GaussianModel::ShStep::Eager);
+	a.exp_avg = a.exp_avg.narrow(0, row0, n);
+	a.exp_avg_sq = a.exp_avg_sq.narrow(0, row0, n);
 	auto sh = g->features_.detach().narrow(0, row0, n);
 	shAdamFromViews(g->xyz_.detach().narrow(0, row0, n), campos_views, dL_dcolor_views, g->active_sh_degree_,
 	                1.0f / static_cast<float>(dL_dcolor_views.size(0)), sh, a);
@@ -491,13 +483,8 @@ void TrainStep::stepFeaturesFromPackedViews(torch::Tensor messages, int64_t msg_
 	g->syncFeatures();
 	auto& grp = g->groups_[1];
 	grp.step++;
-	ShAdamStep a;
-	a.exp_avg = grp.exp_avg;
-	a.exp_avg_sq = grp.exp_avg_sq;
-	a.lr = grp.lr * g->lr_scale_;
-	a.lr_tail = grp.lr_tail * g->lr_scale_;
-	a.step = grp.step;
-	shAdamFromPackedViews(g->xyz_.detach(), messages, msg_stride, n_views, g->active_sh_degree_, scale, sh, a);
+	shAdamFromPackedViews(g->xyz_.detach(), messages, msg_stride, n_views, g->active_sh_degree_, scale, sh,
+	                      g->featuresAdamStep(GaussianModel::ShStep::Eager));
 }
 
 void TrainStep::finishFeaturesFromViews()
