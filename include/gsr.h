@@ -117,7 +117,8 @@ typedef struct gsr_forward_args {
 	float scale_modifier;
 	const float* rotations;      /* [P,4] (r,x,y,z), NOT normalised in-kernel (forward.cu:127) */
 	const float* cov3D_precomp;  /* [P,6] or NULL (exactly one of scales+rotations / cov3D_precomp) */
-	const float* viewmatrix;     /* [16] = W2C^T row-major, i.e. element (r,c) at [4c+r] */
+	const float* viewmatrix;     /* [16] = W2C^T row-major, i.e. element (r,c) at [4c+r].  The backward pass can differentiate with
+	                                respect to viewmatrix, projmatrix and cam_pos: gsr_backward_args.dL_dviewmatrix and below */
 	const float* projmatrix;     /* [16] = (Proj W2C)^T */
 	const float* cam_pos;        /* [3] */
 	float tan_fovx, tan_fovy;
@@ -214,7 +215,7 @@ typedef struct gsr_backward_args {
 	float scale_modifier;
 	const float* rotations;
 	const float* cov3D_precomp;
-	const float* viewmatrix;
+	const float* viewmatrix;     /* these three have gradients: dL_dviewmatrix / dL_dprojmatrix / dL_dcampos below */
 	const float* projmatrix;
 	const float* campos;
 	float tan_fovx, tan_fovy;
@@ -297,6 +298,24 @@ typedef struct gsr_backward_args {
 	 * fused Adam steps, geom_adam included). */
 	const float* dL_ddepth;
 	const float* dL_dalpha;
+	/* Extension (all four or none, GSR_ERR_INVALID_ARG otherwise; NULL = the reference contract): gradients of the loss with respect
+	 * to the camera -- viewmatrix, projmatrix and campos AS THE KERNELS USE THEM, treated as three independent inputs, with the
+	 * conventions of the rest of this pass (consistent with dL_dmean3D: the frustum-clamp rule of computeCov2D, and the depth map's
+	 * dL/dz when dL_ddepth is given).  Summed over the Gaussians with radii > 0, x = (mean, 1):
+	 *   dL_dviewmatrix[4c+r] = sum dL/dt_r x_c + (J^T dL/dT)(r,c) [c < 3]    t = W2C x, T = J W of the EWA projection, r < 3
+	 *   dL_dprojmatrix[4c+r] = sum dL/dhom_r x_c                              hom = Proj x of the pixel position, r = 0, 1, 3
+	 *   dL_dcampos           = - sum (the SH view-direction term of dL_dmean3D);  0 with colors_precomp and at D == 0
+	 * All 35 floats are written (no zero-fill by the caller); the entries the render does not depend on -- [3], [7], [11], [15] of
+	 * dL_dviewmatrix, [2], [6], [10], [14] of dL_dprojmatrix -- are 0, and so is everything for P == 0 or a view that sees nothing.
+	 * Nothing here assumes projmatrix = Proj W2C or campos = -R^T t: a caller that built the three from one pose chains the
+	 * raw gradients through that construction.  The sums are formed without atomics, in a fixed order: the same inputs give the
+	 * same bits.  pose_scratch: gsr_pose_grad_scratch_bytes(P) device bytes, 4-byte aligned, the caller's (contents: don't care).
+	 * With geom_adam the sums use the positions as they were before the fused step.  Not together with dL_dcolor_view /
+	 * packed_view (the multi-GPU exchange): GSR_ERR_UNSUPPORTED. */
+	float* dL_dviewmatrix;       /* [16] device floats, the layout of viewmatrix */
+	float* dL_dprojmatrix;       /* [16], the layout of projmatrix */
+	float* dL_dcampos;           /* [3] */
+	char* pose_scratch;
 } gsr_backward_args;
 
 /* Rasterizer::backward, cuda_rasterizer/rasterizer_impl.cu:340-433.
@@ -562,6 +581,7 @@ size_t gsr_image_bytes(int width, int height);
 size_t gsr_binning_bytes_for(int num_rendered, int raw_params);
 size_t gsr_image_bytes_for(int width, int height, int raw_params);
 size_t gsr_knn_scratch_bytes(int P);
+size_t gsr_pose_grad_scratch_bytes(int P);   /* gsr_backward_args.pose_scratch */
 
 /* Optional per-stage timing with HIP events recorded on the caller's stream (process-wide switch,
  * meant for single-stream benchmarking).

@@ -111,7 +111,9 @@ class BackwardArgs(C.Structure):
                 ("stat_grad_accum", C.c_void_p), ("stat_denom", C.c_void_p), ("stat_max_radii", C.c_void_p),
                 ("geom_adam", C.POINTER(GeomAdam)), ("color_view_ready_stream", C.c_void_p),
                 ("packed_view", C.c_void_p), ("packed_capacity_rows", C.c_int),
-                ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p)]
+                ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p),
+                ("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p),
+                ("pose_scratch", C.c_void_p)]
 
 class DensifySelectArgs(C.Structure):
     _fields_ = [("P", C.c_int), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p), ("scaling", C.c_void_p),
@@ -143,7 +145,7 @@ EXPORTED_SYMBOLS = [
     "gsr_sh_grad_from_packed_views", "gsr_sh_adam_from_packed_views", "gsr_last_visible_count", "gsr_check_packed_views", "gsr_depth_resort_count",
     "gsr_host_wait_stats", "gsr_binning_tile_first", "gsr_densify_morton_scratch_bytes",
     "gsr_binning_bytes_for", "gsr_image_bytes_for", "gsr_last_forward_only",
-    "gsr_depth_loss_scratch_bytes", "gsr_depth_l1_loss",
+    "gsr_depth_loss_scratch_bytes", "gsr_depth_l1_loss", "gsr_pose_grad_scratch_bytes",
 ]
 
 _libs = {}
@@ -178,7 +180,7 @@ def load(path=None):
     L.gsr_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
     L.gsr_knn_mean_dist2.restype = i32
     L.gsr_knn_mean_dist2.argtypes = [i32, vp, vp, ALLOC_FN, vp, vp]
-    for n in ("gsr_geometry_bytes", "gsr_binning_bytes", "gsr_knn_scratch_bytes"):
+    for n in ("gsr_geometry_bytes", "gsr_binning_bytes", "gsr_knn_scratch_bytes", "gsr_pose_grad_scratch_bytes"):
         getattr(L, n).restype = sz
         getattr(L, n).argtypes = [i32]
     L.gsr_image_bytes.restype = sz

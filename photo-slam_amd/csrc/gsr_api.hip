@@ -328,6 +328,7 @@ extern "C" {
 
 size_t gsr_geometry_bytes(int P) { return geometry_bytes(P < 0 ? 0 : P); }
 size_t gsr_binning_bytes(int R) { return binning_bytes(R < 0 ? 0 : R); }
+size_t gsr_pose_grad_scratch_bytes(int P) { return pose_slab_floats(P) * sizeof(float); }
 size_t gsr_image_bytes(int W, int H) { return (W <= 0 || H <= 0) ? 0 : image_bytes(W, H); }
 size_t gsr_binning_bytes_for(int R, int raw_params) { return binning_bytes(R < 0 ? 0 : R, (raw_params & GSR_FORWARD_ONLY) != 0); }
 size_t gsr_image_bytes_for(int W, int H, int raw_params) { return (W <= 0 || H <= 0) ? 0 : image_bytes(W, H, (raw_params & GSR_FORWARD_ONLY) != 0); }
@@ -553,11 +554,17 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	if (!a) return GSR_ERR_INVALID_ARG;
 	int st = validate_common(a->P, a->D, a->M, a->width, a->height, a->shs, a->colors_precomp, a->scales, a->rotations,
 	                         a->cov3D_precomp);
-	if (a->P == 0) return GSR_OK;
+	// the camera pose gradients (gsr.h): all four pointers or none
+	const int pose_ptrs = (a->dL_dviewmatrix != nullptr) + (a->dL_dprojmatrix != nullptr) + (a->dL_dcampos != nullptr) + (a->pose_scratch != nullptr);
+	if (pose_ptrs != 0 && pose_ptrs != 4) return GSR_ERR_INVALID_ARG;
+	const bool pose = pose_ptrs == 4;
+	if (pose && (reinterpret_cast<uintptr_t>(a->pose_scratch) & 3)) return GSR_ERR_INVALID_ARG;
+	if (a->P == 0) return pose ? launch_pose_zero(a->dL_dviewmatrix, a->dL_dprojmatrix, a->dL_dcampos, (hipStream_t)stream_) : GSR_OK;
 	if (st != GSR_OK) return st;
 	if (!a->background || !a->means3D || !a->viewmatrix || !a->projmatrix || !a->campos || !a->geom_buffer ||
 	    !a->image_buffer || !a->dL_dpix || !a->dL_dcolor || !a->dL_dmean3D || a->R < 0)
 		return GSR_ERR_INVALID_ARG;
+	if (pose && (a->dL_dcolor_view || a->packed_view)) return GSR_ERR_UNSUPPORTED;   // not through the multi-GPU exchange
 	if (!a->dL_dopacity && !a->geom_adam) return GSR_ERR_INVALID_ARG;   // (dL_dmean2D / dL_dcov3D: nullable, see gsr.h)
 	if (a->shs && !a->dL_dsh && !a->dL_dcolor_view && !a->sh_adam) return GSR_ERR_INVALID_ARG;
 	if ((a->stat_grad_accum != nullptr) != (a->stat_denom != nullptr) || (a->stat_denom != nullptr) != (a->stat_max_radii != nullptr))
@@ -742,6 +749,8 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	}
 	pb.geom = geom;
 	pb.depth = (depth && R > 0) ? 1 : 0;
+	pb.pose_scratch = pose ? reinterpret_cast<float*>(a->pose_scratch) : nullptr;
+	pb.dL_dview = a->dL_dviewmatrix; pb.dL_dproj = a->dL_dprojmatrix; pb.dL_dcampos = a->dL_dcampos;
 	pb.notify_stream = nullptr; pb.notify_event = nullptr;
 	if (a->color_view_ready_stream && a->dL_dcolor_view) {
 		if ((st = t_sync.init_notify()) != GSR_OK) return fail(st);

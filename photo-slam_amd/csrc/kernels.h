@@ -196,7 +196,21 @@ struct PreprocessBwdParams {
 	// the backward blend left dL/dz, z = the view-space depth, in slot word [9] (gsr_backward_args.dL_ddepth / dL_dalpha): it joins
 	// dL_dtz, the gradient of the view-space z of the mean
 	int depth;
+	// camera pose gradients (gsr_backward_args.dL_dviewmatrix / dL_dprojmatrix / dL_dcampos): the POSE instantiations leave one slab
+	// entry per workgroup and live sum in pose_scratch (pose_slab_* below), pose_final_sum_kernel adds them up; null = off
+	float* pose_scratch;
+	float* dL_dview;          // [16]
+	float* dL_dproj;          // [16]
+	float* dL_dcampos;        // [3]
 };
+// The pose slab: POSE_VP sums of preprocess_bwd_kernel (12 of the view matrix, 12 of the projection), component-major with one
+// entry per workgroup of it, then the 3 camera-centre sums with one entry per workgroup of the kernel that forms the SH direction
+// term (sh_bwd_rows_kernel on the two-kernel path, else preprocess_bwd_kernel).
+constexpr int POSE_VP = 24;
+static inline size_t pose_slab_a_rows(int P) { return ((size_t)(P > 0 ? P : 0) + 127) / 128; }   // PRB_THREADS
+static inline size_t pose_slab_b_rows(int P) { return ((size_t)(P > 0 ? P : 0) + 63) / 64; }     // SHB_THREADS
+static inline size_t pose_slab_floats(int P) { return POSE_VP * pose_slab_a_rows(P) + 3 * pose_slab_b_rows(P) + 4; }
+int launch_pose_zero(float* dL_dview, float* dL_dproj, float* dL_dcampos, hipStream_t stream);
 int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream);
 // does the backward preprocess take the two-kernel path of the reference's SH layout (preprocess_bwd_kernel<true> +
 // sh_bwd_rows_kernel)?  (aligned 48-float rows, a row consumer: gradient rows out, the factored colour gradient, or the fused step)

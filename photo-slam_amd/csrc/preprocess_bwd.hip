@@ -65,7 +65,9 @@ __device__ __forceinline__ void geom_adam_row4(const GeomAdamTensor& t, size_t i
 // SH backward for aligned 48-float rows; DEG = active SH degree.  FACTORED (gsr_backward_args.dL_dcolor_view): the
 // gradient rows are not produced -- the clamp-masked colour gradient leaves instead (12 B instead of 192 B per Gaussian)
 // and gsr_sh_grad_from_views rebuilds dL_dsh for the whole keyframe batch after the exchange.
-template <int DEG, int MODE>   // MODE: 0 = gradient rows out, 1 = factored (colour gradient out), 2 = fused Adam step
+// POSE (gsr_backward_args.dL_dcampos): the direction term is d/d(mean - campos), so its negative, summed over the wave (= the
+// workgroup), is this workgroup's entry of the camera-centre sums in the pose slab (kernels.h) -- an instantiation of its own.
+template <int DEG, int MODE, bool POSE = false>   // MODE: 0 = gradient rows out, 1 = factored (colour gradient out), 2 = fused Adam step
 #ifndef GSR_SHB_WAVES_LO
 #define GSR_SHB_WAVES_LO 6
 #endif
@@ -167,6 +169,7 @@ sh_bwd_rows_kernel(const PreprocessBwdParams p)
 	}
 	if (MODE == 2 && vis && p.lazy_row_step) p.lazy_row_step[idx] = p.lazy_step;   // lazy mode: this row has taken the step
 	float gm[3] = {0.f, 0.f, 0.f};
+	float gc[3] = {0.f, 0.f, 0.f};   // POSE: minus the direction term
 	if (vis) {
 		const float dLx = ddx[0] * dRGB[0] + ddx[1] * dRGB[1] + ddx[2] * dRGB[2];
 		const float dLy = ddy[0] * dRGB[0] + ddy[1] * dRGB[1] + ddy[2] * dRGB[2];
@@ -178,6 +181,11 @@ sh_bwd_rows_kernel(const PreprocessBwdParams p)
 		gm[0] = p.dL_dmean3D[3 * (size_t)idx + 0] + ((+sum2 - ox * ox) * dLx - oy * ox * dLy - oz * ox * dLz) * invsum32;
 		gm[1] = p.dL_dmean3D[3 * (size_t)idx + 1] + (-ox * oy * dLx + (sum2 - oy * oy) * dLy - oz * oy * dLz) * invsum32;
 		gm[2] = p.dL_dmean3D[3 * (size_t)idx + 2] + (-ox * oz * dLx - oy * oz * dLy + (sum2 - oz * oz) * dLz) * invsum32;
+		if constexpr (POSE) {
+			gc[0] = -(((+sum2 - ox * ox) * dLx - oy * ox * dLy - oz * ox * dLz) * invsum32);
+			gc[1] = -((-ox * oy * dLx + (sum2 - oy * oy) * dLy - oz * oy * dLz) * invsum32);
+			gc[2] = -((-ox * oz * dLx - oy * oz * dLy + (sum2 - oz * oz) * dLz) * invsum32);
+		}
 		if (!p.geom.on) {
 			p.dL_dmean3D[3 * (size_t)idx + 0] = gm[0];
 			p.dL_dmean3D[3 * (size_t)idx + 1] = gm[1];
@@ -186,6 +194,14 @@ sh_bwd_rows_kernel(const PreprocessBwdParams p)
 	}
 	// the position's gradient is complete here: its Adam step (zero gradient for culled Gaussians, as a dense optimizer)
 	if (p.geom.on && in_range) geom_adam_row<3>(p.geom.xyz, (size_t)idx, gm);
+	if constexpr (POSE) {
+		float* slab_b = p.pose_scratch + (size_t)POSE_VP * (((size_t)p.P + PRB_THREADS - 1) / PRB_THREADS);   // (pose_slab_a_rows)
+#pragma unroll
+		for (int k = 0; k < 3; k++) {
+			const float c = wave_sum_f32_lane63(gc[k]);
+			if (l == 63) slab_b[(size_t)k * gridDim.x + blockIdx.x] = c;
+		}
+	}
 }
 
 // The row of Gaussian idx of the view's packed message (include/gsr.h: gsr_backward_args.packed_view).  seen_mask = the ballot of
@@ -227,10 +243,23 @@ __device__ __forceinline__ void pack_view_row(const PreprocessBwdParams& p, int 
 // own: as a run-time branch it cost the kernel of the single-GPU step 8 us (181 -> 189 us at C3, profiles/r04_v) with the option off.
 // DEPTH: the backward blend left dL/dz (the depth / alpha maps) in slot word [9]; it joins dL_dtz below (an instantiation of its own,
 // so that the colour-only kernel is the same code as without the feature).
-template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false>
+// POSE: the camera pose gradients (gsr_backward_args.dL_dviewmatrix / dL_dprojmatrix / dL_dcampos).  Everything they need is in
+// registers here: dL/dt and dL/dT of the EWA projection, dL/dhom of the pixel position, the world mean.  Per lane the 24 products
+// (pose_v below), three packed butterflies over the wave (wave_reduce24_swap_f32), the two waves through LDS, and ONE slab entry
+// per workgroup and sum written with plain stores (kernels.h: pose slab); pose_final_sum_kernel adds the entries in a fixed order.
+// No atomics: the same bits every time.  An instantiation of its own, so that the kernels without it stay the same code.
+template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false>
 __global__ void __launch_bounds__(PRB_THREADS)
 preprocess_bwd_kernel(const PreprocessBwdParams p)
 {
+	__shared__ float s_pose[POSE ? PRB_THREADS / 64 : 1][POSE ? POSE_VP + 3 : 1];
+	// POSE: [3c + r] = dL/dW2C(r, c), r < 3; [12 + 3c + k] = dL/dProj(r, c), r = {0, 1, 3}[k]; this lane's terms
+	float pose_v[POSE ? POSE_VP : 1];
+	float pose_c[3] = {0.f, 0.f, 0.f};   // minus the SH direction term (formed here without sh_bwd_rows_kernel)
+	if constexpr (POSE) {
+#pragma unroll
+		for (int i = 0; i < POSE_VP; i++) pose_v[i] = 0.f;
+	}
 
 	const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
 	const bool in_range = idx < p.P;
@@ -369,6 +398,11 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 				shx = ((+sum2 - ox * ox) * dLx - oy * ox * dLy - oz * ox * dLz) * invsum32;
 				shy = (-ox * oy * dLx + (sum2 - oy * oy) * dLy - oz * oy * dLz) * invsum32;
 				shz = (-ox * oz * dLx - oy * oz * dLy + (sum2 - oz * oz) * dLz) * invsum32;
+				if constexpr (POSE) {
+					pose_c[0] = -shx;
+					pose_c[1] = -shy;
+					pose_c[2] = -shz;
+				}
 			}
 			if (p.dL_dcolor_view && in_range) {
 				if (vis && dRGB[0] == 0.f && dRGB[1] == 0.f && dRGB[2] == 0.f) dRGB[0] = -0.0f;   // (visibility marker: sh_bwd_rows_kernel)
@@ -453,6 +487,18 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		gmx = V[0] * dL_dtx + V[1] * dL_dty + V[2] * dL_dtz;
 		gmy = V[4] * dL_dtx + V[5] * dL_dty + V[6] * dL_dtz;
 		gmz = V[8] * dL_dtx + V[9] * dL_dty + V[10] * dL_dtz;
+		const float xw[4] = {mx, my, mz, 1.f};
+		if constexpr (POSE) {
+			// t = W2C x: dL/dW(r, c) = dL/dt_r x_c; and the rotation block inside T = J W: dL/dW(r, c) += (J^T dL/dT)(r, c)
+			const float gt[3] = {dL_dtx, dL_dty, dL_dtz};
+#pragma unroll
+			for (int c = 0; c < 4; c++)
+#pragma unroll
+				for (int r = 0; r < 3; r++) pose_v[3 * c + r] = gt[r] * xw[c];
+			pose_v[0] += J00 * dL_dT00; pose_v[1] += J11 * dL_dT10; pose_v[2] += J02 * dL_dT00 + J12 * dL_dT10;
+			pose_v[3] += J00 * dL_dT01; pose_v[4] += J11 * dL_dT11; pose_v[5] += J02 * dL_dT01 + J12 * dL_dT11;
+			pose_v[6] += J00 * dL_dT02; pose_v[7] += J11 * dL_dT12; pose_v[8] += J02 * dL_dT02 + J12 * dL_dT12;
+		}
 
 		// ------------------------------------------------------------------ preprocessCUDA (bwd), backward.cu:346-396
 		{
@@ -464,6 +510,14 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 			gmx += (Pm[0] * m_w - Pm[3] * mul1) * g2x + (Pm[1] * m_w - Pm[3] * mul2) * g2y;
 			gmy += (Pm[4] * m_w - Pm[7] * mul1) * g2x + (Pm[5] * m_w - Pm[7] * mul2) * g2y;
 			gmz += (Pm[8] * m_w - Pm[11] * mul1) * g2x + (Pm[9] * m_w - Pm[11] * mul2) * g2y;
+			if constexpr (POSE) {
+				// hom = Proj x, pixel = hom.xy / (hom.w + 1e-7): dL/dhom, then dL/dProj(r, c) = dL/dhom_r x_c (hom.z is not used)
+				const float gh[3] = {m_w * g2x, m_w * g2y, -(mul1 * g2x + mul2 * g2y)};
+#pragma unroll
+				for (int c = 0; c < 4; c++)
+#pragma unroll
+					for (int k = 0; k < 3; k++) pose_v[12 + 3 * c + k] = gh[k] * xw[c];
+			}
 		}
 	}
 
@@ -554,6 +608,31 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		p.dL_dscale[3 * (size_t)idx + 1] = g_scale[1];
 		p.dL_dscale[3 * (size_t)idx + 2] = g_scale[2];
 		reinterpret_cast<float4*>(p.dL_drot)[idx] = dq;
+	}
+	if constexpr (POSE) {
+		const int l = lane_id(), w = wave_id();
+		float packed[3];
+		wave_reduce24_swap_f32(pose_v, packed);
+		if ((l & 7) == 0) {
+#pragma unroll
+			for (int j = 0; j < 3; j++) s_pose[w][8 * j + wave_swap9_component(l)] = packed[j];
+		}
+		if (!rows_ok) {
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				const float c = wave_sum_f32_lane63(pose_c[k]);
+				if (l == 63) s_pose[w][POSE_VP + k] = c;
+			}
+		}
+		__syncthreads();
+		// one slab entry per workgroup and sum: the waves in a fixed order
+		const int t = (int)threadIdx.x;
+		if (t < (rows_ok ? POSE_VP : POSE_VP + 3)) {
+			float sum = s_pose[0][t];
+#pragma unroll
+			for (int k = 1; k < PRB_THREADS / 64; k++) sum += s_pose[k][t];
+			p.pose_scratch[(size_t)t * gridDim.x + blockIdx.x] = sum;
+		}
 	}
 }
 
@@ -696,6 +775,57 @@ long_run_sums_kernel(const PreprocessBwdParams p)
 	}
 }
 
+// The pose slab -> the 35 outputs.  One workgroup per live sum (27): each thread adds its entries (t, t + 256, ...) in double, in
+// index order; the 256 partial sums meet in a binary tree through LDS; one rounding to float at the end.  The order depends on
+// nothing but the entry counts, so the same slab gives the same bits.  Workgroup 0 also writes the eight entries the render does
+// not depend on (row 3 of the view matrix, the z row of the projection).  Entry counts of zero (P == 0, no SH direction term)
+// give zeros.
+constexpr int POSE_SUM_THREADS = 256;
+__global__ void __launch_bounds__(POSE_SUM_THREADS)
+pose_final_sum_kernel(const float* __restrict__ slab, unsigned n_a, unsigned n_b, float* __restrict__ dL_dview, float* __restrict__ dL_dproj,
+                      float* __restrict__ dL_dcampos)
+{
+	__shared__ double s_sum[POSE_SUM_THREADS];
+	const int comp = (int)blockIdx.x, t = (int)threadIdx.x;
+	const bool vp = comp < POSE_VP;
+	const unsigned n = vp ? n_a : n_b;
+	const float* src = vp ? slab + (size_t)comp * n_a : slab + (size_t)POSE_VP * n_a + (size_t)(comp - POSE_VP) * n_b;
+	double acc = 0.0;
+	for (unsigned i = (unsigned)t; i < n; i += POSE_SUM_THREADS) acc += (double)src[i];
+	s_sum[t] = acc;
+	__syncthreads();
+	for (int half = POSE_SUM_THREADS / 2; half > 0; half >>= 1) {
+		if (t < half) s_sum[t] += s_sum[t + half];
+		__syncthreads();
+	}
+	if (t == 0) {
+		const float total = (float)s_sum[0];
+		if (comp < 12) {
+			dL_dview[4 * (comp / 3) + comp % 3] = total;
+		} else if (comp < POSE_VP) {
+			const int k = (comp - 12) % 3;
+			dL_dproj[4 * ((comp - 12) / 3) + (k == 2 ? 3 : k)] = total;
+		} else {
+			dL_dcampos[comp - POSE_VP] = total;
+		}
+	}
+	if (comp == 0 && t >= 1 && t <= 4) dL_dview[4 * (t - 1) + 3] = 0.f;
+	if (comp == 0 && t >= 5 && t <= 8) dL_dproj[4 * (t - 5) + 2] = 0.f;
+}
+
+static int launch_pose_final_sum(const float* slab, unsigned n_a, unsigned n_b, float* dL_dview, float* dL_dproj, float* dL_dcampos,
+                                 hipStream_t stream)
+{
+	GSR_LAUNCH(pose_final_sum_kernel, POSE_VP + 3, POSE_SUM_THREADS, stream, slab, n_a, n_b, dL_dview, dL_dproj, dL_dcampos);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+int launch_pose_zero(float* dL_dview, float* dL_dproj, float* dL_dcampos, hipStream_t stream)
+{
+	return launch_pose_final_sum(nullptr, 0u, 0u, dL_dview, dL_dproj, dL_dcampos, stream);
+}
+
 int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 {
 	if (p.partials && p.depth) GSR_LAUNCH(long_run_sums_kernel<true>, LRS_BLOCKS, 256, stream, p);
@@ -708,8 +838,13 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 	if (p.geom.on && !(rows_ok && p.D >= 0 && p.D <= 3 && p.scales && p.rotations && p.dL_dmean3D))
 		return GSR_ERR_UNSUPPORTED;   // the fused geometry step lives in the two-kernel path of the reference's SH layout
 	const int grid = div_up(p.P, PRB_THREADS);
+	const bool pose = p.pose_scratch != nullptr;
+	unsigned pose_b_rows = 0u;   // entries of the camera centre's sums in the pose slab (kernels.h)
+	if (pose && (factored || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // no pose gradients through the multi-GPU exchange
 	if (rows_ok && p.D >= 0 && p.D <= 3) {
-		if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, true, true>), grid, PRB_THREADS, stream, p);
+		if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, false, true, true>), grid, PRB_THREADS, stream, p);
+		else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<true, false, false, true>), grid, PRB_THREADS, stream, p);
+		else if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, true, true>), grid, PRB_THREADS, stream, p);
 		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<true, true>), grid, PRB_THREADS, stream, p);
 		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, false, true>), grid, PRB_THREADS, stream, p);
 		else GSR_LAUNCH(preprocess_bwd_kernel<true>, grid, PRB_THREADS, stream, p);
@@ -719,9 +854,14 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 			GSR_HIP(hipStreamWaitEvent((hipStream_t)p.notify_stream, (hipEvent_t)p.notify_event, 0));
 		}
 		const int g = div_up(p.P, SHB_THREADS);
+	// (POSE: the direction term vanishes at degree 0 -- the colour-only kernel runs and the camera centre's sums have no entries)
 #define GSR_SHB(DEG)                                                                  \
 	do {                                                                              \
-		if (factored)                                                                 \
+		if (pose && DEG > 0 && adam)                                                  \
+			GSR_LAUNCH((sh_bwd_rows_kernel<(DEG > 0 ? DEG : 1), 2, true>), g, SHB_THREADS, stream, p); \
+		else if (pose && DEG > 0)                                                     \
+			GSR_LAUNCH((sh_bwd_rows_kernel<(DEG > 0 ? DEG : 1), 0, true>), g, SHB_THREADS, stream, p); \
+		else if (factored)                                                                 \
 			GSR_LAUNCH((sh_bwd_rows_kernel<DEG, 1>), g, SHB_THREADS, stream, p);      \
 		else if (adam)                                                                \
 			GSR_LAUNCH((sh_bwd_rows_kernel<DEG, 2>), g, SHB_THREADS, stream, p);      \
@@ -737,8 +877,11 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 		else
 			GSR_SHB(0);
 #undef GSR_SHB
+		pose_b_rows = p.D > 0 ? (unsigned)g : 0u;
 	} else {
-		if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, true, true>), grid, PRB_THREADS, stream, p);
+		if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, false, true, true>), grid, PRB_THREADS, stream, p);
+		else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<false, false, false, true>), grid, PRB_THREADS, stream, p);
+		else if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, true, true>), grid, PRB_THREADS, stream, p);
 		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<false, true>), grid, PRB_THREADS, stream, p);
 		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, false, true>), grid, PRB_THREADS, stream, p);
 		else GSR_LAUNCH(preprocess_bwd_kernel<false>, grid, PRB_THREADS, stream, p);
@@ -746,8 +889,11 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 			GSR_HIP(hipEventRecord((hipEvent_t)p.notify_event, stream));
 			GSR_HIP(hipStreamWaitEvent((hipStream_t)p.notify_stream, (hipEvent_t)p.notify_event, 0));
 		}
+		// (the SH direction term, if any, was formed by preprocess_bwd_kernel: one camera-centre entry per workgroup of it)
+		pose_b_rows = (p.shs && p.D > 0) ? (unsigned)grid : 0u;
 	}
 	GSR_CHECK_LAUNCH();
+	if (pose) return launch_pose_final_sum(p.pose_scratch, (unsigned)grid, pose_b_rows, p.dL_dview, p.dL_dproj, p.dL_dcampos, stream);
 	return GSR_OK;
 }
 

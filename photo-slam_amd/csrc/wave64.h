@@ -331,6 +331,23 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 }
 #endif  // GSR_EMU
 
+// 24 full-wave sums in three registers (the camera pose gradient's view / projection products, preprocess_bwd.hip): three packed
+// butterflies of wave_reduce9_swap_f32, eight values each -- 3 x 15 VALU (the ninth's row sums are not asked for and fall away)
+// against 144 for 24 plain butterflies.  Every lane of the 8-lane group g holds in packed[j] the total of v[8 j + wave_swap9_component(lane)].
+// One source for the device and the emulator: it is built from primitives that have their twins above.
+__device__ __forceinline__ void wave_reduce24_swap_f32(const float (&v)[24], float (&packed)[3])
+{
+#pragma unroll
+	for (int j = 0; j < 3; j++) {
+		float t[9];
+#pragma unroll
+		for (int c = 0; c < 8; c++) t[c] = v[8 * j + c];
+		t[8] = 0.f;
+		float ninth;
+		wave_reduce9_swap_f32(t, packed[j], ninth);
+	}
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 __device__ __forceinline__ int wave_id() { return (int)(threadIdx.x >> 6); }
 __device__ __forceinline__ unsigned long long lanemask_lt()

@@ -70,11 +70,12 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
     return color, radii
 
 
-def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None):
-    """the backward of both autograd Functions: any subset of the image gradients (None = that image took no part in the loss;
-    a missing colour gradient next to a map's is zeros)"""
+def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None, pose=False):
+    """the backward of the autograd Functions: any subset of the image gradients (None = that image took no part in the loss;
+    a missing colour gradient next to a map's is zeros).  pose: the gradients of viewmatrix, projmatrix and campos follow the
+    eight of the Gaussians' inputs (GaussianRasterizerPoseFunction): twelve values"""
     if grad_out_color is None and grad_depth is None and grad_alpha is None:   # (set_materialize_grads(False)): no gradients
-        return (None,) * 9
+        return (None,) * (12 if pose else 9)
     s = ctx.raster_settings
     colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer = \
         ctx.saved_tensors
@@ -82,7 +83,7 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None):
         grad_out_color = torch.zeros((3, int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
     cont = lambda t: None if t is None else t.contiguous().float()
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-     dL_drotations) = rp.RasterizeGaussiansBackwardCUDA(
+     dL_drotations, *dL_dcamera) = rp.RasterizeGaussiansBackwardCUDA(
         s.bg_, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier_, cov3Ds_precomp, s.viewmatrix_,
         s.projmatrix_, s.tanfovx_, s.tanfovy_, grad_out_color, sh, s.sh_degree_, s.campos_, geomBuffer,
         ctx.num_rendered, binningBuffer, imgBuffer, s.raw_params_, s.sh_grad_view_,
@@ -90,12 +91,17 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None):
         # the forward pass (rows this view sees caught up) and lets backward run this step's slice of the rotating
         # catch-up next to the blend kernel
         s.sh_adam_ if (s.sh_grad_view_ is None or (s.sh_adam_ or {}).get("row_step") is not None) else None, s.view_stats_,
-        s.geom_adam_, s.training_outputs_only_, dL_ddepth=cont(grad_depth), dL_dalpha=cont(grad_alpha))
+        s.geom_adam_, s.training_outputs_only_, dL_ddepth=cont(grad_depth), dL_dalpha=cont(grad_alpha),
+        pose_grad=pose, workspace=s.workspace_ if pose else None)
     # order of src/gaussian_rasterizer.cpp:159-179
     def g(t, like):   # (None where an extension took the gradient's place)
         return t if like.numel() and t is not None else None
-    return (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity,
-            g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp), None)
+    grads = (dL_dmeans3D, dL_dmeans2D, g(dL_dsh, sh), g(dL_dcolors, colors_precomp), dL_dopacity,
+             g(dL_dscales, scales), g(dL_drotations, rotations), g(dL_dcov3D, cov3Ds_precomp))
+    if pose:
+        needs = ctx.needs_input_grad
+        return grads + tuple(t if needs[8 + k] else None for k, t in enumerate(dL_dcamera)) + (None,)
+    return grads + (None,)
 
 
 class GaussianRasterizerFunction(torch.autograd.Function):
@@ -126,6 +132,30 @@ class GaussianRasterizerDepthFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_depth, grad_alpha):
         return _backward(ctx, grad_out_color, grad_depth, grad_alpha)
+
+
+class GaussianRasterizerPoseFunction(torch.autograd.Function):
+    """The rasterizer with the camera as a differentiable input: viewmatrix, projmatrix and campos (the settings' three tensors,
+    passed as inputs so that their graph -- a pose built with torch ops, PoseDelta -- continues behind them) get the gradients of
+    gsr_backward_args.dL_dviewmatrix / dL_dprojmatrix / dL_dcampos.  GaussianRasterizer.forward takes this Function when one of
+    the three requires grad.  Returns (color, radii), with settings.render_depth_ (color, radii, depth, alpha)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, projmatrix,
+                campos, raster_settings):
+        s = raster_settings
+        if s.sh_grad_view_ is not None:
+            raise RuntimeError("camera gradients are not available through the view-factored exchange (sh_grad_view_)")
+        if not s.render_depth_:
+            return _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s)
+        depth = torch.zeros((int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
+        alpha = torch.zeros_like(depth)
+        color, radii = _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth, alpha)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
+        return _backward(ctx, grad_out_color, grad_depth, grad_alpha, pose=True)
 
 
 def _rasterize_forward_only(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s):
@@ -185,8 +215,13 @@ class GaussianRasterizer(torch.nn.Module):
         s = self.raster_settings_
         if s.forward_only_ or not torch.is_grad_enabled() or not any(
                 t is not None and t.requires_grad
-                for t in (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)):
+                for t in (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                          s.viewmatrix_, s.projmatrix_, s.campos_)):
             return _rasterize_forward_only(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, s)
+        if any(t is not None and t.requires_grad for t in (s.viewmatrix_, s.projmatrix_, s.campos_)):
+            # the camera is being differentiated (pose refinement): its three tensors enter as inputs
+            return GaussianRasterizerPoseFunction.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                        cov3D_precomp, s.viewmatrix_, s.projmatrix_, s.campos_, s)
         if s.render_depth_:   # (color, radii, depth, alpha)
             return GaussianRasterizerDepthFunction.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                          cov3D_precomp, s)

@@ -32,6 +32,56 @@ class GaussianKeyframe:
         return cls(cam.H, cam.W, cam.tanfovx, cam.tanfovy, t(cam.viewmatrix), t(cam.projmatrix), t(cam.campos))
 
 
+class PoseDelta:
+    """A keyframe pose under refinement: a fixed base W2C_0 and a 6-vector xi = (rho, theta), W2C = exp(xi^) W2C_0 (left
+    perturbation, exp = the matrix exponential of the 4x4 twist [[theta^, rho], [0, 0]]).  keyframe() builds the three tensors
+    the renderer consumes with torch ops, as the reference builds them (GaussianKeyframe::computeTransformTensors,
+    src/gaussian_keyframe.cpp:119-141): world_view_transform_ = W2C^T, full_proj_transform_ = view . projection_matrix_,
+    camera_center_ = inverse(view)[3, :3] -- so the rasterizer's camera gradients (GaussianRasterizerPoseFunction) chain back to
+    xi_ by autograd.  retract() folds xi into the base and zeroes it."""
+
+    def __init__(self, w2c, projection_matrix, image_height, image_width, tanfovx, tanfovy):
+        self.base_ = w2c.detach().clone().float()                            # [4,4] W2C_0 (not transposed)
+        self.projection_matrix_ = projection_matrix.detach().clone().float()  # [4,4] P^T, as the reference keeps it
+        self.xi_ = torch.zeros(6, dtype=torch.float32, device=self.base_.device, requires_grad=True)
+        self.image_height_, self.image_width_, self.tanfovx_, self.tanfovy_ = image_height, image_width, tanfovx, tanfovy
+
+    @classmethod
+    def from_keyframe(cls, kf):
+        """the pose of a GaussianKeyframe; its projection P^T = inverse(view) . full_proj (in double, rounded once)"""
+        view = kf.world_view_transform_.detach().double()
+        proj = torch.linalg.solve(view, kf.full_proj_transform_.detach().double()).float()
+        return cls(kf.world_view_transform_.detach().t(), proj, kf.image_height_, kf.image_width_, kf.tanfovx_, kf.tanfovy_)
+
+    @staticmethod
+    def exp(xi):
+        """exp(xi^) as a [4,4] matrix, differentiable at xi = 0"""
+        rho, th = xi[:3], xi[3:]
+        z = xi.new_zeros(())
+        twist = torch.stack([torch.stack([z, -th[2], th[1], rho[0]]), torch.stack([th[2], z, -th[0], rho[1]]),
+                             torch.stack([-th[1], th[0], z, rho[2]]), xi.new_zeros(4)])
+        return torch.linalg.matrix_exp(twist)
+
+    def w2c(self):
+        return PoseDelta.exp(self.xi_) @ self.base_
+
+    def keyframe(self):
+        view = self.w2c().t()
+        return GaussianKeyframe(self.image_height_, self.image_width_, self.tanfovx_, self.tanfovy_, view,
+                                view @ self.projection_matrix_, torch.linalg.inv(view)[3, :3])
+
+    def retract(self):
+        with torch.no_grad():
+            self.base_ = (PoseDelta.exp(self.xi_) @ self.base_).contiguous()
+            self.xi_.zero_()
+        return self.base_
+
+
+def pose_delta(kf):
+    """PoseDelta.from_keyframe"""
+    return PoseDelta.from_keyframe(kf)
+
+
 class GaussianRenderer:
     @staticmethod
     def render(viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color=None,

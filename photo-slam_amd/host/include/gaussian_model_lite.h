@@ -316,6 +316,16 @@ public:
 	// ... with the depth and alpha maps: (image, depth, alpha), [H,W] each (GaussianRenderer::renderWithDepth)
 	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf);
 	RasterWorkspace view_workspace_;
+	// Photometric refinement of one keyframe's pose against the FROZEN map: `iterations` Adam steps (betas 0.9 / 0.999, eps 1e-8,
+	// learning rates lr_translation for rho and lr_rotation for theta) on the xi of a PoseDelta (gaussian_renderer.h) started at
+	// viewpoint_cam, minimising the train step's loss -- fused L1 + lambda_dssim_ (1 - SSIM), plus the depth L1 loss with gt_depth
+	// when depth_loss_weight_ != 0.  The camera gradients come from the rasterizer's backward (gsr_backward_args.dL_dviewmatrix ...)
+	// and reach xi through the pose's construction by autograd.  The map's tensors enter detached, no optimizer or lazy-row state is
+	// touched (lazily stepped SH rows: a caught-up copy is rendered), and the render uses the second workspace as renderView does.
+	// Returns (the refined W2C [4,4], the loss of every iteration [iterations]).
+	std::tuple<torch::Tensor, torch::Tensor> refinePose(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image,
+	                                                    torch::Tensor mask, int iterations, double lr_translation, double lr_rotation,
+	                                                    torch::Tensor gt_depth = torch::Tensor());
 	GaussianRasterizationExtensions viewExtensions();   // what the two calls above hand to GaussianRenderer
 	bool early_gather_ = true;        // the exchange's all-gather waits for the colour gradients only, not for the whole backward pass
 	// The view-factored exchange in its PACKED form (include/gsr.h: gsr_pack_color_view): every rank sends only the rows its

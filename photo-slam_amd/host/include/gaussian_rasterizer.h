@@ -119,6 +119,22 @@ public:
 	                                             torch::autograd::tensor_list grad_out_color);
 };
 
+// The rasterizer with the camera as a differentiable input: viewmatrix, projmatrix and campos (the settings' three tensors, passed
+// as inputs so that their graph -- a pose built with torch ops, PoseDelta of gaussian_renderer.h -- continues behind them) get the
+// gradients of gsr_backward_args.dL_dviewmatrix / dL_dprojmatrix / dL_dcampos.  GaussianRasterizerEx takes this node when one of
+// the three requires grad; the reference-signature GaussianRasterizerFunction keeps its nine inputs and nine gradients.
+class GaussianRasterizerFunctionPose : public torch::autograd::Function<GaussianRasterizerFunctionPose> {
+public:
+	static torch::autograd::tensor_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor means3D,
+	                                            torch::Tensor means2D, torch::Tensor sh, torch::Tensor colors_precomp,
+	                                            torch::Tensor opacities, torch::Tensor scales, torch::Tensor rotations,
+	                                            torch::Tensor cov3Ds_precomp, torch::Tensor viewmatrix, torch::Tensor projmatrix,
+	                                            torch::Tensor campos, GaussianRasterizationSettings raster_settings,
+	                                            GaussianRasterizationExtensions extensions);
+	static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+	                                             torch::autograd::tensor_list grad_out_color);
+};
+
 // GaussianRasterizer with the extensions: same forward() contract and exception texts
 class GaussianRasterizerEx : public GaussianRasterizer {
 public:

@@ -61,6 +61,51 @@ bool lazy_view(Model&, ShAdamStep&, torch::Tensor&, long)
 }
 }  // namespace gsr_renderer_detail
 
+// A keyframe pose under refinement: a fixed base W2C_0 and a 6-vector xi = (rho, theta), W2C = exp(xi^) W2C_0 (left perturbation,
+// exp = the matrix exponential of the 4x4 twist [[theta^, rho], [0, 0]]).  apply() builds the three tensors render() consumes with
+// torch ops, as the reference builds them (GaussianKeyframe::computeTransformTensors, src/gaussian_keyframe.cpp:119-141):
+// world_view_transform_ = W2C^T, full_proj_transform_ = view . projection_matrix_, camera_center_ = inverse(view)[3, :3] -- so the
+// rasterizer's camera gradients (GaussianRasterizerFunctionPose) chain back to xi_ by autograd.  retract() folds xi into the base
+// and zeroes it.
+struct PoseDelta {
+	torch::Tensor base_;                // [4,4] W2C_0 (not transposed)
+	torch::Tensor projection_matrix_;   // [4,4] P^T, as the reference keeps it
+	torch::Tensor xi_;                  // [6] leaf, requires grad
+	// from a keyframe's world_view_transform_ and full_proj_transform_: P^T = inverse(view) . full_proj (in double, rounded once)
+	PoseDelta(const torch::Tensor& world_view_transform, const torch::Tensor& full_proj_transform)
+	{
+		torch::NoGradGuard ng;
+		auto view = world_view_transform.detach().to(torch::kFloat64);
+		projection_matrix_ = at::linalg_solve(view, full_proj_transform.detach().to(torch::kFloat64)).to(torch::kFloat32);
+		base_ = world_view_transform.detach().t().contiguous().to(torch::kFloat32).clone();
+		xi_ = torch::zeros({6}, base_.options()).set_requires_grad(true);
+	}
+	// exp(xi^) as a [4,4] matrix, differentiable at xi = 0
+	static torch::Tensor exp(const torch::Tensor& xi)
+	{
+		auto z = xi.new_zeros({});
+		auto row = [&](const torch::Tensor& a, const torch::Tensor& b, const torch::Tensor& c, const torch::Tensor& d) { return torch::stack({a, b, c, d}); };
+		auto twist = torch::stack({row(z, -xi[5], xi[4], xi[0]), row(xi[5], z, -xi[3], xi[1]), row(-xi[4], xi[3], z, xi[2]), xi.new_zeros({4})});
+		return at::linalg_matrix_exp(twist);
+	}
+	torch::Tensor w2c() const { return torch::matmul(exp(xi_), base_); }
+	template <class Keyframe>
+	void apply(Keyframe& kf) const
+	{
+		auto view = w2c().t();
+		kf.world_view_transform_ = view;
+		kf.full_proj_transform_ = torch::matmul(view, projection_matrix_);
+		kf.camera_center_ = torch::inverse(view)[3].slice(0, 0, 3);
+	}
+	torch::Tensor retract()
+	{
+		torch::NoGradGuard ng;
+		base_ = torch::matmul(exp(xi_), base_).contiguous();
+		xi_.zero_();
+		return base_;
+	}
+};
+
 class GaussianRenderer {
 public:
 	// returns (render, viewspace_points, visibility_filter, radii).  The reference's parameters, then this repository's

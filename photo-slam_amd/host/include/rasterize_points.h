@@ -47,6 +47,14 @@ struct GeomAdamStep {
 // every new largest size is a hipMalloc of a gigabyte -- up to 45 ms on the pool's boxes, profiles/r06_w*).
 struct RasterWorkspace {
 	torch::Tensor geom, binning, img;
+	torch::Tensor pose;   // the scratch of the pose gradients' sums (gsr_backward_args.pose_scratch): refinePose allocates nothing per iteration
+};
+
+// Extension: the gradients of the loss with respect to the camera -- viewmatrix [4,4], projmatrix [4,4], campos [3] as the kernels
+// use them, treated as three independent inputs (gsr_backward_args.dL_dviewmatrix / dL_dprojmatrix / dL_dcampos).  Filled by
+// RasterizeGaussiansBackwardCUDA when RasterBackwardExtensions::pose_grad points at one: its results next to the tuple of eight.
+struct PoseGradients {
+	torch::Tensor dL_dviewmatrix, dL_dprojmatrix, dL_dcampos;
 };
 
 // What this repository adds to the reference's forward parameter list.  The pointers are read during the call only.
@@ -84,6 +92,10 @@ struct RasterBackwardExtensions {
 	// packViewPlan() fills between the forward and the backward pass; backward writes rows and header next to dL_dcolor_view
 	torch::Tensor packed_view;
 	int64_t packed_capacity = 0;
+	// the camera pose gradients: non-null = requested, filled by the call (zeros for P == 0).  Not together with dL_dcolor_view.
+	// workspace: when given, it owns the scratch of the sums (otherwise allocated per call)
+	PoseGradients* pose_grad = nullptr;
+	RasterWorkspace* workspace = nullptr;
 };
 
 // (num_rendered, out_color[3,H,W], radii[P] i32, geomBuffer u8, binningBuffer u8, imgBuffer u8)

@@ -74,15 +74,17 @@ torch::autograd::tensor_list forward_impl(torch::autograd::AutogradContext* ctx,
 }
 
 // n_extra: undefined gradients for the trailing non-tensor inputs (raster_settings [, extensions])
+// pose: the gradients of viewmatrix, projmatrix and campos follow the eight (GaussianRasterizerFunctionPose)
 torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx, torch::autograd::tensor_list grad_outputs,
-                                           int n_extra)
+                                           int n_extra, bool pose = false)
 {
+	const int n_camera = pose ? 3 : 0;
 	// render_depth_: (color, radii, depth, alpha) -- the gradients of the two maps, either undefined (not in the loss)
 	const torch::Tensor dL_ddepth = grad_outputs.size() > 2 ? grad_outputs[2] : torch::Tensor();
 	const torch::Tensor dL_dalpha = grad_outputs.size() > 3 ? grad_outputs[3] : torch::Tensor();
 	// no image took part in the loss (set_materialize_grads(false)): no gradients
 	if (!grad_outputs[0].defined() && !dL_ddepth.defined() && !dL_dalpha.defined()) {
-		torch::autograd::tensor_list none(static_cast<size_t>(8 + n_extra));
+		torch::autograd::tensor_list none(static_cast<size_t>(8 + n_camera + n_extra));
 		return none;
 	}
 	const auto state = c10::static_intrusive_pointer_cast<SavedState>(ctx->saved_data["state"].toCapsule());
@@ -106,6 +108,11 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 	b.color_view_ready_stream = e.color_view_ready_stream_;
 	b.packed_view = e.packed_view_;
 	b.packed_capacity = e.packed_capacity_;
+	PoseGradients camera;
+	if (pose) {
+		b.pose_grad = &camera;
+		b.workspace = e.workspace_;
+	}
 	auto v = ctx->get_saved_variables();
 	auto g = RasterizeGaussiansBackwardCUDA(v[0] /*bg*/, v[5] /*means3D*/, v[9] /*radii*/, v[4] /*colors_precomp*/,
 	                                        v[6] /*scales*/, v[7] /*rotations*/, s.scale_modifier_, v[8] /*cov3Ds*/,
@@ -124,6 +131,11 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 	                                    opt(std::get<6>(g), v[6]) /*scales*/,
 	                                    opt(std::get<7>(g), v[7]) /*rotations*/,
 	                                    opt(std::get<4>(g), v[8]) /*cov3Ds_precomp*/};
+	if (pose) {
+		out.push_back(camera.dL_dviewmatrix);
+		out.push_back(camera.dL_dprojmatrix);
+		out.push_back(camera.dL_dcampos);
+	}
 	for (int i = 0; i < n_extra; i++) out.push_back(torch::Tensor());
 	return out;
 }
@@ -169,8 +181,11 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> rasterize
 	const GaussianRasterizationExtensions& e = ext ? *ext : none;
 	// forward_only_, or a render no backward pass can follow (NoGradGuard, or nothing to differentiate): the forward pass alone
 	// (GSR_FORWARD_ONLY) -- RasterizeGaussiansCUDA directly with the bit, no autograd node, no buffers kept
+	// (the camera counts only where a node exists that differentiates it: the reference-signature rasterizer, ext == nullptr, has
+	// none -- GaussianRasterizerFunction keeps its nine inputs -- and decides as before)
+	const bool camera_grad = ext && !no_backward({&s.viewmatrix_, &s.projmatrix_, &s.campos_});
 	if (e.forward_only_ ||
-	    no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp})) {
+	    (!camera_grad && no_backward({&means3D, &means2D, &shs, &colors_precomp, &opacities, &scales, &rotations, &cov3D_precomp}))) {
 		torch::NoGradGuard no_grad;
 		torch::Tensor depth, alpha;
 		if (with_depth) {
@@ -181,6 +196,17 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> rasterize
 		auto r = rasterize_forward(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, s, e, GSR_FORWARD_ONLY,
 		                           depth, alpha);
 		return std::make_tuple(std::get<1>(r), std::get<2>(r), depth, alpha);
+	}
+	// the camera is being differentiated (pose refinement): its three tensors enter the node as inputs
+	if (camera_grad) {
+		if (e.sh_grad_view_.defined())
+			throw std::runtime_error("camera gradients are not available through the view-factored exchange (sh_grad_view_)");
+		GaussianRasterizationExtensions node_ext = e;
+		if (with_depth) node_ext.render_depth_ = true;
+		auto result = GaussianRasterizerFunctionPose::apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+		                                                    cov3D_precomp, s.viewmatrix_, s.projmatrix_, s.campos_, s, std::move(node_ext));
+		if (!with_depth) return std::make_tuple(result[0], result[1], torch::Tensor(), torch::Tensor());
+		return std::make_tuple(result[0], result[1], result[2], result[3]);
 	}
 	if (!ext) {
 		auto result = rasterizeGaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, s);
@@ -225,6 +251,24 @@ torch::autograd::tensor_list GaussianRasterizerFunctionEx::backward(torch::autog
                                                                     torch::autograd::tensor_list grad_outputs)
 {
 	return backward_impl(ctx, grad_outputs, 2);
+}
+
+torch::autograd::tensor_list GaussianRasterizerFunctionPose::forward(
+    torch::autograd::AutogradContext* ctx, torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh,
+    torch::Tensor colors_precomp, torch::Tensor opacities, torch::Tensor scales, torch::Tensor rotations,
+    torch::Tensor cov3Ds_precomp, torch::Tensor viewmatrix, torch::Tensor projmatrix, torch::Tensor campos,
+    GaussianRasterizationSettings s, GaussianRasterizationExtensions e)
+{
+	(void)means2D;
+	// (the values come from the settings, which hold the same three tensors; as inputs they give the node its edges)
+	(void)viewmatrix; (void)projmatrix; (void)campos;
+	return forward_impl(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, std::move(s), std::move(e));
+}
+
+torch::autograd::tensor_list GaussianRasterizerFunctionPose::backward(torch::autograd::AutogradContext* ctx,
+                                                                      torch::autograd::tensor_list grad_outputs)
+{
+	return backward_impl(ctx, grad_outputs, 2, true);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> GaussianRasterizer::forward(

@@ -196,6 +196,52 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> trainer_render_view_dept
 {
 	return get(h)->renderViewWithDepth(make_kf(view, proj, campos, fovx, fovy, H, W));
 }
+// TrainStep::refinePose: (the refined W2C [4,4], the loss per iteration); gt_depth with no elements = none
+std::tuple<torch::Tensor, torch::Tensor> trainer_refine_pose(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos,
+                                                             double fovx, double fovy, int64_t H, int64_t W, torch::Tensor gt,
+                                                             torch::Tensor mask, int64_t iterations, double lr_translation,
+                                                             double lr_rotation, torch::Tensor gt_depth)
+{
+	return get(h)->refinePose(make_kf(view, proj, campos, fovx, fovy, H, W), gt, mask, (int)iterations, lr_translation, lr_rotation,
+	                          gt_depth.numel() ? gt_depth : torch::Tensor());
+}
+// every tensor a refinement must leave alone: the five leaves as they are, their Adam moments, the lazy rows' counters, the
+// training workspace
+std::vector<torch::Tensor> trainer_state(int64_t h)
+{
+	auto t = get(h);
+	std::vector<torch::Tensor> out = t->gaussians_->paramsRaw();
+	for (auto& grp : t->gaussians_->groups_) {
+		out.push_back(grp.exp_avg);
+		out.push_back(grp.exp_avg_sq);
+	}
+	if (t->gaussians_->features_row_step_.defined()) out.push_back(t->gaussians_->features_row_step_);
+	for (const torch::Tensor* b : {&t->workspace_.geom, &t->workspace_.binning, &t->workspace_.img})
+		if (b->defined()) out.push_back(*b);
+	return out;
+}
+// the camera gradients of a loss <dL_dpix, image> through GaussianRasterizerEx with a PoseDelta at xi = 0 on the trainer's model:
+// dL/dxi [6] (the autograd route of the C++ host)
+torch::Tensor trainer_pose_gradient(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx, double fovy,
+                                    int64_t H, int64_t W, torch::Tensor dL_dpix)
+{
+	auto t = get(h);
+	auto kf = make_kf(view, proj, campos, fovx, fovy, H, W);
+	PoseDelta pose(kf->world_view_transform_, kf->full_proj_transform_);
+	pose.apply(*kf);
+	torch::Tensor override_color;
+	GaussianRasterizationExtensions ext;
+	ext.raw_params_ = 7;
+	// (the map frozen for this render: only the camera requires grad)
+	auto frozen = t->gaussians_;
+	std::vector<bool> was;
+	for (auto& p : frozen->paramsRaw()) { was.push_back(p.requires_grad()); p.set_requires_grad(false); }
+	auto pkg = GaussianRenderer::render(kf, (int)H, (int)W, frozen, t->pipe_, t->background_, override_color, 1.0f, false, ext);
+	auto leaves = frozen->paramsRaw();
+	for (size_t i = 0; i < leaves.size(); i++) leaves[i].set_requires_grad(was[i]);
+	TORCH_CHECK(std::get<0>(pkg).requires_grad(), "a render in which only the camera requires grad must take the training path");
+	return torch::autograd::grad({(std::get<0>(pkg) * dL_dpix).sum()}, {pose.xi_})[0];
+}
 void trainer_finish(int64_t h) { get(h)->finishOneIteration(); }
 void trainer_finish_begin(int64_t h) { get(h)->finishBegin(); }
 void trainer_adam_group(int64_t h, int64_t group) { get(h)->finishAdamGroup(static_cast<int>(group)); }
@@ -249,6 +295,7 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "opacity_reset_interval") p.opacity_reset_interval_ = (int)v;
 		else if (k == "densify_grad_threshold") p.densify_grad_threshold_ = (float)v;
 		else if (k == "percent_dense") p.percent_dense_ = (float)v;
+		else if (k == "lambda_dssim") p.lambda_dssim_ = (float)v;
 		else TORCH_CHECK(false, "unknown trainer option: ", k);
 	}
 }
@@ -476,6 +523,9 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("trainer_adam_group", &trainer_adam_group);
 	m.def("trainer_finish_end", &trainer_finish_end);
 	m.def("trainer_params", &trainer_params);
+	m.def("trainer_refine_pose", &trainer_refine_pose);
+	m.def("trainer_state", &trainer_state);
+	m.def("trainer_pose_gradient", &trainer_pose_gradient);
 	m.def("trainer_grads", &trainer_grads);
 	m.def("trainer_stats", &trainer_stats);
 	m.def("trainer_create_from_pcd", &trainer_create_from_pcd);

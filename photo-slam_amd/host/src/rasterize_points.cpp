@@ -304,6 +304,12 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 		dL_dscales.zero_();
 		dL_drotations.zero_();
 	}
+	// the camera pose gradients: ONE buffer of 35 floats (view, projection, centre), written whole by gsr_backward
+	torch::Tensor pose, pose_scratch;
+	if (ext.pose_grad) {
+		if (factored) throw std::runtime_error("pose_grad is not available through the view-factored exchange (dL_dcolor_view)");
+		pose = P != 0 ? torch::empty({35}, o) : torch::zeros({35}, o);
+	}
 
 	if (P != 0) {
 		F32 bg(background), m3(means3D), col(colors), sc(scales), rot(rotations), cov(cov3D_precomp), view(viewmatrix),
@@ -387,7 +393,28 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 			ga.beta1 = geom_adam.beta1; ga.beta2 = geom_adam.beta2; ga.eps = geom_adam.eps;
 			a.geom_adam = &ga;
 		}
+		if (ext.pose_grad) {
+			const size_t bytes = gsr_pose_grad_scratch_bytes(P);
+			if (ext.workspace) {
+				torch::Tensor& ws = ext.workspace->pose;
+				if (!ws.defined() || ws.device() != means3D.device() || ws.scalar_type() != torch::kByte) ws = torch::empty({0}, means3D.options().dtype(torch::kByte));
+				grow_tensor(&ws, bytes);
+				pose_scratch = ws;
+			} else {
+				pose_scratch = torch::empty({static_cast<int64_t>(bytes)}, means3D.options().dtype(torch::kByte));
+			}
+			a.dL_dviewmatrix = pose.data_ptr<float>();
+			a.dL_dprojmatrix = a.dL_dviewmatrix + 16;
+			a.dL_dcampos = a.dL_dviewmatrix + 32;
+			a.pose_scratch = reinterpret_cast<char*>(pose_scratch.data_ptr());
+		}
 		check(gsr_backward(&a, current_stream(means3D)), "RasterizeGaussiansBackwardCUDA");
+	}
+	if (ext.pose_grad) {
+		// (the [16] arrays hold element (r, c) at [4c + r]: exactly the row-major [4,4] tensors the host passes in)
+		ext.pose_grad->dL_dviewmatrix = pose.narrow(0, 0, 16).view({4, 4});
+		ext.pose_grad->dL_dprojmatrix = pose.narrow(0, 16, 16).view({4, 4});
+		ext.pose_grad->dL_dcampos = pose.narrow(0, 32, 3);
 	}
 	if (geom) dL_dmeans3D = torch::Tensor();   // (was scratch)
 	return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,

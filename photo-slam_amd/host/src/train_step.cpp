@@ -218,6 +218,90 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::renderViewWit
 	return std::make_tuple(std::get<0>(pkg), std::get<4>(pkg), std::get<5>(pkg));
 }
 
+namespace {
+// the frozen map of refinePose: exactly the members GaussianRenderer::render touches, detached tensors
+struct FrozenModel {
+	torch::Tensor xyz_, features_, opacity_, scaling_, rotation_;
+	int active_sh_degree_ = 0, max_sh_degree_ = 0;
+	torch::Tensor getXYZ() { return xyz_; }
+	torch::Tensor getFeatures() { return features_; }
+	torch::Tensor getOpacityActivation() { return torch::sigmoid(opacity_); }
+	torch::Tensor getScalingActivation() { return torch::exp(scaling_); }
+	torch::Tensor getRotationActivation() { return torch::nn::functional::normalize(rotation_); }
+	torch::Tensor getCovarianceActivation() { throw std::runtime_error("refinePose renders the raw model (compute_cov3D_ must be off)"); }
+};
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor> TrainStep::refinePose(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image,
+                                                              torch::Tensor mask, int iterations, double lr_translation,
+                                                              double lr_rotation, torch::Tensor gt_depth)
+{
+	if (pipe_.convert_SHs_ || pipe_.compute_cov3D_)
+		throw std::runtime_error("refinePose renders the raw model (convert_SHs_ / compute_cov3D_ must be off)");
+	const bool use_depth = usesDepthLoss(gt_depth);
+	auto& g = gaussians_;
+	auto frozen = std::make_shared<FrozenModel>();
+	frozen->xyz_ = g->xyz_.detach();
+	frozen->opacity_ = g->opacity_.detach();
+	frozen->scaling_ = g->scaling_.detach();
+	frozen->rotation_ = g->rotation_.detach();
+	frozen->features_ = g->features_.detach();
+	frozen->active_sh_degree_ = g->active_sh_degree_;
+	frozen->max_sh_degree_ = g->max_sh_degree_;
+	if (g->features_row_step_.defined() && !g->features_lr_hist_.empty() && g->groups_.size() > 1) {
+		// lazily stepped SH rows: the zero-gradient steps the rows are behind are taken on COPIES (one copy per call, nothing per
+		// iteration) -- neither the tensor, its moments nor row_step change
+		torch::NoGradGuard ng;
+		ShAdamStep s = g->featuresAdamStep(GaussianModel::ShStep::LazyTaken);
+		s.exp_avg = s.exp_avg.clone();
+		s.exp_avg_sq = s.exp_avg_sq.clone();
+		s.row_step = s.row_step.clone();
+		frozen->features_ = frozen->features_.clone();
+		shAdamFlush(frozen->features_, s);
+	}
+	PoseDelta pose(viewpoint_cam->world_view_transform_, viewpoint_cam->full_proj_transform_);
+	auto kf = std::make_shared<GaussianKeyframe>(*viewpoint_cam);
+	const auto opts = pose.xi_.options().requires_grad(false);
+	auto lr = torch::cat({torch::full({3}, lr_translation, opts), torch::full({3}, lr_rotation, opts)});
+	auto m = torch::zeros({6}, opts), v = torch::zeros({6}, opts);
+	const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
+	torch::Tensor eff_mask = mask;
+	if (mask.defined() && mask.numel() && (mask == 1).all().item<bool>()) eff_mask = torch::empty({0}, mask.options());
+	GaussianRasterizationExtensions ext;
+	ext.raw_params_ = 7;
+	ext.cull_empty_tiles_ = cull_empty_tiles_;
+	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
+	std::vector<torch::Tensor> losses;
+	torch::Tensor override_color;
+	for (int it = 1; it <= iterations; it++) {
+		pose.apply(*kf);
+		torch::Tensor rendered, depth;
+		if (use_depth) {
+			auto pkg = GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, frozen, pipe_, background_,
+			                                             override_color, 1.0f, false, ext);
+			rendered = std::get<0>(pkg);
+			depth = std::get<4>(pkg);
+		} else {
+			auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, frozen, pipe_, background_, override_color, 1.0f,
+			                                    false, ext);
+			rendered = std::get<0>(pkg);
+		}
+		auto loss = fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
+		if (use_depth) loss = loss + loss_utils::depth_l1(depth, gt_depth, depth_loss_weight_, depth_min_, depth_max_);
+		auto grad = torch::autograd::grad({loss}, {pose.xi_})[0];
+		{
+			torch::NoGradGuard ng;
+			m.mul_(b1).add_(grad, 1.0 - b1);
+			v.mul_(b2).addcmul_(grad, grad, 1.0 - b2);
+			auto step = lr / (1.0 - std::pow(b1, it));
+			pose.xi_.sub_(step * m / (v.sqrt() / std::sqrt(1.0 - std::pow(b2, it)) + eps));
+		}
+		losses.push_back(loss.detach());
+	}
+	auto w2c = pose.retract();
+	return std::make_tuple(w2c, losses.empty() ? torch::zeros({0}, opts) : torch::stack(losses));
+}
+
 torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
                                            torch::Tensor gt_depth)
 {

@@ -85,6 +85,14 @@ class RasterWorkspace:
 
     def __init__(self):
         self.bufs = [None, None, None]   # geometry, binning, image
+        self.pose = None                 # the pose gradients' scratch (gsr_backward_args.pose_scratch): refinePose allocates nothing per iteration
+
+    def pose_scratch(self, nbytes, dev):
+        b = self.pose
+        if b is None or b.device != dev or b.numel() < int(nbytes):
+            self.pose = b = None
+            self.pose = b = torch.empty((int(nbytes) + int(nbytes) // 2,), dtype=torch.uint8, device=dev)
+        return b
 
     def taker(self, i, dev):
         def fn(_ctx, nbytes):
@@ -173,7 +181,7 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                                    viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                    geomBuffer, R, binningBuffer, imageBuffer, raw_params=0, dL_dcolor_view=None, sh_adam=None,
                                    view_stats=None, geom_adam=None, training_outputs_only=False, packed_view=None,
-                                   dL_ddepth=None, dL_dalpha=None):
+                                   dL_ddepth=None, dL_dalpha=None, pose_grad=False, workspace=None):
     """dL_dcolor_view (extension, default None = reference contract): a [P,3] float tensor that receives the clamp-masked
     colour gradient; dL_dsh is then NOT computed and None is returned in its place (view-factored gradient exchange,
     shGradFromViews below).
@@ -190,7 +198,11 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
     fuses the densification statistics (view_stats: the only consumer of dL_dmeans2D in a train step) and optimises scales /
     rotations (no cov3D_precomp).
     dL_ddepth / dL_dalpha (extension, default None): [H, W] upstream gradients of the forward pass's out_depth / out_alpha
-    (gsr_backward_args.dL_ddepth / dL_dalpha); either may be None.  The forward pass need not have rendered the maps."""
+    (gsr_backward_args.dL_ddepth / dL_dalpha); either may be None.  The forward pass need not have rendered the maps.
+    pose_grad (extension, default False): the gradients with respect to viewmatrix [4,4], projmatrix [4,4] and campos [3] -- the
+    three inputs as the kernels use them, treated as independent (gsr_backward_args.dL_dviewmatrix ...) -- are returned behind
+    the eight of the reference: a tuple of eleven.  Not together with dL_dcolor_view.  workspace: a RasterWorkspace that then
+    owns the scratch of the sums (otherwise allocated per call)."""
     lib = _lib()
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
@@ -224,6 +236,10 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                      not dL_dcolor_view.is_contiguous() or dL_dcolor_view.device != dev):
         raise RuntimeError("dL_dcolor_view must be a contiguous float32 (num_points, 3) tensor on the device of means3D")
     dL_dsh = None if factored or sh_adam is not None else torch.empty((P, M, 3), **opts)
+    if pose_grad:
+        if factored:
+            raise RuntimeError("pose_grad is not available through the view-factored exchange (dL_dcolor_view)")
+        pose = torch.zeros((35,), **opts) if P == 0 else torch.empty((35,), **opts)
     if P != 0:
         keep = []
         a = capi.BackwardArgs()
@@ -278,6 +294,11 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
             ga = capi.make_geom_adam(geom_adam)
             a.geom_adam = C.pointer(ga)
             a.dL_dopacity = a.dL_dscale = a.dL_drot = None
+        if pose_grad:
+            lib_bytes = int(lib.gsr_pose_grad_scratch_bytes(P))
+            pose_scratch = workspace.pose_scratch(lib_bytes, dev) if workspace is not None else torch.empty((lib_bytes,), dtype=torch.uint8, device=dev)
+            a.dL_dviewmatrix, a.dL_dprojmatrix, a.dL_dcampos = pose.data_ptr(), pose.data_ptr() + 64, pose.data_ptr() + 128
+            a.pose_scratch = pose_scratch.data_ptr()
         st = lib.gsr_backward(C.byref(a), _stream_ptr(means3D))
         capi.check(lib, st, "RasterizeGaussiansBackwardCUDA")
         if not has_sh and dL_dsh is not None:
@@ -289,7 +310,11 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
         dL_dmeans2D = dL_dcov3D = None
     if geom_adam is not None:
         dL_dopacity = dL_dmeans3D = dL_dscales = dL_drotations = None
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
+    if pose_grad:
+        # (the [16] arrays hold element (r, c) at [4c + r]: exactly the row-major [4,4] tensors the host passes in)
+        out += (pose[0:16].view(4, 4), pose[16:32].view(4, 4), pose[32:35])
+    return out
 
 
 def _views_args(means3D, campos_views, dL_dcolor_views):

@@ -3,6 +3,8 @@ without the SLAM keyframe scheduling -- render -> mask -> L1 + lambda*(1-SSIM) -
 densification statistics -> Adam -- plus the keyframe-batch data parallelism of SURVEY.md 8(e):
 one keyframe per rank, mean of the five leaf gradients over the ranks (ViewFactoredExchange, or the plain
 all-reduce of GradientReduction), SUM/MAX of the statistics."""
+import os
+
 import torch
 import torch.distributed as dist
 
@@ -259,6 +261,69 @@ class TrainStep:
         if with_depth:
             return out[0], out[4], out[5]
         return out[0]
+
+    def _frozen_map(self):
+        """The model's tensors for a render that must not touch the model (refinePose): detached, and with lazily stepped SH rows
+        a caught-up COPY of the SH tensor (the zero-gradient steps the rows are behind, taken on clones: neither the tensor, its
+        moments nor row_step change).  One copy per call, nothing per iteration."""
+        g = self.gaussians_
+        sh = g._features.detach()
+        o = g.optimizer_
+        st = o.state.get(id(g._features)) if o is not None else None
+        if st is not None and "row_step" in st and st["lr_hist"]:
+            hist = st["lr_hist"]
+            sh = sh.clone()
+            from . import rasterize_points as rp_
+            rp_.shAdamFlush(sh, dict(exp_avg=st["exp_avg"].clone(), exp_avg_sq=st["exp_avg_sq"].clone(), lr=hist[0][0], lr_tail=hist[0][1],
+                                     beta1=o.betas[0], beta2=o.betas[1], eps=o.eps, step=st["step"], row_step=st["row_step"].clone(),
+                                     window=st["window"], lr_past=[a for a, _ in hist[1:]], lr_tail_past=[b for _, b in hist[1:]]))
+        return g.xyz_.detach(), sh, g.opacity_.detach(), g.scaling_.detach(), g.rotation_.detach()
+
+    def refinePose(self, viewpoint_cam, gt_image, mask, iterations, lr_translation, lr_rotation, gt_depth=None):
+        """Photometric refinement of one keyframe's pose against the frozen map: `iterations` Adam steps (betas 0.9 / 0.999,
+        eps 1e-8, learning rates lr_translation for rho and lr_rotation for theta) on the xi of a PoseDelta started at
+        viewpoint_cam, minimising the train step's loss -- fused L1 + lambda_dssim_ (1 - SSIM), plus depth_l1_loss with gt_depth
+        when depth_loss_weight_ != 0.  The camera gradients come from the rasterizer's backward (gsr_backward_args.dL_dviewmatrix
+        ...) and reach xi through the pose's construction by autograd.  The map is frozen: its tensors enter detached, no
+        optimizer or lazy-row state is touched, and the render uses the second workspace, as render_view does -- a refinement
+        between a training forward and its backward disturbs nothing.  Returns (W2C [4,4], [loss per iteration])."""
+        from .gaussian_rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+        from .gaussian_renderer import PoseDelta
+        from . import capi
+        use_depth = gt_depth is not None and self.depth_loss_weight_ != 0.0
+        g, opt = self.gaussians_, self.opt_
+        if self.pipe_.convert_SHs_ or self.pipe_.compute_cov3D_:
+            raise RuntimeError("refinePose renders the raw model (convert_SHs_ / compute_cov3D_ must be off)")
+        xyz, sh, opacity, scaling, rotation = self._frozen_map()
+        pose = PoseDelta.from_keyframe(viewpoint_cam)
+        dev = xyz.device
+        lr = torch.tensor([lr_translation] * 3 + [lr_rotation] * 3, dtype=torch.float32, device=dev)
+        m, v = torch.zeros(6, device=dev), torch.zeros(6, device=dev)
+        b1, b2, eps = 0.9, 0.999, 1e-8
+        env = os.environ.get("GSR_CULL_EMPTY_TILES")
+        cull = (env == "1") if env else self.cull_empty_tiles_
+        means2D = torch.zeros_like(xyz)
+        eff_mask = self._effective_mask(mask)
+        losses = []
+        for it in range(1, int(iterations) + 1):
+            kf = pose.keyframe()
+            s = GaussianRasterizationSettings(
+                kf.image_height_, kf.image_width_, kf.tanfovx_, kf.tanfovy_, self.background_, 1.0, kf.world_view_transform_,
+                kf.full_proj_transform_, g.active_sh_degree_, kf.camera_center_, False, 7, cull_empty_tiles_=cull,
+                workspace_=self.view_workspace_ if self.persistent_workspace_ else None, render_depth_=use_depth)
+            out = GaussianRasterizer(s)(xyz, means2D, opacity, True, False, True, True, False, sh, None, scaling, rotation, None)
+            loss = loss_utils.fused_l1_ssim_loss(out[0], gt_image, eff_mask, opt.lambda_dssim_, is_root=True)
+            if use_depth:
+                loss = loss + loss_utils.depth_l1_loss(out[2], gt_depth, self.depth_loss_weight_, self.depth_min_, self.depth_max_)
+            (grad,) = torch.autograd.grad(loss, pose.xi_)
+            with torch.no_grad():
+                m.mul_(b1).add_(grad, alpha=1 - b1)
+                v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
+                step = lr / (1 - b1 ** it)
+                pose.xi_.sub_(step * m / (v.sqrt() / (1 - b2 ** it) ** 0.5 + eps))
+            losses.append(loss.detach())
+        w2c = pose.retract()
+        return w2c, [float(x) for x in torch.stack(losses).cpu()] if losses else []
 
     def _effective_mask(self, mask):
         """rendered * mask with a mask of ones is the identity (src/gaussian_mapper.cpp:692-693; most keyframes carry a full
