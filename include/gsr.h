@@ -189,6 +189,30 @@ typedef struct gsr_forward_args {
  * caller whose tensor has taken S steps passes step = S + 1 and lr_past[0] = the learning rates of step S: the image is then
  * the one a training forward renders after gsr_sh_adam_flush. */
 #define GSR_FORWARD_ONLY 128
+/* ... and one that changes what is rendered (read by gsr_forward AND gsr_backward: it must be the same in both calls, like the
+ * GSR_RAW_* bits; gsr_backward refuses, with GSR_ERR_INVALID_ARG, the geometry buffer of the calling thread's last training forward
+ * when the bit differs).  ANTI-ALIASED rendering: the reference adds 0.3 to the diagonal of every projected 2-D covariance
+ * (computeCov2D, forward.cu:74-113) and leaves the opacity alone, so a Gaussian smaller than a pixel deposits
+ * sqrt(det(Sigma + 0.3 I) / det Sigma) times the alpha it should -- a factor that depends on the resolution of the render.  With
+ * this bit the opacity is compensated (the 2-D filter normalisation of Mip-Splatting; `antialiasing` of upstream
+ * diff-gaussian-rasterization, rasterize_mode="antialiased" of gsplat).  With Sigma = (a b; b c) the projected covariance BEFORE
+ * the low-pass:
+ *   h = sqrt(max(0.000025, det Sigma / det(Sigma + 0.3 I)))      the opacity every later stage uses = opacity_activated * h
+ * in float32, every operation rounded on its own (no contraction), in this order:
+ *   a1 = a + 0.3f;  c1 = c + 0.3f;  det1 = a1 * c1 - b * b      (the determinant the conic is formed from)
+ *   det0 = a * c - b * b;  h2 = fmaxf(0.000025f, det0 / det1);  h = sqrtf(h2);  opacity = opacity_activated * h
+ * (a, b, c in the operation order of computeCov2D; opacity_activated = the input, or its sigmoid under GSR_RAW_OPACITY).
+ * Unchanged by the bit: the conic, the 3-sigma radius, the tile rectangle, radii, the sort keys, the lists and *num_rendered --
+ * all those of Sigma + 0.3 I, bit for bit; only the opacity of the blend record differs, and the blend kernels, the bound of
+ * GSR_CULL_EMPTY_TILES and out_depth / out_alpha all read that value.
+ * gsr_backward: dL_dopacity = (the blend's gradient of the compensated opacity) * h, times o (1 - o) under GSR_RAW_OPACITY; and
+ * dL/dh = that gradient * opacity_activated is chained through h(a, b, c) into the gradient of the 2-D covariance (zero where
+ * the clamp 0.000025 is active), from where it reaches dL_dcov3D, the covariance part of dL_dmean3D, dL_dscale / dL_drot, the fused
+ * geom_adam steps and the J^T dL/dT term of dL_dviewmatrix like every other covariance gradient.
+ * Works with both GSR_BINNING_* arrangements, GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY, GSR_RAW_*, colors_precomp, cov3D_precomp,
+ * the depth / alpha maps and their gradients, the pose gradients, geom_adam, sh_adam and the view-factored exchange.  0 = the
+ * reference's render, bit for bit, by the same kernels as before (the bit selects instantiations of its own). */
+#define GSR_ANTIALIAS 256
 
 /* Rasterizer::forward, cuda_rasterizer/rasterizer_impl.cu:198-336.
  * Fills out_color and radii, returns the number of (tile, Gaussian) instances in

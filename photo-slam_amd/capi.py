@@ -132,6 +132,7 @@ class DensifyGatherArgs(C.Structure):
 
 RAW_OPACITY, RAW_SCALING, RAW_ROTATION = 1, 2, 4   # GSR_RAW_* of include/gsr.h
 CULL_EMPTY_TILES, FORWARD_ONLY = 8, 128             # GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY
+ANTIALIAS = 256                                     # GSR_ANTIALIAS: forward AND backward (the same value in both calls)
 
 
 # every symbol include/gsr.h declares

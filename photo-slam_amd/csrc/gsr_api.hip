@@ -114,6 +114,11 @@ static thread_local int t_last_forward_only = -1;   // gsr_last_forward_only()
 // the geometry buffer of this thread's last forward-only gsr_forward (GSR_FORWARD_ONLY): gsr_backward refuses it -- a cheap guard,
 // not a full check (a backward pass on another thread is not caught); a training forward on the same buffer clears it
 static thread_local const char* t_forward_only_geom = nullptr;
+// GSR_ANTIALIAS must be the same in gsr_forward and gsr_backward (the record holds the compensated opacity): the geometry buffer
+// and the bit of this thread's last training forward are remembered, and gsr_backward refuses that buffer with the other value.
+// The same kind of cheap guard: a backward pass on another thread is not caught.
+static thread_local const char* t_antialias_geom = nullptr;
+static thread_local int t_antialias_bit = 0;
 // gsr_host_wait_stats(): how long the calling thread was blocked in gsr_forward's ONE host synchronisation (the instance count)
 static thread_local double t_sync_wait_us = 0.0;
 static thread_local long long t_sync_waits = 0;
@@ -384,6 +389,10 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	GeometryState g = GeometryState::carve(geom_chunk, (size_t)P);
 	if (fwd_only) t_forward_only_geom = geom_chunk;
 	else if (t_forward_only_geom == geom_chunk) t_forward_only_geom = nullptr;
+	if (!fwd_only) {
+		t_antialias_geom = geom_chunk;
+		t_antialias_bit = a->raw_params & GSR_ANTIALIAS;
+	}
 	char* img_chunk = imageBuffer(image_ctx, image_bytes(W, H, fwd_only));
 	if (!img_chunk) return GSR_ERR_ALLOC;
 	ImageState im = ImageState::carve(img_chunk, (size_t)W * H, (size_t)tiles, nullptr, fwd_only);
@@ -579,6 +588,9 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	if (a->R > 0 && !a->binning_buffer) return GSR_ERR_INVALID_ARG;
 	// the buffers of a forward-only pass hold nothing a backward pass needs (GSR_FORWARD_ONLY; this thread's last such pass only)
 	if (t_forward_only_geom != nullptr && a->geom_buffer == t_forward_only_geom) return GSR_ERR_INVALID_ARG;
+	// GSR_ANTIALIAS differs from the forward pass that filled this geometry buffer (this thread's last training forward only)
+	if (t_antialias_geom != nullptr && a->geom_buffer == t_antialias_geom && (a->raw_params & GSR_ANTIALIAS) != t_antialias_bit)
+		return GSR_ERR_INVALID_ARG;
 	// (a stream cannot be made to wait for an event of its own future: refused HERE, before anything is enqueued and before the
 	// lazy rows' catch-up has advanced a step counter)
 	if (a->color_view_ready_stream && a->dL_dcolor_view && a->color_view_ready_stream == stream_) return GSR_ERR_INVALID_ARG;

@@ -256,6 +256,16 @@ int launch_knn(int P, const float* points, float* meanDists, char* scratch, hipS
 int launch_morton_order(int n, const float* points, uint32_t** order_out, char* scratch, hipStream_t stream);
 float* morton_points_buffer(int n, char* scratch);
 
+// GSR_ANTIALIAS (include/gsr.h): h^2 of the opacity compensation, h = sqrt(h^2), from the projected covariance (a0 b; b c0) BEFORE
+// the low-pass and det1 = (a0 + 0.3f) (c0 + 0.3f) - b b, the determinant the conic is formed from.  ONE function for the forward
+// and the backward preprocess (both compiled with -ffp-contract=off: the same bits); the operation order is part of the contract.
+constexpr float AA_H2_MIN = 0.000025f;
+__device__ __forceinline__ float antialias_h2(float a0, float b, float c0, float det1)
+{
+	const float det0 = a0 * c0 - b * b;
+	return fmaxf(AA_H2_MIN, det0 / det1);
+}
+
 // computeCov3D, forward.cu:118-152 (M = S*R with S diagonal: M[c][r] = s_r * R[c][r]; Sigma = transpose(M) * M), with the
 // activations of raw_params applied first (getScalingActivation / getRotationActivation, gaussian_model.cpp:48-56).
 // ONE function for the forward preprocess, which needs Sigma for the projection, and for the backward preprocess, which

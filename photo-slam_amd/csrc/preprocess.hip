@@ -36,6 +36,9 @@ __device__ __forceinline__ float ndc2pix(float v, int S) { return (float)(((v + 
 constexpr int FWD_ROWS = GSR_FWD_STAGE_ROWS;   // SH rows staged per pass and wave
 // (PRE_THREADS = 128, state.h: 2 waves per workgroup)
 
+// AA: GSR_ANTIALIAS (include/gsr.h) -- the opacity of the blend record is multiplied by h = sqrt(det Sigma / det(Sigma + 0.3 I))
+// (kernels.h: antialias_h2).  An instantiation of its own, so that the default kernel is the same code as without the feature.
+template <bool AA>
 __global__ void __launch_bounds__(PRE_THREADS)
 preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 {
@@ -59,6 +62,7 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 	float px = 0.f, py = 0.f, pz = 0.f;
 	float pix = 0.f, piy = 0.f, conx = 0.f, cony = 0.f, conz = 0.f;
 	uint32_t rect_lo = 0, rect_hi = 0;
+	float aa_h = 1.0f;   // AA: the opacity compensation of the low-pass
 
 	// ---------------- phase 1: geometry (per lane)
 	if (in_range) {
@@ -117,6 +121,9 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 			// conic + radius, forward.cu:218-232
 			const float det = cov00 * cov11 - cov01 * cov01;
 			if (det == 0.0f) break;
+			// AA: the diagonal before the low-pass is the same two sums again (the same bits; the compiler folds them) -- written
+			// here, not above, so that the statements of the default kernel stay exactly as they were
+			if constexpr (AA) aa_h = sqrtf(antialias_h2(A00 * T00 + A10 * T01 + A20 * T02, cov01, A01 * T10 + A11 * T11 + A21 * T12, det));
 			const float det_inv = 1.f / det;
 			conx = cov11 * det_inv;
 			cony = -cov01 * det_inv;
@@ -229,6 +236,7 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 			g.rec[3 * (size_t)idx + 0] = make_float4(pix, piy, conx, cony);
 			float opac = p.opacities[idx];
 			if (p.raw_params & GSR_RAW_OPACITY) opac = 1.0f / (1.0f + expf(-opac));   // getOpacityActivation, :68-71
+			if constexpr (AA) opac = opac * aa_h;   // every later stage reads the compensated opacity from the record
 			g.rec[3 * (size_t)idx + 1] = make_float4(conz, opac, cr, cg);
 			g.rec[3 * (size_t)idx + 2] = make_float4(cb, __uint_as_float(rect_lo), __uint_as_float(rect_hi), 0.f);
 			if (!p.forward_only) g.clamped[idx] = clamp_bits;   // (read by the backward pass only)
@@ -265,7 +273,8 @@ check_frustum_kernel(int P, const float* __restrict__ means3D, const float* __re
 
 int launch_preprocess_fwd(const PreprocessParams& p, const GeometryState& g, hipStream_t stream)
 {
-	GSR_LAUNCH(preprocess_fwd_kernel, div_up(p.P, PRE_THREADS), PRE_THREADS, stream, p, g);
+	if (p.raw_params & GSR_ANTIALIAS) GSR_LAUNCH(preprocess_fwd_kernel<true>, div_up(p.P, PRE_THREADS), PRE_THREADS, stream, p, g);
+	else GSR_LAUNCH(preprocess_fwd_kernel<false>, div_up(p.P, PRE_THREADS), PRE_THREADS, stream, p, g);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

@@ -248,7 +248,12 @@ __device__ __forceinline__ void pack_view_row(const PreprocessBwdParams& p, int 
 // (pose_v below), three packed butterflies over the wave (wave_reduce24_swap_f32), the two waves through LDS, and ONE slab entry
 // per workgroup and sum written with plain stores (kernels.h: pose slab); pose_final_sum_kernel adds the entries in a fixed order.
 // No atomics: the same bits every time.  An instantiation of its own, so that the kernels without it stay the same code.
-template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false>
+// AA: GSR_ANTIALIAS (include/gsr.h) -- the blend record holds o h, h = sqrt(max(0.000025, det Sigma / det(Sigma + 0.3 I))) (kernels.h:
+// antialias_h2, the forward pass's bits), and a[8] is the gradient of that product.  dL_dopacity = a[8] h; dL/dh = a[8] o joins the
+// gradient of the 2-D covariance BEFORE it is chained into T, Sigma and the mean, so cov3D, scale / rotation, the mean, the fused
+// steps and the pose sums all carry it without further code.  The opacity gradient then leaves behind computeCov2D instead of in
+// front of it.  An instantiation of its own: the kernels without it stay the same code.
+template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false>
 __global__ void __launch_bounds__(PRB_THREADS)
 preprocess_bwd_kernel(const PreprocessBwdParams p)
 {
@@ -296,6 +301,7 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 	// dL_dcolor (x, y, z) + dL_dmean2D.x (w) ; dL_dmean2D.y (x) + dL_dconic (y, z, w)
 	float4 ga0 = make_float4(0.f, 0.f, 0.f, 0.f), ga1 = make_float4(0.f, 0.f, 0.f, 0.f);
 	float g_opacity = 0.f;
+	float aa_o = 0.f;   // AA: the record's (compensated) opacity
 
 	if (vis) {
 		mx = p.means3D[3 * (size_t)idx];
@@ -309,8 +315,12 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		ga0 = make_float4(a[0], a[1], a[2], -o * p.half_w * (a[3] * A + a[4] * B));
 		ga1 = make_float4(-o * p.half_h * (a[4] * C + a[3] * B), -0.5f * o * a[5], -0.5f * o * a[6], -0.5f * o * a[7]);
 		g_opacity = a[8];
-		// raw logit: d sigmoid = o (1 - o), o = the activated opacity kept in the blend record
-		if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o * (1.0f - o);
+		if constexpr (AA) {
+			aa_o = o;   // (the chain rule of the opacity waits for h: below, behind the 2-D covariance)
+		} else {
+			// raw logit: d sigmoid = o (1 - o), o = the activated opacity kept in the blend record
+			if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o * (1.0f - o);
+		}
 	}
 	const float gcx = ga1.y, gcy = ga1.z, gcz = ga1.w;
 	if (in_range) {
@@ -341,11 +351,13 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 			p.dL_dcolor_view[3 * (size_t)idx + 2] = v2;
 			if (PACKED) pack_view_row(p, idx, vis, seen_mask, v0, v1, v2);
 		}
-		if (p.geom.on) {
-			const float go[1] = {g_opacity};
-			geom_adam_row<1>(p.geom.opacity, (size_t)idx, go);
-		} else {
-			p.dL_dopacity[idx] = g_opacity;
+		if constexpr (!AA) {
+			if (p.geom.on) {
+				const float go[1] = {g_opacity};
+				geom_adam_row<1>(p.geom.opacity, (size_t)idx, go);
+			} else {
+				p.dL_dopacity[idx] = g_opacity;
+			}
 		}
 		if (p.dL_dconic) reinterpret_cast<float4*>(p.dL_dconic)[idx] = make_float4(gcx, gcy, 0.f, gcz);
 	}
@@ -451,12 +463,37 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		const float b = A01 * T00 + A11 * T01 + A21 * T02;
 		const float c = (A01 * T10 + A11 * T11 + A21 * T12) + 0.3f;
 		const float denom = a * c - b * b;
+		float aa_dh2 = 0.f;   // AA: dL/d(h^2), zero where the clamp of h^2 is active
+		float a_0 = 0.f, c_0 = 0.f;   // AA: the diagonal before the low-pass
+		if constexpr (AA) {
+			// (the same two sums as in a and c, the same bits -- written here so that the statements of the kernels without AA
+			// stay exactly as they were)
+			a_0 = A00 * T00 + A10 * T01 + A20 * T02;
+			c_0 = A01 * T10 + A11 * T11 + A21 * T12;
+			const float h2 = antialias_h2(a_0, b, c_0, denom);
+			const float h = sqrtf(h2);
+			// the activated opacity o is recovered from the record (o h) and h, not from the input: gsr_backward_args carries no
+			// opacities (the reference's backward has none either); h >= 0.005, and the quotient is o to two roundings
+			const float o_act = aa_o / h;
+			const float dL_dh = g_opacity * o_act;
+			g_opacity = g_opacity * h;
+			if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o_act * (1.0f - o_act);
+			aa_dh2 = (h2 <= AA_H2_MIN) ? 0.f : dL_dh / (2.0f * h);
+		}
 		float dL_da = 0, dL_db = 0, dL_dc = 0;
 		const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
 		if (denom2inv != 0) {
 			dL_da = denom2inv * (-c * c * gcx + 2 * b * c * gcy + (denom - a * c) * gcz);
 			dL_dc = denom2inv * (-a * a * gcz + 2 * a * b * gcy + (denom - a * c) * gcx);
 			dL_db = denom2inv * 2 * (b * c * gcx - (denom + 2 * b * b) * gcy + a * b * gcz);
+			if constexpr (AA) {
+				// r = det Sigma / det Sigma', w = 0.3: dr/da0 = w (c0^2 + w c0 + b^2) / det'^2, dr/dc0 likewise, dr/db = -2 b w (a0 + c0 + w) / det'^2
+				const float w = 0.3f;
+				const float f = aa_dh2 / (denom * denom);
+				dL_da += w * (c_0 * c_0 + w * c_0 + b * b) * f;
+				dL_dc += w * (a_0 * a_0 + w * a_0 + b * b) * f;
+				dL_db += -2.0f * b * w * (a_0 + c_0 + w) * f;
+			}
 			dcov[0] = (T00 * T00 * dL_da + T00 * T10 * dL_db + T10 * T10 * dL_dc);
 			dcov[3] = (T01 * T01 * dL_da + T01 * T11 * dL_db + T11 * T11 * dL_dc);
 			dcov[5] = (T02 * T02 * dL_da + T02 * T12 * dL_db + T12 * T12 * dL_dc);
@@ -517,6 +554,17 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 				for (int c = 0; c < 4; c++)
 #pragma unroll
 					for (int k = 0; k < 3; k++) pose_v[12 + 3 * c + k] = gh[k] * xw[c];
+			}
+		}
+	}
+
+	if constexpr (AA) {
+		if (in_range) {   // (culled: zero, like every other output)
+			if (p.geom.on) {
+				const float go[1] = {g_opacity};
+				geom_adam_row<1>(p.geom.opacity, (size_t)idx, go);
+			} else {
+				p.dL_dopacity[idx] = g_opacity;
 			}
 		}
 	}
@@ -841,13 +889,19 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 	const bool pose = p.pose_scratch != nullptr;
 	unsigned pose_b_rows = 0u;   // entries of the camera centre's sums in the pose slab (kernels.h)
 	if (pose && (factored || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // no pose gradients through the multi-GPU exchange
+	const bool aa = (p.raw_params & GSR_ANTIALIAS) != 0;
+#define GSR_PRB(RO, AAV)                                                                                                          \
+	do {                                                                                                                          \
+		if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, true, AAV>), grid, PRB_THREADS, stream, p);       \
+		else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, true, AAV>), grid, PRB_THREADS, stream, p);            \
+		else if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, true, true, false, AAV>), grid, PRB_THREADS, stream, p); \
+		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<RO, true, false, false, AAV>), grid, PRB_THREADS, stream, p);    \
+		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV>), grid, PRB_THREADS, stream, p);         \
+		else GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV>), grid, PRB_THREADS, stream, p);                     \
+	} while (0)
 	if (rows_ok && p.D >= 0 && p.D <= 3) {
-		if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, false, true, true>), grid, PRB_THREADS, stream, p);
-		else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<true, false, false, true>), grid, PRB_THREADS, stream, p);
-		else if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, true, true>), grid, PRB_THREADS, stream, p);
-		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<true, true>), grid, PRB_THREADS, stream, p);
-		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<true, false, true>), grid, PRB_THREADS, stream, p);
-		else GSR_LAUNCH(preprocess_bwd_kernel<true>, grid, PRB_THREADS, stream, p);
+		if (aa) GSR_PRB(true, true);
+		else GSR_PRB(true, false);
 		GSR_CHECK_LAUNCH();
 		if (p.notify_stream && p.notify_event) {   // dL_dcolor_view is complete: whoever gathers it need not wait for the SH kernel
 			GSR_HIP(hipEventRecord((hipEvent_t)p.notify_event, stream));
@@ -879,12 +933,8 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 #undef GSR_SHB
 		pose_b_rows = p.D > 0 ? (unsigned)g : 0u;
 	} else {
-		if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, false, true, true>), grid, PRB_THREADS, stream, p);
-		else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<false, false, false, true>), grid, PRB_THREADS, stream, p);
-		else if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, true, true>), grid, PRB_THREADS, stream, p);
-		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<false, true>), grid, PRB_THREADS, stream, p);
-		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<false, false, true>), grid, PRB_THREADS, stream, p);
-		else GSR_LAUNCH(preprocess_bwd_kernel<false>, grid, PRB_THREADS, stream, p);
+		if (aa) GSR_PRB(false, true);
+		else GSR_PRB(false, false);
 		if (p.notify_stream && p.notify_event) {
 			GSR_HIP(hipEventRecord((hipEvent_t)p.notify_event, stream));
 			GSR_HIP(hipStreamWaitEvent((hipStream_t)p.notify_stream, (hipEvent_t)p.notify_event, 0));
@@ -892,6 +942,7 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 		// (the SH direction term, if any, was formed by preprocess_bwd_kernel: one camera-centre entry per workgroup of it)
 		pose_b_rows = (p.shs && p.D > 0) ? (unsigned)grid : 0u;
 	}
+#undef GSR_PRB
 	GSR_CHECK_LAUNCH();
 	if (pose) return launch_pose_final_sum(p.pose_scratch, (unsigned)grid, pose_b_rows, p.dL_dview, p.dL_dproj, p.dL_dcampos, stream);
 	return GSR_OK;

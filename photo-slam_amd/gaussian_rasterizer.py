@@ -52,6 +52,9 @@ class GaussianRasterizationSettings:
     # extension: GaussianRasterizer.forward also renders the depth map sum z alpha T and the alpha map 1 - T_final (include/gsr.h:
     # gsr_forward_args.out_depth / out_alpha) and returns (color, radii, depth, alpha); both maps are differentiable
     render_depth_: bool = False
+    # extension (GSR_ANTIALIAS, include/gsr.h): the opacity is compensated for the 0.3 px low-pass of the projected covariance
+    # (upstream's `antialiasing`); forward and backward get the same value
+    antialiasing_: bool = False
 
 
 def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth=None, alpha=None):
@@ -60,7 +63,7 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
         s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
         s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
         s.campos_, s.prefiltered_, s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0), s.sh_adam_,   # sh_adam_: lazy mode brings visible rows up to date first
-        s.workspace_, out_depth=depth, out_alpha=alpha)
+        s.workspace_, out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_)
     ctx.set_materialize_grads(False)   # (no zero tensor for the unused gradient of `radii`)
     ctx.num_rendered = num_rendered
     ctx.raster_settings = s
@@ -92,7 +95,7 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None, pose=False)
         # catch-up next to the blend kernel
         s.sh_adam_ if (s.sh_grad_view_ is None or (s.sh_adam_ or {}).get("row_step") is not None) else None, s.view_stats_,
         s.geom_adam_, s.training_outputs_only_, dL_ddepth=cont(grad_depth), dL_dalpha=cont(grad_alpha),
-        pose_grad=pose, workspace=s.workspace_ if pose else None)
+        pose_grad=pose, workspace=s.workspace_ if pose else None, antialiasing=s.antialiasing_)
     # order of src/gaussian_rasterizer.cpp:159-179
     def g(t, like):   # (None where an extension took the gradient's place)
         return t if like.numel() and t is not None else None
@@ -173,7 +176,7 @@ def _rasterize_forward_only(means3D, sh, colors_precomp, opacities, scales, rota
             s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
             s.campos_, s.prefiltered_,
             s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0) | capi.FORWARD_ONLY, lazy, s.workspace_,
-            out_depth=depth, out_alpha=alpha)
+            out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_)
     if s.render_depth_:
         return color, radii, depth, alpha
     return color, radii

@@ -87,7 +87,7 @@ class GaussianRenderer:
     def render(viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color=None,
                scaling_modifier=1.0, use_override_color=False, fuse_activations=True, sh_grad_view=None, sh_adam=None, view_stats=None,
                geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None, forward_only=False,
-               render_depth=False):
+               render_depth=False, antialiasing=False):
         """returns (render, viewspace_points, visibility_filter, radii), with render_depth (render, viewspace_points,
         visibility_filter, radii, depth, alpha)
 
@@ -108,7 +108,12 @@ class GaussianRenderer:
 
         render_depth (extension): the depth map sum z alpha T and the alpha map 1 - T_final ([H, W] each, include/gsr.h:
         gsr_forward_args.out_depth / out_alpha) are appended to the tuple; both are differentiable (a depth or alpha loss
-        reaches the positions, opacities, scales and rotations)."""
+        reaches the positions, opacities, scales and rotations).
+
+        antialiasing (extension; False = the reference's render): the opacity of every Gaussian is compensated for the 0.3 px
+        low-pass of its projected covariance (GSR_ANTIALIAS, include/gsr.h; upstream's `antialiasing`), so that a Gaussian keeps
+        its brightness across the resolutions a map is trained and viewed at.  A map is rendered with the value it was trained
+        with."""
         env = os.environ.get("GSR_CULL_EMPTY_TILES")
         if env:
             cull_empty_tiles = env == "1"
@@ -142,7 +147,7 @@ class GaussianRenderer:
             sh_grad_view if sh_in_rasterizer else None, sh_adam if sh_in_rasterizer else None, view_stats,
             geom_adam if raw == 7 else None, bool((geom_adam is not None or training_outputs_only) and raw == 7),
             cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace, forward_only_=forward_only,
-            render_depth_=bool(render_depth))
+            render_depth_=bool(render_depth), antialiasing_=bool(antialiasing))
         rasterizer = GaussianRasterizer(raster_settings)
         means3D = pc.getXYZ()
         means2D = screenspace_points

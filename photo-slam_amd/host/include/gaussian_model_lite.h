@@ -303,6 +303,11 @@ public:
 	// Scheduling / list-building switches, each at its measured-best value; none changes a result.  They
 	// are options of THIS object -- a SLAM process that links the library decides per TrainStep -- and the environment variables
 	// of the bench sessions (GSR_CULL_EMPTY_TILES, GSR_EARLY_GATHER, GSR_LAZY_SLICE_EARLY, GSR_SH_ADAM_SIDE_STREAM) only override.
+	// Anti-aliased rendering (GSR_ANTIALIAS, include/gsr.h): every render of this object -- the train step at whatever H x W the
+	// keyframe's pyramid level has, renderView, refinePose -- compensates the opacity for the 0.3 px low-pass of the projected
+	// covariance.  Unlike the switches above it CHANGES the result; densification and pruning keep their thresholds on the
+	// uncompensated sigmoid(opacity), as upstream does.
+	bool antialiasing_ = false;
 	bool cull_empty_tiles_ = false;   // instances of tiles no pixel of which can blend the Gaussian leave the list (a wash on MI355X)
 	// the rasterizer's three scratch buffers, kept across iterations and grown with headroom (rasterize_points.h: RasterWorkspace);
 	// persistent_workspace_ = false: fresh buffers per call, as the reference's resizeFunctional

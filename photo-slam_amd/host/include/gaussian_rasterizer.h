@@ -106,6 +106,10 @@ struct GaussianRasterizationExtensions {
 	// more outputs of GaussianRasterizerFunctionEx -- (color, radii, depth, alpha), both maps differentiable; its backward takes
 	// any subset of the three image gradients.  Set by GaussianRasterizerEx::forwardWithDepth (forward() renders no maps).
 	bool render_depth_ = false;
+	// GSR_ANTIALIAS (include/gsr.h): anti-aliased rendering -- the opacity of every Gaussian is multiplied by
+	// sqrt(det Sigma / det(Sigma + 0.3 I)) of its projected covariance (upstream's `antialiasing`), in the forward pass, the
+	// forward-only path and the backward pass alike
+	bool antialiasing_ = false;
 };
 
 class GaussianRasterizerFunctionEx : public torch::autograd::Function<GaussianRasterizerFunctionEx> {

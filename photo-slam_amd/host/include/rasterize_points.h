@@ -66,6 +66,9 @@ struct RasterForwardExtensions {
 	// the depth and alpha maps (gsr_forward_args.out_depth / out_alpha): caller-allocated contiguous float32 [H,W] tensors on
 	// the device of means3D, written for every pixel; undefined = not rendered.  depth = sum z alpha T, alpha = 1 - T_final.
 	torch::Tensor out_depth, out_alpha;
+	// GSR_ANTIALIAS (include/gsr.h): the opacity is compensated for the 0.3 px low-pass of the projected covariance; the backward
+	// call must be given the same value
+	bool antialiasing_ = false;
 };
 
 // ... and to the reference's backward parameter list
@@ -96,6 +99,8 @@ struct RasterBackwardExtensions {
 	// workspace: when given, it owns the scratch of the sums (otherwise allocated per call)
 	PoseGradients* pose_grad = nullptr;
 	RasterWorkspace* workspace = nullptr;
+	// GSR_ANTIALIAS: the value the forward call was given
+	bool antialiasing_ = false;
 };
 
 // (num_rendered, out_color[3,H,W], radii[P] i32, geomBuffer u8, binningBuffer u8, imgBuffer u8)

@@ -38,6 +38,7 @@ auto rasterize_forward(const torch::Tensor& means3D, const torch::Tensor& sh, co
 	f.workspace = e.workspace_;
 	f.out_depth = depth;
 	f.out_alpha = alpha;
+	f.antialiasing_ = e.antialiasing_;
 	return RasterizeGaussiansCUDA(s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
 	                              s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh,
 	                              s.sh_degree_, s.campos_, s.prefiltered_, f);
@@ -96,6 +97,7 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 	auto map_grad = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
 	RasterBackwardExtensions b;
 	b.raw_params = e.raw_params_;
+	b.antialiasing_ = e.antialiasing_;
 	b.dL_dcolor_view = e.sh_grad_view_;
 	// view-factored mode: the SH step follows the exchange (gsr_sh_adam_from_views); sh_adam_ -- its lazy form only -- served
 	// the forward pass (rows this view sees caught up) and lets backward run this step's slice of the rotating catch-up

@@ -59,6 +59,7 @@ std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_modes(torch::Tensor
 	GaussianRasterizationExtensions e;
 	e.raw_params_ = (int)raw_params & 7;
 	e.cull_empty_tiles_ = (raw_params & 8) != 0;
+	e.antialiasing_ = (raw_params & 256) != 0;   // GSR_ANTIALIAS
 	e.forward_only_ = extension_forward_only;
 	GaussianRasterizerEx r(s, e);
 	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
@@ -179,6 +180,7 @@ std::tuple<torch::Tensor, torch::Tensor> trainer_render(int64_t h, torch::Tensor
 	torch::Tensor override_color;
 	GaussianRasterizationExtensions ext;
 	ext.raw_params_ = fuse_activations ? 7 : 0;
+	ext.antialiasing_ = t->antialiasing_;
 	auto pkg = GaussianRenderer::render(make_kf(view, proj, campos, fovx, fovy, H, W), (int)H, (int)W, t->gaussians_, pipe,
 	                                    t->background_, override_color, 1.0f, false, ext);
 	return std::make_tuple(std::get<0>(pkg), std::get<3>(pkg));
@@ -232,6 +234,7 @@ torch::Tensor trainer_pose_gradient(int64_t h, torch::Tensor view, torch::Tensor
 	torch::Tensor override_color;
 	GaussianRasterizationExtensions ext;
 	ext.raw_params_ = 7;
+	ext.antialiasing_ = t->antialiasing_;
 	// (the map frozen for this render: only the camera requires grad)
 	auto frozen = t->gaussians_;
 	std::vector<bool> was;
@@ -269,6 +272,7 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "fused_geom_adam") t->fused_geom_adam_ = v != 0.0;
 		else if (k == "active_sh_degree") t->gaussians_->active_sh_degree_ = std::min((int)v, t->gaussians_->max_sh_degree_);
 		else if (k == "cull_empty_tiles") t->cull_empty_tiles_ = v != 0.0;
+		else if (k == "antialiasing") t->antialiasing_ = v != 0.0;
 		else if (k == "depth_loss_weight") t->depth_loss_weight_ = static_cast<float>(v);
 		else if (k == "depth_min") t->depth_min_ = static_cast<float>(v);
 		else if (k == "depth_max") t->depth_max_ = static_cast<float>(v);

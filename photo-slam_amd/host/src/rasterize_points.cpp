@@ -205,7 +205,7 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
 		a.tan_fovx = tan_fovx;
 		a.tan_fovy = tan_fovy;
 		a.prefiltered = prefiltered ? 1 : 0;
-		a.raw_params = ext.raw_params;
+		a.raw_params = ext.raw_params | (ext.antialiasing_ ? GSR_ANTIALIAS : 0);
 		a.out_color = out_color.data_ptr<float>();
 		a.radii = radii.data_ptr<int>();
 		a.out_depth = map_ptr(ext.out_depth, means3D, H, W, "out_depth");
@@ -379,7 +379,7 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 		}
 		a.dL_dscale = (has_scales && !geom) ? dL_dscales.data_ptr<float>() : nullptr;
 		a.dL_drot = (has_scales && !geom) ? dL_drotations.data_ptr<float>() : nullptr;
-		a.raw_params = ext.raw_params;
+		a.raw_params = ext.raw_params | (ext.antialiasing_ ? GSR_ANTIALIAS : 0);
 		gsr_geom_adam ga{};
 		if (geom) {
 			gsr_adam_tensor* ts[4] = {&ga.xyz, &ga.opacity, &ga.scaling, &ga.rotation};

@@ -195,6 +195,7 @@ GaussianRasterizationExtensions TrainStep::viewExtensions()
 	GaussianRasterizationExtensions ext;
 	ext.raw_params_ = 7;
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
+	ext.antialiasing_ = antialiasing_;
 	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
 	ext.forward_only_ = true;
 	return ext;
@@ -270,6 +271,7 @@ std::tuple<torch::Tensor, torch::Tensor> TrainStep::refinePose(std::shared_ptr<G
 	GaussianRasterizationExtensions ext;
 	ext.raw_params_ = 7;
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
+	ext.antialiasing_ = antialiasing_;
 	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
 	std::vector<torch::Tensor> losses;
 	torch::Tensor override_color;
@@ -352,6 +354,7 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	ext.raw_params_ = 7;
 	ext.sh_grad_view_ = sh_grad_view_;
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
+	ext.antialiasing_ = antialiasing_;
 	ext.workspace_ = persistent_workspace_ ? &workspace_ : nullptr;
 	ShAdamStep& sh_adam = ext.sh_adam_;
 	const auto& o = g->opt_;

@@ -106,7 +106,8 @@ class RasterWorkspace:
 
 def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                            viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                           prefiltered, raw_params=0, sh_adam=None, workspace=None, out_depth=None, out_alpha=None):
+                           prefiltered, raw_params=0, sh_adam=None, workspace=None, out_depth=None, out_alpha=None,
+                           antialiasing=False):
     """raw_params (extension, default 0 = reference contract): GSR_RAW_* mask -- opacity / scales / rotations are the
     model's raw parameters and are activated in-kernel (include/gsr.h).  With capi.FORWARD_ONLY in it the call renders the same
     image and radii without preparing anything for a backward pass: the returned buffers are then NOT valid input to
@@ -116,7 +117,10 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
     (forward-only: in registers only -- nothing of the Adam state is written).
     out_depth / out_alpha (extension, default None): caller-allocated contiguous float32 [H, W] tensors on the device of means3D
     that receive the depth map sum z alpha T and the alpha map 1 - T_final (include/gsr.h: gsr_forward_args.out_depth); either
-    may be given alone.  The return tuple is the same."""
+    may be given alone.  The return tuple is the same.
+    antialiasing (extension, default False = the reference's render): the opacity is compensated for the 0.3 px low-pass of the
+    projected covariance (capi.ANTIALIAS in raw_params says the same; include/gsr.h: GSR_ANTIALIAS).  The backward call must be
+    given the same value."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # AT_ERROR, rasterize_points.cu:57-59
     lib = _lib()
@@ -137,7 +141,7 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
         a = capi.ForwardArgs()
         a.P, a.D, a.M, a.width, a.height = P, int(degree), M, W, H
         a.scale_modifier, a.tan_fovx, a.tan_fovy, a.prefiltered = float(scale_modifier), float(tan_fovx), float(tan_fovy), int(bool(prefiltered))
-        a.raw_params = int(raw_params)
+        a.raw_params = int(raw_params) | (capi.ANTIALIAS if antialiasing else 0)
         for name, t in (("background", background), ("means3D", means3D), ("shs", sh), ("colors_precomp", colors),
                         ("opacities", opacity), ("scales", scales), ("rotations", rotations),
                         ("cov3D_precomp", cov3D_precomp), ("viewmatrix", viewmatrix), ("projmatrix", projmatrix),
@@ -181,7 +185,7 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                                    viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                    geomBuffer, R, binningBuffer, imageBuffer, raw_params=0, dL_dcolor_view=None, sh_adam=None,
                                    view_stats=None, geom_adam=None, training_outputs_only=False, packed_view=None,
-                                   dL_ddepth=None, dL_dalpha=None, pose_grad=False, workspace=None):
+                                   dL_ddepth=None, dL_dalpha=None, pose_grad=False, workspace=None, antialiasing=False):
     """dL_dcolor_view (extension, default None = reference contract): a [P,3] float tensor that receives the clamp-masked
     colour gradient; dL_dsh is then NOT computed and None is returned in its place (view-factored gradient exchange,
     shGradFromViews below).
@@ -202,7 +206,10 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
     pose_grad (extension, default False): the gradients with respect to viewmatrix [4,4], projmatrix [4,4] and campos [3] -- the
     three inputs as the kernels use them, treated as independent (gsr_backward_args.dL_dviewmatrix ...) -- are returned behind
     the eight of the reference: a tuple of eleven.  Not together with dL_dcolor_view.  workspace: a RasterWorkspace that then
-    owns the scratch of the sums (otherwise allocated per call)."""
+    owns the scratch of the sums (otherwise allocated per call).
+    antialiasing (extension, default False): the value the forward call was given (GSR_ANTIALIAS; capi.ANTIALIAS in raw_params says
+    the same) -- dL_dopacity is then the gradient of the uncompensated opacity, and the compensation's own gradient reaches the
+    covariance, the scales / rotations, the positions and the camera."""
     lib = _lib()
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
@@ -245,7 +252,7 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
         a = capi.BackwardArgs()
         a.P, a.D, a.M, a.R, a.width, a.height = P, int(degree), M, int(R), W, H
         a.scale_modifier, a.tan_fovx, a.tan_fovy = float(scale_modifier), float(tan_fovx), float(tan_fovy)
-        a.raw_params = int(raw_params)
+        a.raw_params = int(raw_params) | (capi.ANTIALIAS if antialiasing else 0)
         for name, t in (("background", background), ("means3D", means3D), ("shs", sh), ("colors_precomp", colors),
                         ("scales", scales), ("rotations", rotations), ("cov3D_precomp", cov3D_precomp),
                         ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("campos", campos),

@@ -209,7 +209,7 @@ def allreduce_mean(tensors, world_size):
 class TrainStep:
     def __init__(self, gaussians, opt, pipe, background, world_size=1, cameras_extent=None, densify=False,
                  densify_min_opacity=0.005, prune_big_point_after_iter=30000, seed=0, factored_exchange=True, fused_sh_adam=True,
-                 lazy_sh_adam_window=32, fused_geom_adam=True, cull_empty_tiles=False):
+                 lazy_sh_adam_window=32, fused_geom_adam=True, cull_empty_tiles=False, antialiasing=False):
         # the rasterizer's scratch buffers, kept across iterations and grown with headroom (rasterize_points.RasterWorkspace);
         # persistent_workspace_ = False: fresh buffers per call, as the reference's resizeFunctional
         from . import rasterize_points as rp
@@ -218,6 +218,10 @@ class TrainStep:
         # ... and a second set for render_view(): a view between a training forward and its backward must not overwrite the
         # buffers that forward saved
         self.view_workspace_ = rp.RasterWorkspace()
+        # anti-aliased rendering (GSR_ANTIALIAS, include/gsr.h): every render of this object -- the train step at whatever H x W the
+        # keyframe's pyramid level has, render_view, refinePose -- compensates the opacity for the 0.3 px low-pass.  Densification and
+        # pruning keep their thresholds on the uncompensated sigmoid(opacity), as upstream does.
+        self.antialiasing_ = bool(antialiasing)
         self.cull_empty_tiles_ = bool(cull_empty_tiles)   # option of this object; GSR_CULL_EMPTY_TILES only overrides (gaussian_renderer.py)
         self.gaussians_, self.opt_, self.pipe_, self.background_ = gaussians, opt, pipe, background
         self.cameras_extent_ = cameras_extent if cameras_extent is not None else gaussians.spatial_lr_scale_
@@ -257,7 +261,7 @@ class TrainStep:
                 viewpoint_cam, viewpoint_cam.image_height_, viewpoint_cam.image_width_, self.gaussians_, self.pipe_,
                 self.background_, cull_empty_tiles=self.cull_empty_tiles_,
                 workspace=self.view_workspace_ if self.persistent_workspace_ else None, forward_only=True,
-                render_depth=bool(with_depth))
+                render_depth=bool(with_depth), antialiasing=self.antialiasing_)
         if with_depth:
             return out[0], out[4], out[5]
         return out[0]
@@ -310,7 +314,8 @@ class TrainStep:
             s = GaussianRasterizationSettings(
                 kf.image_height_, kf.image_width_, kf.tanfovx_, kf.tanfovy_, self.background_, 1.0, kf.world_view_transform_,
                 kf.full_proj_transform_, g.active_sh_degree_, kf.camera_center_, False, 7, cull_empty_tiles_=cull,
-                workspace_=self.view_workspace_ if self.persistent_workspace_ else None, render_depth_=use_depth)
+                workspace_=self.view_workspace_ if self.persistent_workspace_ else None, render_depth_=use_depth,
+                antialiasing_=self.antialiasing_)
             out = GaussianRasterizer(s)(xyz, means2D, opacity, True, False, True, True, False, sh, None, scaling, rotation, None)
             loss = loss_utils.fused_l1_ssim_loss(out[0], gt_image, eff_mask, opt.lambda_dssim_, is_root=True)
             if use_depth:
@@ -399,7 +404,7 @@ class TrainStep:
                 sh_grad_view=sh_view, sh_adam=fwd_adam, view_stats=view_stats, geom_adam=geom_adam,
                 training_outputs_only=True,   # the statistics are fused (or over): nobody reads the viewspace gradient
                 cull_empty_tiles=self.cull_empty_tiles_, workspace=self.workspace_ if self.persistent_workspace_ else None,
-                render_depth=use_depth)
+                render_depth=use_depth, antialiasing=self.antialiasing_)
             rendered_image, viewspace_point_tensor, visibility_filter, radii = out[:4]
         finally:
             g._in_lazy_step = False
