@@ -34,6 +34,10 @@ __device__ __forceinline__ float ndc2pix(float v, int S) { return (float)(((v + 
 #define GSR_FWD_STAGE_ROWS STAGE_ROWS
 #endif
 constexpr int FWD_ROWS = GSR_FWD_STAGE_ROWS;   // SH rows staged per pass and wave
+#ifndef GSR_FWD_TRIP_GROUPS
+#define GSR_FWD_TRIP_GROUPS 4
+#endif
+constexpr int FWD_TRIP_GROUPS = GSR_FWD_TRIP_GROUPS;   // row groups the loader asks for together (shrows.h)
 // (PRE_THREADS = 128, state.h: 2 waves per workgroup)
 
 // AA: GSR_ANTIALIAS (include/gsr.h) -- the opacity of the blend record is multiplied by h = sqrt(det Sigma / det(Sigma + 0.3 I))
@@ -191,7 +195,7 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 			const int nf4 = lagging ? ROW_F4 : (3 * ncoef + 3) >> 2;   // whole rows where some must be updated
 			for (int r0 = 0; r0 < nvis; r0 += FWD_ROWS) {
 				const int count = (nvis - r0) < FWD_ROWS ? (nvis - r0) : FWD_ROWS;
-				wave_load_listed_rows(reinterpret_cast<const float4*>(p.shs), wave_first, nf4, r0, count, s_rows[w], s_list[w]);
+				wave_load_listed_rows<false, FWD_TRIP_GROUPS>(reinterpret_cast<const float4*>(p.shs), wave_first, nf4, r0, count, s_rows[w], s_list[w]);
 				if (lagging) {
 					// (forward-only: the caught-up values live in the stage alone -- the row stays behind in HBM, shrows.h)
 					if (p.forward_only) wave_lazy_peek_listed(p.lazy, wave_first, r0, count, s_rows[w], s_list[w], s_lag[w]);

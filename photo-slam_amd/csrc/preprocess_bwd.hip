@@ -9,8 +9,9 @@
 //     (src/rasterize_points.cu:149-157, 300 B/Gaussian);
 //   * sh_bwd_rows_kernel: the SH backward (cuda_rasterizer/backward.cu:20-139).  Rows move through LDS (shrows.h); it
 //     writes dL_dsh for EVERY Gaussian and adds the view-direction term to dL_dmean3D last (the reference's order).
-// They were one kernel until its 140+ VGPRs capped it at three waves per SIMD; both halves are
-// latency-bound (measured: time ~ 1/occupancy), and apart they run at 6-8 waves.  Other SH layouts take the
+// They were one kernel until its 140+ VGPRs capped it at three waves per SIMD; both halves were
+// latency-bound (measured: time ~ 1/occupancy), and apart they run at 4-8 waves.  The loads of a row pass, of a fused Adam
+// trip and of a geometry tensor are issued together and waited for once (shrows.h; EXPERIMENTS.md R7.5).  Other SH layouts take the
 // fused instantiation with per-lane row access.
 //
 // HBM per Gaussian: culled: 4 read (radius) + (55+3M)*4 written zeros; visible: reads mean 12 (x2), cov3D 24, record 32,
@@ -31,25 +32,62 @@ constexpr int SHB_THREADS = 64;    // one wave x 6.5 KiB of row staging per work
 
 // One Adam step of row idx of a [P,N] geometry tensor with the gradient in registers (gsr_geom_adam): the thread that holds
 // the gradient applies it -- the gradient is not written and not read back, the four separate passes disappear.
+// The 3 N operands are loaded first, then all are computed, then all are stored: one HBM round trip per tensor.  (Element by
+// element -- load m, v; store m, v; load param; store -- the compiler may not move the next element's loads above the
+// stores through these unqualified pointers: 2 N dependent round trips.)  The two halves are callable apart so that a kernel
+// that steps two tensors in a row asks for the operands of both before it stores the first.
 template <int N>
-__device__ __forceinline__ void geom_adam_row(const GeomAdamTensor& t, size_t idx, const float (&g)[N])
+struct GeomAdamRegs {
+	float m[N], v[N], w[N];
+};
+template <int N>
+__device__ __forceinline__ void geom_adam_load(const GeomAdamTensor& t, size_t idx, GeomAdamRegs<N>& r)
 {
 #pragma unroll
 	for (int k = 0; k < N; k++) {
 		const size_t i = (size_t)N * idx + k;
-		const float m = t.s.b1 * t.exp_avg[i] + t.s.omb1 * g[k];
-		const float v = t.s.b2 * t.exp_avg_sq[i] + t.s.omb2 * g[k] * g[k];
-		t.exp_avg[i] = m;
-		t.exp_avg_sq[i] = v;
-		t.param[i] -= t.s.step_size * adam_ratio(m, v, t.s.inv_sqrt_bc2, t.s.eps);
+		r.m[k] = t.exp_avg[i];
+		r.v[k] = t.exp_avg_sq[i];
+		r.w[k] = t.param[i];
 	}
 }
-__device__ __forceinline__ void geom_adam_row4(const GeomAdamTensor& t, size_t idx, const float4& g4)
+template <int N>
+__device__ __forceinline__ void geom_adam_finish(const GeomAdamTensor& t, size_t idx, const float (&g)[N], GeomAdamRegs<N>& r)
 {
-	float4 pv = reinterpret_cast<const float4*>(t.param)[idx];
-	float4 mv = reinterpret_cast<const float4*>(t.exp_avg)[idx];
-	float4 vv = reinterpret_cast<const float4*>(t.exp_avg_sq)[idx];
-	float* pp = &pv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+	for (int k = 0; k < N; k++) {
+		r.m[k] = t.s.b1 * r.m[k] + t.s.omb1 * g[k];
+		r.v[k] = t.s.b2 * r.v[k] + t.s.omb2 * g[k] * g[k];
+		r.w[k] -= t.s.step_size * adam_ratio(r.m[k], r.v[k], t.s.inv_sqrt_bc2, t.s.eps);
+	}
+#pragma unroll
+	for (int k = 0; k < N; k++) {
+		const size_t i = (size_t)N * idx + k;
+		t.exp_avg[i] = r.m[k];
+		t.exp_avg_sq[i] = r.v[k];
+		t.param[i] = r.w[k];
+	}
+}
+template <int N>
+__device__ __forceinline__ void geom_adam_row(const GeomAdamTensor& t, size_t idx, const float (&g)[N])
+{
+	GeomAdamRegs<N> r;
+	geom_adam_load<N>(t, idx, r);
+	geom_adam_finish<N>(t, idx, g, r);
+}
+// ... and a [P,4] tensor as 16-byte vectors
+struct GeomAdamRegs4 {
+	float4 p, m, v;
+};
+__device__ __forceinline__ void geom_adam_load4(const GeomAdamTensor& t, size_t idx, GeomAdamRegs4& r)
+{
+	r.p = reinterpret_cast<const float4*>(t.param)[idx];
+	r.m = reinterpret_cast<const float4*>(t.exp_avg)[idx];
+	r.v = reinterpret_cast<const float4*>(t.exp_avg_sq)[idx];
+}
+__device__ __forceinline__ void geom_adam_finish4(const GeomAdamTensor& t, size_t idx, const float4& g4, GeomAdamRegs4& r)
+{
+	float* pp = &r.p.x; float* mp = &r.m.x; float* vp = &r.v.x;
 	const float g[4] = {g4.x, g4.y, g4.z, g4.w};
 #pragma unroll
 	for (int k = 0; k < 4; k++) {
@@ -57,9 +95,9 @@ __device__ __forceinline__ void geom_adam_row4(const GeomAdamTensor& t, size_t i
 		vp[k] = t.s.b2 * vp[k] + t.s.omb2 * g[k] * g[k];
 		pp[k] -= t.s.step_size * adam_ratio(mp[k], vp[k], t.s.inv_sqrt_bc2, t.s.eps);
 	}
-	reinterpret_cast<float4*>(t.param)[idx] = pv;
-	reinterpret_cast<float4*>(t.exp_avg)[idx] = mv;
-	reinterpret_cast<float4*>(t.exp_avg_sq)[idx] = vv;
+	reinterpret_cast<float4*>(t.param)[idx] = r.p;
+	reinterpret_cast<float4*>(t.exp_avg)[idx] = r.m;
+	reinterpret_cast<float4*>(t.exp_avg_sq)[idx] = r.v;
 }
 
 // SH backward for aligned 48-float rows; DEG = active SH degree.  FACTORED (gsr_backward_args.dL_dcolor_view): the
@@ -68,10 +106,13 @@ __device__ __forceinline__ void geom_adam_row4(const GeomAdamTensor& t, size_t i
 // POSE (gsr_backward_args.dL_dcampos): the direction term is d/d(mean - campos), so its negative, summed over the wave (= the
 // workgroup), is this workgroup's entry of the camera-centre sums in the pose slab (kernels.h) -- an instantiation of its own.
 template <int DEG, int MODE, bool POSE = false>   // MODE: 0 = gradient rows out, 1 = factored (colour gradient out), 2 = fused Adam step
+#ifndef GSR_SHB_SMALL_TRIP
+#define GSR_SHB_SMALL_TRIP 4
+#endif
 #ifndef GSR_SHB_WAVES_LO
 #define GSR_SHB_WAVES_LO 6
 #endif
-__global__ void __launch_bounds__(SHB_THREADS) GSR_WAVES_PER_EU(GSR_SHB_WAVES_LO, 8)   // 80 VGPRs (3 dwords of scratch at degree 3)
+__global__ void __launch_bounds__(SHB_THREADS) GSR_WAVES_PER_EU(GSR_SHB_WAVES_LO, 8)   // modes 0 / 1: 80 VGPRs (2 dwords of scratch at degree 3); the fused step: 118, LDS-limited
 sh_bwd_rows_kernel(const PreprocessBwdParams p)
 {
 	__shared__ float4 s_rows[SHB_THREADS / 64][STAGE_ROWS][ROW_F4_PAD];
@@ -90,6 +131,9 @@ sh_bwd_rows_kernel(const PreprocessBwdParams p)
 	const bool vis = in_range && (p.radii[idx] > 0);
 	constexpr int ncoef = (DEG + 1) * (DEG + 1);
 	constexpr bool FACTORED = MODE == 1;
+	// the fused step is LDS-limited to four waves per SIMD and has the registers for a whole pass per trip; the other two modes
+	// run at six waves per SIMD on 80 VGPRs and take half a pass per trip (shrows.h)
+	constexpr int SHB_TRIP_GROUPS = MODE == 2 ? STAGE_ROWS / 4 : (STAGE_ROWS / 4 > GSR_SHB_SMALL_TRIP ? GSR_SHB_SMALL_TRIP : STAGE_ROWS / 4);
 	float dRGB[3] = {0.f, 0.f, 0.f};
 	float ddx[3] = {0.f, 0.f, 0.f}, ddy[3] = {0.f, 0.f, 0.f}, ddz[3] = {0.f, 0.f, 0.f};  // dRGBdx/dy/dz
 	float ox = 0.f, oy = 0.f, oz = 1.f;
@@ -126,7 +170,7 @@ sh_bwd_rows_kernel(const PreprocessBwdParams p)
 				const unsigned long long m = wave_ballot(vis && mine);
 				if (vis && mine) s_list[w][__popcll(m & lanemask_lt())] = (uint32_t)(l % STAGE_ROWS);
 				wave_fence();
-				wave_load_listed_rows<true>(reinterpret_cast<const float4*>(p.shs), half_first, nf4, 0, __popcll(m), s_rows[w], s_list[w]);
+				wave_load_listed_rows<true, SHB_TRIP_GROUPS>(reinterpret_cast<const float4*>(p.shs), half_first, nf4, 0, __popcll(m), s_rows[w], s_list[w]);
 				if (mine && in_range) {
 					float4* row = s_rows[w][l % STAGE_ROWS];
 					if (vis) {
@@ -160,7 +204,9 @@ sh_bwd_rows_kernel(const PreprocessBwdParams p)
 					// took the step in gsr_forward (their rows then are neither read nor written)
 					const uint32_t lit = (uint32_t)(m >> (h * STAGE_ROWS));
 					const uint32_t rows = p.adam_skip_culled ? lit : 0xFFFFFFFFu;
-					wave_adam_rows_rank1(ra, half_first, (int)(left > STAGE_ROWS ? STAGE_ROWS : left), s_rows[w], s_aux[w], rows, lit);
+					// (only the lit rows step: the movers walk the loader's list of them instead of all STAGE_ROWS positions)
+					wave_adam_rows_rank1(ra, half_first, (int)(left > STAGE_ROWS ? STAGE_ROWS : left), s_rows[w], s_aux[w], rows, lit,
+					                     p.adam_skip_culled ? s_list[w] : nullptr, __popcll(m));
 				} else {
 					wave_fence();   // the next pass refills the slice
 				}
@@ -649,8 +695,13 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		}
 	}
 	if (in_range && p.geom.on) {
-		geom_adam_row<3>(p.geom.scaling, (size_t)idx, g_scale);
-		geom_adam_row4(p.geom.rotation, (size_t)idx, dq);
+		// (the operands of both tensors are asked for before the first is stored: one round trip for the two)
+		GeomAdamRegs<3> rs;
+		GeomAdamRegs4 rq;
+		geom_adam_load<3>(p.geom.scaling, (size_t)idx, rs);
+		geom_adam_load4(p.geom.rotation, (size_t)idx, rq);
+		geom_adam_finish<3>(p.geom.scaling, (size_t)idx, g_scale, rs);
+		geom_adam_finish4(p.geom.rotation, (size_t)idx, dq, rq);
 	} else if (in_range && p.dL_dscale) {
 		p.dL_dscale[3 * (size_t)idx + 0] = g_scale[0];
 		p.dL_dscale[3 * (size_t)idx + 1] = g_scale[1];

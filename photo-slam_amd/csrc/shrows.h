@@ -38,18 +38,35 @@ constexpr int STAGE_ROWS = GSR_STAGE_ROWS;    // rows staged per pass (16 or 32:
 // Fill s_rows[j][0..nf4) for j = 0 .. count-1 with the first nf4 vectors of row (first_row + s_list[list_first + j])
 // (BY_SOURCE: the row lands in s_rows[s_list[..]] instead, i.e. at its owner's position).
 // gbase points at row 0; row pitch is ROW_F4 vectors.  count <= STAGE_ROWS.  Wave-uniform arguments.
-template <bool BY_SOURCE = false>
+// TRIP_GROUPS: row groups asked for together (TRIP_GROUPS float4 per lane, transient).  STAGE_ROWS / 4 = the whole pass in one
+// trip; a kernel without the registers for that takes half a pass per trip (one trip for up to 16 listed rows, two beyond).
+template <bool BY_SOURCE = false, int TRIP_GROUPS = STAGE_ROWS / 4>
 __device__ __forceinline__ void wave_load_listed_rows(const float4* __restrict__ gbase, size_t first_row, int nf4, int list_first,
                                                       int count, float4 (*s_rows)[ROW_F4_PAD], const uint32_t* s_list)
 {
 	const int l = lane_id();
 	const int slot = l >> 4, col = l & 15;
-	for (int j0 = 0; j0 < count; j0 += 4) {
-		const int j = j0 + slot;
-		if (col < nf4 && j < count) {
-			const uint32_t src = s_list[list_first + j];
-			// streaming load: a row is read once per pass over the model (the next reader comes after ~3 GB of other traffic)
-			s_rows[BY_SOURCE ? (int)src : j][col] = load_stream_f4(gbase + (first_row + src) * ROW_F4 + col);
+	// Every row group of a trip is asked for before the first LDS write: its loads are in flight together and the trip costs
+	// one HBM round trip, not one per group of four rows (a loop that loads and writes per group compiles to load,
+	// s_waitcnt vmcnt(0), ds_write per group: count / 4 dependent round trips per pass).
+#pragma unroll 1
+	for (int j0 = 0; j0 < count; j0 += 4 * TRIP_GROUPS) {
+		float4 v[TRIP_GROUPS];
+#pragma unroll
+		for (int k = 0; k < TRIP_GROUPS; k++) {
+			const int j = j0 + 4 * k + slot;
+			if (col < nf4 && j < count) {
+				const uint32_t src = s_list[list_first + j];
+				// streaming load: a row is read once per pass over the model (the next reader comes after ~3 GB of other traffic)
+				v[k] = load_stream_f4(gbase + (first_row + src) * ROW_F4 + col);
+			}
+		}
+		GSR_WAIT_LOADS();
+#pragma unroll
+		for (int k = 0; k < TRIP_GROUPS; k++) {
+			const int j = j0 + 4 * k + slot;
+			// (BY_SOURCE: the list entry is read a second time -- an LDS read is cheaper than a register held across the wait)
+			if (col < nf4 && j < count) s_rows[BY_SOURCE ? (int)s_list[list_first + j] : j][col] = v[k];
 		}
 	}
 	wave_fence();
@@ -153,13 +170,41 @@ __device__ __forceinline__ void wave_adam_rows(const RowAdam& a, size_t first_ro
 // vis_mask: rows whose parameter and s_aux entry are staged; the other rows of row_mask step with a zero gradient and read
 // their parameter from HBM as wave_adam_rows does.
 constexpr int AUX_PITCH = 21;   // 16 basis values + 3 colour gradients, odd pitch: conflict-free owner writes
+// One element step of the fused form on the mover's vector (the expressions of wave_adam_rows).
+__device__ __forceinline__ void rank1_vector_step(const RowAdam& a, float ss_first, float4& pv, const float4& gv, float4& mv, float4& vv)
+{
+	float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+	for (int e = 0; e < 4; e++) {
+		const float ss = e < 3 ? ss_first : a.s.step_size_tail;
+		mp[e] = a.s.b1 * mp[e] + a.s.omb1 * gp[e];
+		vp[e] = a.s.b2 * vp[e] + a.s.omb2 * gp[e] * gp[e];
+		pp[e] -= ss * adam_ratio(mp[e], vp[e], a.s.inv_sqrt_bc2, a.s.eps);
+	}
+}
+// Two forms, chosen by the (wave-uniform) caller:
+//   * listed (s_list != nullptr: only the lit rows step -- row_mask == vis_mask, the lazy and the side-stream modes): the movers
+//     walk the compact list of the half's lit rows that the loader used (s_list[0 .. count) = their positions in the stage),
+//     four rows per group and RANK1_LIST_GROUPS groups per trip; the moment vectors of a whole trip are asked for before the
+//     first is stored.  A half with 15 lit rows is ONE trip = one HBM round trip -- the masked walk over all STAGE_ROWS
+//     positions took eight, one per group, half of them for groups with fewer than two lit rows;
+//   * masked (eager mode: every row steps, the culled ones with a zero gradient and their parameter from HBM): GSR_RANK1_MASKED_GROUPS row
+//     groups per trip.
+// The stores of a trip stand in front of the next trip's loads; with 16 listed rows per trip the common half has no next trip.
+#ifndef GSR_RANK1_LIST_GROUPS
+#define GSR_RANK1_LIST_GROUPS 4
+#endif
+constexpr int RANK1_LIST_GROUPS = GSR_RANK1_LIST_GROUPS;
+#ifndef GSR_RANK1_MASKED_GROUPS
+#define GSR_RANK1_MASKED_GROUPS 2
+#endif
 __device__ __forceinline__ void wave_adam_rows_rank1(const RowAdam& a, size_t first_row, int nrows, float4 (*s_rows)[ROW_F4_PAD],
-                                                     const float (*s_aux)[AUX_PITCH], uint32_t row_mask, uint32_t vis_mask)
+                                                     const float (*s_aux)[AUX_PITCH], uint32_t row_mask, uint32_t vis_mask,
+                                                     const uint32_t* s_list = nullptr, int count = 0)
 {
 	const int l = lane_id();
 	const int slot = l >> 4, col = l & 15;
 	wave_fence();
-	const size_t base = (first_row + slot) * ROW_F4 + col;
 	const float ss_first = col == 0 ? a.s.step_size : a.s.step_size_tail;
 	int kc[4], cc[4];   // element e = 4 col + c of the row is coefficient e / 3, channel e % 3
 #pragma unroll
@@ -168,33 +213,75 @@ __device__ __forceinline__ void wave_adam_rows_rank1(const RowAdam& a, size_t fi
 		kc[c] = e / 3;
 		cc[c] = 16 + e - 3 * kc[c];
 	}
-#pragma unroll GSR_ADAM_UNROLL
-	for (int k = 0; k < STAGE_ROWS / 4; k++) {
-		const int r = 4 * k + slot;
-		if (col < ROW_F4 && r < nrows && ((row_mask >> r) & 1u)) {
-			const size_t i = base + (size_t)(4 * k * ROW_F4);
-			float4 mv = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg) + i);
-			float4 vv = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg_sq) + i);
-			float4 pv, gv;
-			if ((vis_mask >> r) & 1u) {
-				pv = s_rows[r][col];
-				const float* ax = s_aux[r];
-				gv = make_float4(ax[kc[0]] * ax[cc[0]], ax[kc[1]] * ax[cc[1]], ax[kc[2]] * ax[cc[2]], ax[kc[3]] * ax[cc[3]]);
-			} else {
-				pv = load_stream_f4(reinterpret_cast<const float4*>(a.param) + i);
-				gv = make_float4(0.f, 0.f, 0.f, 0.f);
-			}
-			float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+	if (s_list != nullptr) {
+#pragma unroll 1
+		for (int j0 = 0; j0 < count; j0 += 4 * RANK1_LIST_GROUPS) {
+			float4 mv[RANK1_LIST_GROUPS], vv[RANK1_LIST_GROUPS];
+			int r[RANK1_LIST_GROUPS];
 #pragma unroll
-			for (int e = 0; e < 4; e++) {
-				const float ss = e < 3 ? ss_first : a.s.step_size_tail;
-				mp[e] = a.s.b1 * mp[e] + a.s.omb1 * gp[e];
-				vp[e] = a.s.b2 * vp[e] + a.s.omb2 * gp[e] * gp[e];
-				pp[e] -= ss * adam_ratio(mp[e], vp[e], a.s.inv_sqrt_bc2, a.s.eps);
+			for (int b = 0; b < RANK1_LIST_GROUPS; b++) {
+				const int j = j0 + 4 * b + slot;
+				if (col < ROW_F4 && j < count) {
+					r[b] = (int)s_list[j];
+					const size_t i = (first_row + (size_t)r[b]) * ROW_F4 + col;
+					mv[b] = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg) + i);
+					vv[b] = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg_sq) + i);
+				}
 			}
-			store_stream_f4(reinterpret_cast<float4*>(a.param) + i, pv);
-			store_stream_f4(reinterpret_cast<float4*>(a.exp_avg) + i, mv);
-			store_stream_f4(reinterpret_cast<float4*>(a.exp_avg_sq) + i, vv);
+			GSR_WAIT_LOADS();
+#pragma unroll
+			for (int b = 0; b < RANK1_LIST_GROUPS; b++) {
+				const int j = j0 + 4 * b + slot;
+				if (col < ROW_F4 && j < count) {
+					const size_t i = (first_row + (size_t)r[b]) * ROW_F4 + col;
+					float4 pv = s_rows[r[b]][col];
+					const float* ax = s_aux[r[b]];
+					const float4 gv = make_float4(ax[kc[0]] * ax[cc[0]], ax[kc[1]] * ax[cc[1]], ax[kc[2]] * ax[cc[2]], ax[kc[3]] * ax[cc[3]]);
+					rank1_vector_step(a, ss_first, pv, gv, mv[b], vv[b]);
+					store_stream_f4(reinterpret_cast<float4*>(a.param) + i, pv);
+					store_stream_f4(reinterpret_cast<float4*>(a.exp_avg) + i, mv[b]);
+					store_stream_f4(reinterpret_cast<float4*>(a.exp_avg_sq) + i, vv[b]);
+				}
+			}
+		}
+		wave_fence();
+		return;
+	}
+	const size_t base = (first_row + slot) * ROW_F4 + col;
+	constexpr int ADAM_BATCH = GSR_RANK1_MASKED_GROUPS;
+	static_assert((STAGE_ROWS / 4) % ADAM_BATCH == 0, "a trip takes ADAM_BATCH whole row groups");
+#pragma unroll 1
+	for (int k0 = 0; k0 < STAGE_ROWS / 4; k0 += ADAM_BATCH) {
+		float4 pv[ADAM_BATCH], mv[ADAM_BATCH], vv[ADAM_BATCH];
+#pragma unroll
+		for (int b = 0; b < ADAM_BATCH; b++) {
+			const int r = 4 * (k0 + b) + slot;
+			if (col < ROW_F4 && r < nrows && ((row_mask >> r) & 1u)) {
+				const size_t i = base + (size_t)(4 * (k0 + b) * ROW_F4);
+				mv[b] = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg) + i);
+				vv[b] = load_stream_f4(reinterpret_cast<const float4*>(a.exp_avg_sq) + i);
+				if (!((vis_mask >> r) & 1u)) pv[b] = load_stream_f4(reinterpret_cast<const float4*>(a.param) + i);
+			}
+		}
+		GSR_WAIT_LOADS();
+#pragma unroll
+		for (int b = 0; b < ADAM_BATCH; b++) {
+			const int r = 4 * (k0 + b) + slot;
+			if (col < ROW_F4 && r < nrows && ((row_mask >> r) & 1u)) {
+				const size_t i = base + (size_t)(4 * (k0 + b) * ROW_F4);
+				float4 gv;
+				if ((vis_mask >> r) & 1u) {
+					pv[b] = s_rows[r][col];
+					const float* ax = s_aux[r];
+					gv = make_float4(ax[kc[0]] * ax[cc[0]], ax[kc[1]] * ax[cc[1]], ax[kc[2]] * ax[cc[2]], ax[kc[3]] * ax[cc[3]]);
+				} else {
+					gv = make_float4(0.f, 0.f, 0.f, 0.f);
+				}
+				rank1_vector_step(a, ss_first, pv[b], gv, mv[b], vv[b]);
+				store_stream_f4(reinterpret_cast<float4*>(a.param) + i, pv[b]);
+				store_stream_f4(reinterpret_cast<float4*>(a.exp_avg) + i, mv[b]);
+				store_stream_f4(reinterpret_cast<float4*>(a.exp_avg_sq) + i, vv[b]);
+			}
 		}
 	}
 	wave_fence();

@@ -83,6 +83,7 @@ static inline void wave_reduce10_swap_f32(const float (&v)[10], float& packed, f
 static inline float4 load_stream_f4(const float4* p) { return *p; }
 static inline void store_stream_f4(float4* p, const float4 v) { *p = v; }
 #define GSR_SCHED_BARRIER() ((void)0)
+#define GSR_WAIT_LOADS() ((void)0)
 #else
 
 // Broadcast lane `lane`'s value to the whole wave through an SGPR (v_readlane_b32): the value
@@ -156,6 +157,15 @@ __device__ __forceinline__ void store_stream_f4(float4* p, const float4 v)
 		asm volatile("" ::: "memory");     \
 		__builtin_amdgcn_sched_barrier(0); \
 	} while (0)
+
+// Every vector-memory load issued so far has delivered.  Placed behind a group of PREDICATED loads whose results are used under
+// the same predicates further down: without it the compiler cannot tell that a load it skipped is not still in flight, and it
+// puts a full s_waitcnt vmcnt(0) in front of every later load that writes one of those registers again (next pass of the
+// loop, next predicated block) -- one HBM round trip per load instead of one per group.  With it the group is issued back to
+// back and waited for once.
+// (The builtin, not inline assembly: the compiler's own wait-count bookkeeping reads the instruction and not an asm string.  gfx9
+// encoding: vmcnt = 0 in bits 3:0 and 15:14, expcnt (6:4) and lgkmcnt (11:8) at their maxima = not waited for.)
+#define GSR_WAIT_LOADS() __builtin_amdgcn_s_waitcnt(0x0F70)
 
 // Scheduling fence for intra-wave communication through LDS that relies on lock-step
 // execution (lanes read, then a leader lane writes).  The hardware issues a wave's LDS
