@@ -12,6 +12,9 @@
 #include "kernels.h"
 #include "state.h"
 #include "wave64.h"
+#ifdef GSR_EMU
+#include <atomic>
+#endif
 
 namespace gsr {
 
@@ -99,6 +102,21 @@ constexpr int LWV = LGV + 2 * LH;
 constexpr int H_UNITS = LRY * (LT / LG);   // 336
 static_assert(H_UNITS > 256 && H_UNITS <= 512, "two horizontal units per thread at most");
 
+// A 16-byte load of the vector staging path.  `vec` in gsr_l1_ssim_loss promises that every one of them is 16-byte aligned; a host
+// CPU and the device both take a load that is not, so no result would show a broken promise: the emulator build counts them
+// (gsr_emu_loss_misaligned_loads, tests/loss_cases.py).
+#ifdef GSR_EMU
+static std::atomic<long long> g_loss_misaligned_loads{0};
+static inline float4 loss_load_f4_counted(const float* p)
+{
+	if (reinterpret_cast<uintptr_t>(p) & 15) g_loss_misaligned_loads++;
+	return *reinterpret_cast<const float4*>(p);
+}
+#define LOSS_LOAD_F4(p) loss_load_f4_counted(p)
+#else
+#define LOSS_LOAD_F4(p) (*reinterpret_cast<const float4*>(p))
+#endif
+
 // Stage NA planes (row pitch W) of the tile at (x0, y0) into s[a][LRY][SP4]; plane 0 is multiplied by mask if given.
 template <int NA>
 __device__ __forceinline__ void loss_stage_tile(const float* const (&src)[NA], const float* mask, int W, int H, int vec, int x0,
@@ -114,9 +132,9 @@ __device__ __forceinline__ void loss_stage_tile(const float* const (&src)[NA], c
 			for (int a = 0; a < NA; a++) {
 				float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
 				if (in) {
-					v = *reinterpret_cast<const float4*>(src[a] + o);
+					v = LOSS_LOAD_F4(src[a] + o);
 					if (a == 0 && mask) {
-						const float4 m = *reinterpret_cast<const float4*>(mask + o);
+						const float4 m = LOSS_LOAD_F4(mask + o);
 						v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
 					}
 				}
@@ -480,6 +498,11 @@ densify_stats_kernel(int P, const float* __restrict__ dL_dmean2D, const int* __r
 using namespace gsr;
 
 extern "C" {
+
+#ifdef GSR_EMU
+// (emulator build only) the number of misaligned 16-byte staging loads since the last call
+long long gsr_emu_loss_misaligned_loads() { return g_loss_misaligned_loads.exchange(0); }
+#endif
 
 size_t gsr_loss_scratch_bytes(int width, int height)
 {
