@@ -464,6 +464,21 @@ size_t gsr_loss_scratch_bytes(int width, int height);
 int gsr_l1_ssim_loss(const float* rendered, const float* gt, const float* mask, int width, int height,
                      float lambda_dssim, float* grad_rendered, float* loss, char* scratch, void* stream);
 
+/* The same loss behind a per-keyframe exposure: a [3,4] affine colour map E (row-major, ON THE DEVICE: it is a tensor being
+ * optimised, nothing is read on the host) between render and loss, upstream 3DGS's image.permute(1,2,0) @ E[:3,:3] + E[:3,3]:
+ *   x_c = (r_0 E[0][c] + r_1 E[1][c] + r_2 E[2][c] + E[c][3]) * mask_c     (summed in this order; gt is not mapped)
+ *   loss as above on x;   G_c = dloss/dx_c * mask_c;   grad_rendered_k = sum_c E[k][c] G_c
+ *   grad_exposure[k][c] = sum_p r_k(p) G_c(p)  (c < 3),   grad_exposure[c][3] = sum_p G_c(p)     (all 12 written)
+ * Three launches, no atomics: the same inputs give the same bits.  With E = eye(3,4) loss and grad_rendered are those of
+ * gsr_l1_ssim_loss bit for bit.  scratch: gsr_loss_exposure_scratch_bytes(width, height) device bytes. */
+size_t gsr_loss_exposure_scratch_bytes(int width, int height);
+int gsr_l1_ssim_loss_exposure(const float* rendered, const float* gt, const float* mask, int width, int height,
+                              float lambda_dssim, const float* exposure, float* grad_rendered, float* grad_exposure,
+                              float* loss, char* scratch, void* stream);
+/* out_c = image_0 E[0][c] + image_1 E[1][c] + image_2 E[2][c] + E[c][3] per pixel of a [3,H,W] image, for evaluation renders of
+ * a keyframe that carries an exposure; no clamping; out may be image. */
+int gsr_apply_exposure(const float* image, const float* exposure, int width, int height, float* out, void* stream);
+
 /* Depth L1 loss of an RGB-D keyframe against the rendered depth map (gsr_forward_args.out_depth), Photo-SLAM's
  * RGBD.min_depth / RGBD.max_depth as the sensor's valid range:
  *   loss = weight * sum_{valid p} |depth[p] - gt_depth[p]| / (H W),   valid = min_depth < gt_depth[p] < max_depth

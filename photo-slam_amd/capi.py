@@ -147,6 +147,7 @@ EXPORTED_SYMBOLS = [
     "gsr_host_wait_stats", "gsr_binning_tile_first", "gsr_densify_morton_scratch_bytes",
     "gsr_binning_bytes_for", "gsr_image_bytes_for", "gsr_last_forward_only",
     "gsr_depth_loss_scratch_bytes", "gsr_depth_l1_loss", "gsr_pose_grad_scratch_bytes",
+    "gsr_loss_exposure_scratch_bytes", "gsr_l1_ssim_loss_exposure", "gsr_apply_exposure",
 ]
 
 _libs = {}
@@ -208,6 +209,12 @@ def load(path=None):
     L.gsr_loss_scratch_bytes.argtypes = [i32, i32]
     L.gsr_l1_ssim_loss.restype = i32
     L.gsr_l1_ssim_loss.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]
+    L.gsr_loss_exposure_scratch_bytes.restype = sz
+    L.gsr_loss_exposure_scratch_bytes.argtypes = [i32, i32]
+    L.gsr_l1_ssim_loss_exposure.restype = i32
+    L.gsr_l1_ssim_loss_exposure.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp]
+    L.gsr_apply_exposure.restype = i32
+    L.gsr_apply_exposure.argtypes = [vp, vp, i32, i32, vp, vp]
     L.gsr_depth_loss_scratch_bytes.restype = sz
     L.gsr_depth_loss_scratch_bytes.argtypes = [i32, i32]
     L.gsr_depth_l1_loss.restype = i32

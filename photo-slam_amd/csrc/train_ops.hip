@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "state.h"
 #include "wave64.h"
+#include <type_traits>
 #ifdef GSR_EMU
 #include <atomic>
 #endif
@@ -118,7 +119,9 @@ static inline float4 loss_load_f4_counted(const float* p)
 #endif
 
 // Stage NA planes (row pitch W) of the tile at (x0, y0) into s[a][LRY][SP4]; plane 0 is multiplied by mask if given.
-template <int NA>
+// EXPO: the same code as an instantiation of its own for loss_bwd_kernel<true> -- with ONE instantiation inlined into both backward
+// kernels the compiler schedules the plain kernel's staging differently from the code without the exposure feature.
+template <int NA, bool EXPO = false>
 __device__ __forceinline__ void loss_stage_tile(const float* const (&src)[NA], const float* mask, int W, int H, int vec, int x0,
                                                 int y0, float4* s, int tid)
 {
@@ -161,6 +164,73 @@ __device__ __forceinline__ void loss_stage_tile(const float* const (&src)[NA], c
 	}
 }
 
+// ---- per-keyframe exposure (gsr_l1_ssim_loss_exposure): x_c = (r_0 E[0][c] + r_1 E[1][c] + r_2 E[2][c] + E[c][3]) m_c, E [3,4]
+// row-major on the device.  Instantiations of their own (loss_fwd_kernel<true>, loss_bwd_kernel<true>; their parameters: LossParams
+// with three pointers behind it), so that the plain kernels are the same code with the same arguments as without the feature.
+struct LossExposureParams : LossParams {
+	const float* E;          // [12]
+	float* xpartial;         // [4][nblocks]: per workgroup (channel c) sum r_0 G_c, sum r_1 G_c, sum r_2 G_c, sum G_c
+	float* grad_exposure;    // [12]
+};
+template <bool EXPO> using LossKernelParams = std::conditional_t<EXPO, LossExposureParams, LossParams>;
+
+// One element of the map, in the order of the contract and without contraction: pass 1 (both staging paths), pass 2 and
+// gsr_apply_exposure produce the same bits from the same inputs, whatever surrounds the call (see adam_update).
+__device__ __forceinline__ float exposure_map(float r0, float r1, float r2, float e0, float e1, float e2, float e3)
+{
+#pragma clang fp contract(off)
+	return r0 * e0 + r1 * e1 + r2 * e2 + e3;
+}
+
+// loss_stage_tile<2> for the exposure kernels: plane 0 is the mapped (and masked) rendered image of channel ch -- three rendered
+// loads per element, ONE staged plane (a fourth staged plane would not fit the 30 KB region) -- plane 1 is gt.
+__device__ __forceinline__ void loss_stage_tile_exposure(const float* rendered, const float* gt, const float* mask, size_t plane,
+                                                         const float (&e)[4], int W, int H, int vec, int x0, int y0, float4* s, int tid)
+{
+	const float* r0 = rendered;
+	const float* r1 = rendered + plane;
+	const float* r2 = rendered + 2 * plane;
+	if (vec) {
+		for (int i = tid; i < LRY * SW4; i += 256) {
+			const int r = i / SW4, q = i - r * SW4;
+			const int gx = x0 - SX0 + 4 * q, gy = y0 - LH + r;
+			const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
+			const size_t o = in ? (size_t)gy * W + gx : 0;
+			float4 v = make_float4(0.f, 0.f, 0.f, 0.f), y = make_float4(0.f, 0.f, 0.f, 0.f);
+			if (in) {
+				const float4 a = LOSS_LOAD_F4(r0 + o), b = LOSS_LOAD_F4(r1 + o), c = LOSS_LOAD_F4(r2 + o);
+				y = LOSS_LOAD_F4(gt + o);
+				v.x = exposure_map(a.x, b.x, c.x, e[0], e[1], e[2], e[3]);
+				v.y = exposure_map(a.y, b.y, c.y, e[0], e[1], e[2], e[3]);
+				v.z = exposure_map(a.z, b.z, c.z, e[0], e[1], e[2], e[3]);
+				v.w = exposure_map(a.w, b.w, c.w, e[0], e[1], e[2], e[3]);
+				if (mask) {
+					const float4 m = LOSS_LOAD_F4(mask + o);
+					v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
+				}
+			}
+			s[r * SP4 + q] = v;
+			s[(LRY + r) * SP4 + q] = y;
+		}
+	} else {
+		float* sf = reinterpret_cast<float*>(s);
+		for (int i = tid; i < LRY * SW4 * 4; i += 256) {
+			const int r = i / (SW4 * 4), c = i - r * (SW4 * 4);
+			const int gx = x0 - SX0 + c, gy = y0 - LH + r;
+			const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
+			const size_t o = in ? (size_t)gy * W + gx : 0;
+			float v = 0.f, y = 0.f;
+			if (in) {
+				v = exposure_map(r0[o], r1[o], r2[o], e[0], e[1], e[2], e[3]);
+				if (mask) v *= mask[o];
+				y = gt[o];
+			}
+			sf[r * (SP4 * 4) + c] = v;
+			sf[(LRY + r) * (SP4 * 4) + c] = y;
+		}
+	}
+}
+
 // the aligned 20 floats around the 14-float window of horizontal unit (r, g): window element t sits at [3 + t]
 __device__ __forceinline__ void loss_load_window(const float4* plane, int r, int g, float (&w)[20])
 {
@@ -172,8 +242,10 @@ __device__ __forceinline__ void loss_load_window(const float4* plane, int r, int
 }
 
 // Pass 1: window statistics -> SSIM map value + the three derivative maps, and L1 / SSIM partial sums.
+// EXPO: the staging applies the exposure map as it loads (loss_stage_tile_exposure); everything behind it is the same code.
+template <bool EXPO>
 __global__ void __launch_bounds__(256)
-loss_fwd_kernel(const LossParams p)
+loss_fwd_kernel(const LossKernelParams<EXPO> p)
 {
 	// staged x, y: 2 x 42 x 13 float4; then the five filtered maps: 5 x 42 x 9 float4 in the same memory
 	__shared__ float4 s_mem[5 * LRY * HP4];
@@ -183,7 +255,11 @@ loss_fwd_kernel(const LossParams p)
 	if (!loss_tile(p, t, ch, x0, y0)) return;   // (workgroup-uniform)
 	const size_t plane = (size_t)p.W * p.H;
 	const int tid = (int)threadIdx.x;
-	{
+	if constexpr (EXPO) {
+		const float e[4] = {p.E[ch], p.E[4 + ch], p.E[8 + ch], p.E[4 * ch + 3]};
+		loss_stage_tile_exposure(p.rendered, p.gt + ch * plane, p.mask ? p.mask + ch * plane : nullptr, plane, e, p.W, p.H, p.vec,
+		                         x0, y0, s_mem, tid);
+	} else {
 		const float* const src[2] = {p.rendered + ch * plane, p.gt + ch * plane};
 		loss_stage_tile<2>(src, p.mask ? p.mask + ch * plane : nullptr, p.W, p.H, p.vec, x0, y0, s_mem, tid);
 	}
@@ -317,8 +393,11 @@ __device__ __forceinline__ void loss_finalize(const LossParams& p, float* s_red)
 }
 
 // Pass 2: dL/dx = G*(dL/dmu1) + 2x G*(dL/de11) + y G*(dL/de12) + (1-lambda)/N sign(x-y), times mask.
+// EXPO: x is recomputed from the three rendered planes at the thread's pixel, G_c = dL/dx_c m_c is written instead of the final
+// gradient (exposure_mix_kernel mixes it per pixel), and the workgroup leaves its four partial sums of grad_exposure's column c.
+template <bool EXPO>
 __global__ void __launch_bounds__(256)
-loss_bwd_kernel(const LossParams p)
+loss_bwd_kernel(const LossKernelParams<EXPO> p)
 {
 	// staged derivative maps: 3 x 42 x 13 float4; then their filtered rows: 3 x 42 x 9 float4 in the same memory
 	__shared__ float4 s_mem[3 * LRY * SP4];
@@ -329,7 +408,7 @@ loss_bwd_kernel(const LossParams p)
 	const int tid = (int)threadIdx.x;
 	{
 		const float* const src[3] = {p.dmaps + (0 * 3 + ch) * plane, p.dmaps + (1 * 3 + ch) * plane, p.dmaps + (2 * 3 + ch) * plane};
-		loss_stage_tile<3>(src, nullptr, p.W, p.H, p.vec, x0, y0, s_mem, tid);
+		loss_stage_tile<3, EXPO>(src, nullptr, p.W, p.H, p.vec, x0, y0, s_mem, tid);
 	}
 	__syncthreads();
 	auto h_unit = [&](const float (&w)[20], float4& out) {
@@ -390,21 +469,97 @@ loss_bwd_kernel(const LossParams p)
 		}
 		const int gx = x0 + c;
 		const float l1w = (1.0f - p.lambda_dssim) * inv_n;
+		if constexpr (EXPO) {
+			const float e0 = p.E[ch], e1 = p.E[4 + ch], e2 = p.E[8 + ch], e3 = p.E[4 * ch + 3];
+			float xs[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-		for (int o = 0; o < LGV; o++) {
-			const int gy = y0 + r0 + o;
-			if (gx < p.W && gy < p.H) {
-				const size_t oo = ch * plane + (size_t)gy * p.W + gx;
-				const float m = p.mask ? p.mask[oo] : 1.f;
-				const float xv = p.rendered[oo] * m, yv = p.gt[oo];
-				const float d = xv - yv;
-				const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-				const float gx_ = cv[0][o] + 2.f * xv * cv[1][o] + yv * cv[2][o] + l1w * sgn;
-				p.grad[oo] = gx_ * m;
+			for (int o = 0; o < LGV; o++) {
+				const int gy = y0 + r0 + o;
+				if (gx < p.W && gy < p.H) {
+					const size_t po = (size_t)gy * p.W + gx, oo = ch * plane + po;
+					const float m = p.mask ? p.mask[oo] : 1.f;
+					const float ra = p.rendered[po], rb = p.rendered[plane + po], rc = p.rendered[2 * plane + po];
+					const float xv = exposure_map(ra, rb, rc, e0, e1, e2, e3) * m, yv = p.gt[oo];   // (the mask as the plain kernel applies it)
+					const float d = xv - yv;
+					const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+					const float gx_ = cv[0][o] + 2.f * xv * cv[1][o] + yv * cv[2][o] + l1w * sgn;
+					const float G = gx_ * m;
+					p.grad[oo] = G;
+					xs[0] += ra * G; xs[1] += rb * G; xs[2] += rc * G; xs[3] += G;
+				}
+			}
+#pragma unroll
+			for (int k = 0; k < 4; k++) {
+				const float sk = block_sum_256(xs[k], s_red);
+				if (tid == 0) p.xpartial[k * p.nblocks + t] = sk;   // (indexed by tile, as p.partial)
+			}
+		} else {
+#pragma unroll
+			for (int o = 0; o < LGV; o++) {
+				const int gy = y0 + r0 + o;
+				if (gx < p.W && gy < p.H) {
+					const size_t oo = ch * plane + (size_t)gy * p.W + gx;
+					const float m = p.mask ? p.mask[oo] : 1.f;
+					const float xv = p.rendered[oo] * m, yv = p.gt[oo];
+					const float d = xv - yv;
+					const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+					const float gx_ = cv[0][o] + 2.f * xv * cv[1][o] + yv * cv[2][o] + l1w * sgn;
+					p.grad[oo] = gx_ * m;
+				}
 			}
 		}
 	}
 	if (t == 0) loss_finalize(p, s_red);
+}
+
+// Pass 3 of the exposure loss, element-wise: grad_rendered_k(p) = sum_c E[k][c] G_c(p), in place over G (a thread reads the three
+// G of its pixels before it writes them).  Workgroup 0 then adds the [4][nblocks] partial sums of pass 2 to the 12 entries of
+// grad_exposure in tile order, as loss_finalize does for the loss: [k][c] (c < 3) and [c][3] come from the tiles of channel c.
+constexpr int MIX_MAX_BLOCKS = 2048;
+static inline int stream_blocks(size_t n) { return (int)((n + 255) / 256 < (size_t)MIX_MAX_BLOCKS ? (n + 255) / 256 : (size_t)MIX_MAX_BLOCKS); }
+__global__ void __launch_bounds__(256)
+exposure_mix_kernel(float* __restrict__ grad, size_t plane, const float* __restrict__ E, const float* __restrict__ xpartial,
+                    float* __restrict__ grad_exposure, int nblocks)
+{
+	__shared__ float s_red[4];
+	float e[9];
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+#pragma unroll
+		for (int c = 0; c < 3; c++) e[3 * k + c] = E[4 * k + c];
+	const size_t stride = (size_t)gridDim.x * 256;
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < plane; i += stride) {
+		const float g0 = grad[i], g1 = grad[plane + i], g2 = grad[2 * plane + i];
+		grad[i] = exposure_map(g0, g1, g2, e[0], e[1], e[2], 0.f);
+		grad[plane + i] = exposure_map(g0, g1, g2, e[3], e[4], e[5], 0.f);
+		grad[2 * plane + i] = exposure_map(g0, g1, g2, e[6], e[7], e[8], 0.f);
+	}
+	if (blockIdx.x == 0) {
+		const int per_ch = nblocks / 3;
+		for (int c = 0; c < 3; c++)
+			for (int k = 0; k < 4; k++) {
+				float a = 0.f;
+				for (int i = (int)threadIdx.x; i < per_ch; i += 256) a += xpartial[k * nblocks + c * per_ch + i];
+				const float sum = block_sum_256(a, s_red);
+				if (threadIdx.x == 0) grad_exposure[k < 3 ? 4 * k + c : 4 * c + 3] = sum;
+			}
+	}
+}
+
+// gsr_apply_exposure: out_c = r_0 E[0][c] + r_1 E[1][c] + r_2 E[2][c] + E[c][3] per pixel, no clamping; out may be the image.
+__global__ void __launch_bounds__(256)
+apply_exposure_kernel(const float* image, const float* __restrict__ E, size_t plane, float* out)
+{
+	float e[12];
+#pragma unroll
+	for (int k = 0; k < 12; k++) e[k] = E[k];
+	const size_t stride = (size_t)gridDim.x * 256;
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < plane; i += stride) {
+		const float r0 = image[i], r1 = image[plane + i], r2 = image[2 * plane + i];
+		out[i] = exposure_map(r0, r1, r2, e[0], e[4], e[8], e[3]);
+		out[plane + i] = exposure_map(r0, r1, r2, e[1], e[5], e[9], e[7]);
+		out[2 * plane + i] = exposure_map(r0, r1, r2, e[2], e[6], e[10], e[11]);
+	}
 }
 
 // ------------------------------------------------------------------ Adam
@@ -512,12 +667,10 @@ size_t gsr_loss_scratch_bytes(int width, int height)
 	return (9 * plane + 2 * nb + 64) * sizeof(float);
 }
 
-int gsr_l1_ssim_loss(const float* rendered, const float* gt, const float* mask, int width, int height, float lambda_dssim,
-                     float* grad_rendered, float* loss, char* scratch, void* stream_)
+// the kernel parameters both loss entries share
+static void loss_params(LossParams& p, const float* rendered, const float* gt, const float* mask, int width, int height,
+                        float lambda_dssim, float* grad_rendered, float* loss, char* scratch)
 {
-	if (!rendered || !gt || !grad_rendered || !loss || !scratch || width <= 0 || height <= 0) return GSR_ERR_INVALID_ARG;
-	hipStream_t stream = (hipStream_t)stream_;
-	LossParams p;
 	p.rendered = rendered; p.gt = gt; p.mask = mask; p.W = width; p.H = height; p.lambda_dssim = lambda_dssim;
 	// 16-byte staging: every row of every plane (inputs and the derivative maps in `scratch`) starts on a 16-byte boundary
 	p.vec = (width % 4 == 0) && !((reinterpret_cast<uintptr_t>(rendered) | reinterpret_cast<uintptr_t>(gt) |
@@ -543,8 +696,57 @@ int gsr_l1_ssim_loss(const float* rendered, const float* gt, const float* mask, 
 	p.partial = p.dmaps + 9 * plane;
 	p.grad = grad_rendered;
 	p.loss = loss;
-	GSR_LAUNCH(loss_fwd_kernel, loss_grid(p.nblocks), 256, stream, p);
-	GSR_LAUNCH(loss_bwd_kernel, loss_grid(p.nblocks), 256, stream, p);
+}
+
+int gsr_l1_ssim_loss(const float* rendered, const float* gt, const float* mask, int width, int height, float lambda_dssim,
+                     float* grad_rendered, float* loss, char* scratch, void* stream_)
+{
+	if (!rendered || !gt || !grad_rendered || !loss || !scratch || width <= 0 || height <= 0) return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	LossParams p;
+	loss_params(p, rendered, gt, mask, width, height, lambda_dssim, grad_rendered, loss, scratch);
+	GSR_LAUNCH(loss_fwd_kernel<false>, loss_grid(p.nblocks), 256, stream, p);
+	GSR_LAUNCH(loss_bwd_kernel<false>, loss_grid(p.nblocks), 256, stream, p);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+size_t gsr_loss_exposure_scratch_bytes(int width, int height)
+{
+	if (width <= 0 || height <= 0) return 0;
+	const size_t nb = (size_t)div_up(width, LT) * div_up(height, LTY) * 3;
+	return gsr_loss_scratch_bytes(width, height) + 4 * nb * sizeof(float);
+}
+
+int gsr_l1_ssim_loss_exposure(const float* rendered, const float* gt, const float* mask, int width, int height, float lambda_dssim,
+                              const float* exposure, float* grad_rendered, float* grad_exposure, float* loss, char* scratch,
+                              void* stream_)
+{
+	if (!rendered || !gt || !exposure || !grad_rendered || !grad_exposure || !loss || !scratch || width <= 0 || height <= 0)
+		return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	LossExposureParams p;
+	loss_params(p, rendered, gt, mask, width, height, lambda_dssim, grad_rendered, loss, scratch);
+	p.E = exposure;
+	// behind the plain entry's region: 9 planes, [2][nblocks] partial sums and its 64 floats of slack
+	p.xpartial = reinterpret_cast<float*>(scratch + gsr_loss_scratch_bytes(width, height));
+	p.grad_exposure = grad_exposure;
+	const size_t plane = (size_t)width * height;
+	const int mix_blocks = stream_blocks(plane);
+	GSR_LAUNCH(loss_fwd_kernel<true>, loss_grid(p.nblocks), 256, stream, p);
+	GSR_LAUNCH(loss_bwd_kernel<true>, loss_grid(p.nblocks), 256, stream, p);
+	GSR_LAUNCH(exposure_mix_kernel, mix_blocks, 256, stream, grad_rendered, plane, p.E, p.xpartial, p.grad_exposure, p.nblocks);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+int gsr_apply_exposure(const float* image, const float* exposure, int width, int height, float* out, void* stream_)
+{
+	if (!image || !exposure || !out || width <= 0 || height <= 0) return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	const size_t plane = (size_t)width * height;
+	const int blocks = stream_blocks(plane);
+	GSR_LAUNCH(apply_exposure_kernel, blocks, 256, stream, image, exposure, plane, out);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

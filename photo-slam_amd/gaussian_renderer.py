@@ -1,6 +1,7 @@
 """GaussianRenderer::render (include/gaussian_renderer.h:29-42, src/gaussian_renderer.cpp:23-149)."""
 import os
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -25,6 +26,13 @@ class GaussianKeyframe:
     world_view_transform_: torch.Tensor
     full_proj_transform_: torch.Tensor
     camera_center_: torch.Tensor
+    # Exposure compensation (include/gsr.h: gsr_l1_ssim_loss_exposure): the keyframe's [3,4] affine colour map between render and
+    # loss, float32 on the device; None = no compensation, the plain loss kernels.  It belongs to the keyframe, not to the map:
+    # its Adam moments and its own step count travel with it (TrainStep.optimize_exposure_).
+    exposure_: Optional[torch.Tensor] = None
+    exposure_exp_avg_: Optional[torch.Tensor] = None
+    exposure_exp_avg_sq_: Optional[torch.Tensor] = None
+    exposure_step_: int = 0
 
     @classmethod
     def from_camera(cls, cam, device):

@@ -42,6 +42,11 @@ struct GaussianKeyframe {
 	int image_height_ = 0, image_width_ = 0;
 	float FoVx_ = 0.f, FoVy_ = 0.f;
 	torch::Tensor world_view_transform_, full_proj_transform_, camera_center_;
+	// Exposure compensation (include/gsr.h: gsr_l1_ssim_loss_exposure): the keyframe's [3,4] affine colour map between render and
+	// loss, float32 on the device; undefined = no compensation, the plain loss kernels.  It belongs to the keyframe, not to the
+	// map: its Adam moments and its own step count travel with it (TrainStep::optimize_exposure_).
+	torch::Tensor exposure_, exposure_exp_avg_, exposure_exp_avg_sq_;
+	int exposure_step_ = 0;
 };
 
 // One Adam parameter group of the fused optimizer (gsr_adam_step)
@@ -230,7 +235,11 @@ public:
 	bool densifyDue() const;
 	torch::Tensor trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask)
 	{
-		if (process_group_) return trainForOneIterationDataParallel(kf, gt_image, mask);
+		if (process_group_) {
+			if (kf->exposure_.defined() || optimize_exposure_)
+				throw std::runtime_error("TrainStep: exposure compensation is not supported with a process group");
+			return trainForOneIterationDataParallel(kf, gt_image, mask);
+		}
 		auto loss = renderAndBackward(kf, gt_image, mask);
 		finishOneIteration();
 		return loss;
@@ -243,6 +252,8 @@ public:
 		if (process_group_) {
 			if (usesDepthLoss(gt_depth))
 				throw std::runtime_error("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)");
+			if (kf->exposure_.defined() || optimize_exposure_)
+				throw std::runtime_error("TrainStep: exposure compensation is not supported with a process group");
 			return trainForOneIterationDataParallel(kf, gt_image, mask);
 		}
 		auto loss = renderAndBackward(kf, gt_image, mask, gt_depth);
@@ -255,6 +266,19 @@ public:
 	float depth_min_ = 0.0f;
 	float depth_max_ = std::numeric_limits<float>::infinity();
 	bool usesDepthLoss(const torch::Tensor& gt_depth) const { return gt_depth.defined() && depth_loss_weight_ != 0.0f; }
+	// Per-keyframe exposure compensation (upstream 3DGS's per-image exposure): a keyframe that carries exposure_ has it applied
+	// between render and loss, inside the loss kernels, in renderAndBackward and refinePose.  optimize_exposure_: the keyframe of a
+	// train step gets the identity at first use and takes one Adam step on its 12 floats in finishEnd() (gsr_adam_step,
+	// the model's betas and eps; densifying iterations included), at a learning rate that falls log-linearly from exposure_lr_init_
+	// to exposure_lr_final_ over exposure_lr_max_steps_ (< 0: opt_.iterations_) of the keyframe's OWN steps.  refinePose applies
+	// a keyframe's exposure and never optimises it.  Not with a process group: throws.
+	bool optimize_exposure_ = false;
+	float exposure_lr_init_ = 0.01f, exposure_lr_final_ = 0.001f;
+	int exposure_lr_max_steps_ = -1;
+	double exposureLearningRate(int step) const;   // of a keyframe's `step`-th exposure step (1-based)
+	std::shared_ptr<GaussianKeyframe> exposure_kf_;   // the keyframe of the last backward pass and the gradient of its exposure,
+	torch::Tensor exposure_grad_;                     // until finishEnd() has taken the step
+	void finishExposure();
 	// Keyframe batches, one keyframe per rank: with a process group set, trainForOneIteration() is the
 	// data-parallel step -- render + backward of THIS rank's keyframe, the gradient exchange over c10d (RCCL on the GPU boxes:
 	// ViewFactoredExchange by default, the plain GradientReduction otherwise; host/include/keyframe_batch_exchange.h), the
@@ -317,7 +341,8 @@ public:
 	// (GSR_FORWARD_ONLY) into a second workspace of its own -- a view between a training forward and its backward must not
 	// overwrite the buffers that forward saved -- with lazily stepped SH rows read as they are: no flush, no counter advanced,
 	// nothing of the model touched.  Returns the [3,H,W] image.
-	torch::Tensor renderView(std::shared_ptr<GaussianKeyframe> kf);
+	// apply_exposure: the image behind the keyframe's exposure_ (what the loss compares with the target), if it has one
+	torch::Tensor renderView(std::shared_ptr<GaussianKeyframe> kf, bool apply_exposure = false);
 	// ... with the depth and alpha maps: (image, depth, alpha), [H,W] each (GaussianRenderer::renderWithDepth)
 	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf);
 	RasterWorkspace view_workspace_;

@@ -52,6 +52,13 @@ torch::Tensor ssim(
 //   (1 - lambda_dssim) * l1_loss(rendered * mask, gt) + lambda_dssim * (1 - ssim(rendered * mask, gt))
 // mask: undefined / empty = all ones.  is_root: the caller promises to call backward() on this very value.
 torch::Tensor fused_l1_ssim(torch::Tensor rendered, torch::Tensor gt, torch::Tensor mask, float lambda_dssim, bool is_root = false);
+// (extension) ... behind a keyframe's exposure: a [3,4] float32 affine colour map on the device, applied to the rendered image inside
+// the loss kernels (include/gsr.h: gsr_l1_ssim_loss_exposure); differentiable in rendered AND exposure.
+torch::Tensor fused_l1_ssim_exposure(torch::Tensor rendered, torch::Tensor gt, torch::Tensor mask, float lambda_dssim,
+                                     torch::Tensor exposure, bool is_root = false);
+// (extension) image_0 E[0][c] + image_1 E[1][c] + image_2 E[2][c] + E[c][3] per pixel of a [3,H,W] image (gsr_apply_exposure): what
+// the loss compares with the target, for evaluation renders of a keyframe with an exposure.  No clamping, no gradient.
+torch::Tensor apply_exposure(torch::Tensor image, torch::Tensor exposure);
 // (extension) the depth L1 loss of an RGB-D keyframe (csrc/train_ops.hip, gsr_depth_l1_loss; deterministic):
 //   weight * sum over the pixels with min_depth < gt_depth < max_depth of |depth - gt_depth|, divided by H W
 // depth, gt_depth: [H,W] float32 on one device; differentiable in depth.

@@ -54,6 +54,40 @@ public:
 	}
 };
 
+// the same value behind a [3,4] exposure map; gradients for `rendered` and `exposure`
+class FusedL1SSIMExposureFunction : public torch::autograd::Function<FusedL1SSIMExposureFunction> {
+public:
+	static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor rendered, torch::Tensor gt,
+	                             torch::Tensor mask, double lambda_dssim, bool is_root, torch::Tensor exposure)
+	{
+		ctx->saved_data["is_root"] = is_root;
+		if (exposure.dim() != 2 || exposure.size(0) != 3 || exposure.size(1) != 4 || exposure.scalar_type() != torch::kFloat32 ||
+		    exposure.device() != rendered.device())
+			throw std::runtime_error("fused_l1_ssim_exposure: exposure must be a float32 [3, 4] tensor on the device of the rendered image");
+		auto r = rendered.contiguous(), g = gt.contiguous(), e = exposure.contiguous();
+		torch::Tensor m = mask.defined() && mask.numel() ? mask.contiguous() : torch::Tensor();
+		const int H = static_cast<int>(r.size(-2)), W = static_cast<int>(r.size(-1));
+		auto grad = torch::empty_like(r);
+		auto grad_e = torch::empty_like(e);
+		auto loss = torch::empty({1}, r.options());
+		auto scratch = torch::empty({static_cast<int64_t>(gsr_loss_exposure_scratch_bytes(W, H))}, r.options().dtype(torch::kByte));
+		check(gsr_l1_ssim_loss_exposure(r.data_ptr<float>(), g.data_ptr<float>(), m.defined() ? m.data_ptr<float>() : nullptr, W, H,
+		                                static_cast<float>(lambda_dssim), e.data_ptr<float>(), grad.data_ptr<float>(),
+		                                grad_e.data_ptr<float>(), loss.data_ptr<float>(), reinterpret_cast<char*>(scratch.data_ptr()),
+		                                stream_of(r)),
+		      "gsr_l1_ssim_loss_exposure");
+		ctx->save_for_backward({grad, grad_e});
+		return loss[0];
+	}
+	static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::tensor_list go)
+	{
+		auto saved = ctx->get_saved_variables();
+		const torch::Tensor none;
+		if (ctx->saved_data["is_root"].toBool()) return {saved[0], none, none, none, none, saved[1]};
+		return {saved[0] * go[0], none, none, none, none, saved[1] * go[0]};
+	}
+};
+
 class DepthL1Function : public torch::autograd::Function<DepthL1Function> {
 public:
 	static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth, torch::Tensor gt_depth, double weight,
@@ -104,6 +138,26 @@ torch::Tensor fused_l1_ssim(torch::Tensor rendered, torch::Tensor gt, torch::Ten
 {
 	if (!mask.defined()) mask = torch::empty({0}, gt.options());   // (autograd::Function::apply needs every tensor argument defined)
 	return FusedL1SSIMFunction::apply(rendered, gt, mask, static_cast<double>(lambda_dssim), is_root);
+}
+
+torch::Tensor fused_l1_ssim_exposure(torch::Tensor rendered, torch::Tensor gt, torch::Tensor mask, float lambda_dssim,
+                                     torch::Tensor exposure, bool is_root)
+{
+	if (!mask.defined()) mask = torch::empty({0}, gt.options());
+	return FusedL1SSIMExposureFunction::apply(rendered, gt, mask, static_cast<double>(lambda_dssim), is_root, exposure);
+}
+
+torch::Tensor apply_exposure(torch::Tensor image, torch::Tensor exposure)
+{
+	if (image.dim() != 3 || image.size(0) != 3 || exposure.dim() != 2 || exposure.size(0) != 3 || exposure.size(1) != 4 ||
+	    image.scalar_type() != torch::kFloat32 || exposure.scalar_type() != torch::kFloat32 || image.device() != exposure.device())
+		throw std::runtime_error("apply_exposure: a float32 [3, H, W] image and a float32 [3, 4] exposure on one device");
+	auto r = image.detach().contiguous(), e = exposure.detach().contiguous();
+	auto out = torch::empty_like(r);
+	check(gsr_apply_exposure(r.data_ptr<float>(), e.data_ptr<float>(), static_cast<int>(r.size(2)), static_cast<int>(r.size(1)),
+	                         out.data_ptr<float>(), stream_of(r)),
+	      "gsr_apply_exposure");
+	return out;
 }
 
 torch::Tensor depth_l1(torch::Tensor depth, torch::Tensor gt_depth, float weight, float min_depth, float max_depth)

@@ -75,6 +75,12 @@ torch::Tensor l1_ssim_loss(torch::Tensor rendered, torch::Tensor gt, torch::Tens
 {
 	return fusedL1SSIMLoss(rendered, gt, mask, (float)lambda_dssim);
 }
+torch::Tensor l1_ssim_loss_exposure(torch::Tensor rendered, torch::Tensor gt, torch::Tensor mask, double lambda_dssim,
+                                    torch::Tensor exposure, bool is_root)
+{
+	return loss_utils::fused_l1_ssim_exposure(rendered, gt, mask, (float)lambda_dssim, exposure, is_root);
+}
+torch::Tensor apply_exposure(torch::Tensor image, torch::Tensor exposure) { return loss_utils::apply_exposure(image, exposure); }
 
 torch::Tensor transform_points(torch::Tensor points, torch::Tensor transformmatrix)
 {
@@ -191,6 +197,47 @@ torch::Tensor trainer_render_view(int64_t h, torch::Tensor view, torch::Tensor p
 {
 	return get(h)->renderView(make_kf(view, proj, campos, fovx, fovy, H, W));
 }
+// ---- keyframes that carry an exposure.  The ops build a keyframe per call, so its exposure state travels as arguments:
+// state = {exposure [3,4], exp_avg, exp_avg_sq}, each possibly empty (= undefined), and the keyframe's step count; tensors given are
+// updated in place, and the state after the call comes back (an exposure created at first use among it).
+std::shared_ptr<GaussianKeyframe> with_exposure(std::shared_ptr<GaussianKeyframe> kf, const std::vector<torch::Tensor>& state, int64_t step)
+{
+	TORCH_CHECK(state.size() == 3, "exposure state: {exposure, exp_avg, exp_avg_sq}");
+	if (state[0].numel()) kf->exposure_ = state[0];
+	if (state[1].numel()) kf->exposure_exp_avg_ = state[1];
+	if (state[2].numel()) kf->exposure_exp_avg_sq_ = state[2];
+	kf->exposure_step_ = (int)step;
+	return kf;
+}
+// TrainStep::trainForOneIteration on such a keyframe: (loss, exposure, exp_avg, exp_avg_sq, [step])
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int64_t> trainer_train_exposure(
+    int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx, double fovy, int64_t H, int64_t W,
+    torch::Tensor gt, torch::Tensor mask, std::vector<torch::Tensor> state, int64_t step)
+{
+	auto kf = with_exposure(make_kf(view, proj, campos, fovx, fovy, H, W), state, step);
+	auto loss = get(h)->trainForOneIteration(kf, gt, mask).detach();
+	auto or_empty = [&](const torch::Tensor& t) { return t.defined() ? t : torch::empty({0}, gt.options()); };
+	return std::make_tuple(loss, or_empty(kf->exposure_), or_empty(kf->exposure_exp_avg_), or_empty(kf->exposure_exp_avg_sq_),
+	                       (int64_t)kf->exposure_step_);
+}
+torch::Tensor trainer_render_view_exposure(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx,
+                                           double fovy, int64_t H, int64_t W, torch::Tensor exposure, bool apply_exposure)
+{
+	auto kf = make_kf(view, proj, campos, fovx, fovy, H, W);
+	if (exposure.numel()) kf->exposure_ = exposure;
+	return get(h)->renderView(kf, apply_exposure);
+}
+std::tuple<torch::Tensor, torch::Tensor> trainer_refine_pose_exposure(int64_t h, torch::Tensor view, torch::Tensor proj,
+                                                                      torch::Tensor campos, double fovx, double fovy, int64_t H,
+                                                                      int64_t W, torch::Tensor gt, torch::Tensor mask,
+                                                                      int64_t iterations, double lr_translation, double lr_rotation,
+                                                                      torch::Tensor exposure)
+{
+	auto kf = make_kf(view, proj, campos, fovx, fovy, H, W);
+	if (exposure.numel()) kf->exposure_ = exposure;
+	return get(h)->refinePose(kf, gt, mask, (int)iterations, lr_translation, lr_rotation);
+}
+double trainer_exposure_lr(int64_t h, int64_t step) { return get(h)->exposureLearningRate((int)step); }
 // TrainStep::renderViewWithDepth: (image, depth, alpha) of a forward-only render into the second workspace
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> trainer_render_view_depth(int64_t h, torch::Tensor view, torch::Tensor proj,
                                                                                   torch::Tensor campos, double fovx, double fovy,
@@ -273,6 +320,10 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "active_sh_degree") t->gaussians_->active_sh_degree_ = std::min((int)v, t->gaussians_->max_sh_degree_);
 		else if (k == "cull_empty_tiles") t->cull_empty_tiles_ = v != 0.0;
 		else if (k == "antialiasing") t->antialiasing_ = v != 0.0;
+		else if (k == "optimize_exposure") t->optimize_exposure_ = v != 0.0;
+		else if (k == "exposure_lr_init") t->exposure_lr_init_ = static_cast<float>(v);
+		else if (k == "exposure_lr_final") t->exposure_lr_final_ = static_cast<float>(v);
+		else if (k == "exposure_lr_max_steps") t->exposure_lr_max_steps_ = (int)v;
 		else if (k == "depth_loss_weight") t->depth_loss_weight_ = static_cast<float>(v);
 		else if (k == "depth_min") t->depth_min_ = static_cast<float>(v);
 		else if (k == "depth_max") t->depth_max_ = static_cast<float>(v);
@@ -498,6 +549,12 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("mark_visible", &mark_visible);
 	m.def("dist_cuda2", &dist_cuda2);
 	m.def("l1_ssim_loss", &l1_ssim_loss);
+	m.def("l1_ssim_loss_exposure", &l1_ssim_loss_exposure);
+	m.def("apply_exposure", &apply_exposure);
+	m.def("trainer_train_exposure", &trainer_train_exposure);
+	m.def("trainer_render_view_exposure", &trainer_render_view_exposure);
+	m.def("trainer_refine_pose_exposure", &trainer_refine_pose_exposure);
+	m.def("trainer_exposure_lr", &trainer_exposure_lr);
 	// host/include/loss_utils.h, the functions behind the reference's names (tests pin them to the reference's header compiled)
 	m.def("loss_ssim", +[](torch::Tensor a, torch::Tensor b, int64_t window_size, bool size_average) {
 		return loss_utils::ssim(a, b, a.device().type(), (int)window_size, size_average);

@@ -201,13 +201,46 @@ GaussianRasterizationExtensions TrainStep::viewExtensions()
 	return ext;
 }
 
-torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf)
+torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf, bool apply_exposure)
 {
 	torch::NoGradGuard no_grad;
 	torch::Tensor override_color;
 	auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_, override_color, 1.0f,
 	                                    false, viewExtensions());
+	if (apply_exposure && kf->exposure_.defined()) return loss_utils::apply_exposure(std::get<0>(pkg), kf->exposure_);
 	return std::get<0>(pkg);
+}
+
+double TrainStep::exposureLearningRate(int step) const
+{
+	const float lr_init = exposure_lr_init_, lr_final = exposure_lr_final_;
+	if (step < 0 || lr_init <= 0.0f || lr_final <= 0.0f) return 0.0;
+	const int max_steps = exposure_lr_max_steps_ >= 0 ? exposure_lr_max_steps_ : gaussians_->opt_.iterations_;
+	float t = static_cast<float>(step) / static_cast<float>(std::max(max_steps, 1));
+	t = std::min(std::max(t, 0.0f), 1.0f);
+	return std::exp(std::log(lr_init) * (1 - t) + std::log(lr_final) * t);   // float arithmetic, as updateLearningRate
+}
+
+// one Adam step of the last backward pass's keyframe exposure, on the keyframe's own moments and step count
+void TrainStep::finishExposure()
+{
+	auto kf = std::move(exposure_kf_);
+	auto grad = std::move(exposure_grad_);
+	exposure_kf_.reset();
+	exposure_grad_ = torch::Tensor();
+	if (!kf || !grad.defined() || iteration_ >= gaussians_->opt_.iterations_) return;
+	torch::NoGradGuard ng;
+	auto& e = kf->exposure_;
+	if (!kf->exposure_exp_avg_.defined()) {
+		kf->exposure_exp_avg_ = torch::zeros_like(e);
+		kf->exposure_exp_avg_sq_ = torch::zeros_like(e);
+	}
+	kf->exposure_step_++;
+	const double lr = exposureLearningRate(kf->exposure_step_);
+	grad = grad.contiguous();
+	check(gsr_adam_step(e.data_ptr<float>(), grad.data_ptr<float>(), kf->exposure_exp_avg_.data_ptr<float>(),
+	                    kf->exposure_exp_avg_sq_.data_ptr<float>(), 12, lr, 0.9, 0.999, 1e-15, kf->exposure_step_, 0, 0, lr, stream_of(e)),
+	      "gsr_adam_step");
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf)
@@ -288,7 +321,11 @@ std::tuple<torch::Tensor, torch::Tensor> TrainStep::refinePose(std::shared_ptr<G
 			                                    false, ext);
 			rendered = std::get<0>(pkg);
 		}
-		auto loss = fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
+		// (a keyframe's exposure is applied, not optimised)
+		auto loss = viewpoint_cam->exposure_.defined()
+		                ? loss_utils::fused_l1_ssim_exposure(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_,
+		                                                     viewpoint_cam->exposure_.detach(), /*is_root=*/true)
+		                : fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
 		if (use_depth) loss = loss + loss_utils::depth_l1(depth, gt_depth, depth_loss_weight_, depth_min_, depth_max_);
 		auto grad = torch::autograd::grad({loss}, {pose.xi_})[0];
 		{
@@ -310,7 +347,16 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	const bool use_depth = usesDepthLoss(gt_depth);
 	if (use_depth && process_group_)
 		throw std::runtime_error("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)");
+	exposure_kf_.reset();
+	exposure_grad_ = torch::Tensor();
+	if ((kf->exposure_.defined() || optimize_exposure_) && process_group_)
+		throw std::runtime_error("TrainStep: exposure compensation is not supported with a process group");
 	auto& g = gaussians_;
+	if (optimize_exposure_ && !kf->exposure_.defined())   // the identity at first use
+		kf->exposure_ = torch::eye(3, 4, g->xyz_.options().requires_grad(false));
+	if (kf->exposure_.defined() && (kf->exposure_.dim() != 2 || kf->exposure_.size(0) != 3 || kf->exposure_.size(1) != 4 ||
+	                                kf->exposure_.scalar_type() != torch::kFloat32 || !kf->exposure_.is_contiguous()))
+		throw std::runtime_error("a keyframe's exposure_ must be a contiguous float32 [3, 4] tensor");
 	iteration_++;
 	// the position learning rate follows the iteration (src/gaussian_mapper.cpp:672-674) or -- a SLAM session -- the number of
 	// times THIS keyframe has been used (:663-671): the caller says which through position_lr_step_
@@ -482,12 +528,20 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		}
 		if (it->second.ones) eff_mask = torch::empty({0}, mask.options());   // (an empty mask = none: FusedL1SSIMFunction::forward)
 	}
-	auto loss = fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
+	torch::Tensor exposure_leaf;   // (a leaf of this step's graph: the keyframe's tensor itself is stepped in place afterwards)
+	if (kf->exposure_.defined()) exposure_leaf = kf->exposure_.detach().set_requires_grad(optimize_exposure_);
+	auto loss = exposure_leaf.defined()
+	                ? loss_utils::fused_l1_ssim_exposure(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, exposure_leaf, /*is_root=*/true)
+	                : fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
 	// (the sum's backward hands both terms the root's exact 1: is_root stays valid)
 	if (use_depth) loss = loss + loss_utils::depth_l1(std::get<4>(pkg), gt_depth, depth_loss_weight_, depth_min_, depth_max_);
 	// the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward()
 	if (!root_grad_.defined() || root_grad_.device() != loss.device()) root_grad_ = torch::ones_like(loss).detach();
 	loss.backward(root_grad_);
+	if (optimize_exposure_ && exposure_leaf.defined()) {
+		exposure_kf_ = kf;
+		exposure_grad_ = exposure_leaf.grad();
+	}
 	if (lazy && !views_adam_pending_) {   // the step is taken: its learning rates join the history the later catch-ups need
 		auto& hist = g->features_lr_hist_;
 		hist.insert(hist.begin(), {sh_adam.lr, sh_adam.lr_tail});
@@ -635,6 +689,7 @@ void TrainStep::finishEnd()
 {
 	finishFeaturesFromViews();   // (a driver that forgot the slice: the lazy state stays consistent)
 	if (iteration_ < gaussians_->opt_.iterations_) gaussians_->zeroGrad();
+	finishExposure();   // the keyframe's exposure takes its own step, on densifying iterations too (it is not rebuilt)
 }
 
 bool TrainStep::densifyDue() const

@@ -89,10 +89,64 @@ class _FusedL1SSIM(torch.autograd.Function):
         return grad * grad_out, None, None, None, None
 
 
-def fused_l1_ssim_loss(rendered, gt, mask, lambda_dssim, is_root=False):
+class _FusedL1SSIMExposure(torch.autograd.Function):
+    """gsr_l1_ssim_loss_exposure: the loss behind a [3,4] exposure map, with the gradients of the rendered image and of the map"""
+    @staticmethod
+    def forward(ctx, rendered, gt, mask, lambda_dssim, is_root, exposure):
+        ctx.is_root = bool(is_root)
+        lib = _rp._lib()
+        _rp._check_device(lib, rendered, gt)
+        if tuple(exposure.shape) != (3, 4) or exposure.device != rendered.device:
+            raise RuntimeError("exposure must be a [3, 4] tensor on the device of the rendered image")
+        r = rendered.contiguous().float()
+        g = gt.contiguous().float()
+        m = None if mask is None else mask.contiguous().float()
+        e = exposure.contiguous().float()
+        _, H, W = r.shape
+        grad = torch.empty_like(r)
+        grad_e = torch.empty_like(e)
+        loss = torch.empty(1, dtype=torch.float32, device=r.device)
+        scratch = torch.empty(int(lib.gsr_loss_exposure_scratch_bytes(W, H)), dtype=torch.uint8, device=r.device)
+        st = lib.gsr_l1_ssim_loss_exposure(r.data_ptr(), g.data_ptr(), None if m is None else m.data_ptr(), W, H,
+                                           float(lambda_dssim), e.data_ptr(), grad.data_ptr(), grad_e.data_ptr(),
+                                           loss.data_ptr(), scratch.data_ptr(), _rp._stream_ptr(r))
+        from . import capi
+        capi.check(lib, st, "gsr_l1_ssim_loss_exposure")
+        ctx.save_for_backward(grad, grad_e)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad, grad_e = ctx.saved_tensors
+        if ctx.is_root:
+            return grad, None, None, None, None, grad_e
+        return grad * grad_out, None, None, None, None, grad_e * grad_out
+
+
+def fused_l1_ssim_loss(rendered, gt, mask, lambda_dssim, is_root=False, exposure=None):
     """is_root: the caller promises to call .backward() on this very value (upstream gradient exactly 1, as the train step
-    does): backward then hands the stored gradient on without the [3,H,W] multiply by one."""
+    does): backward then hands the stored gradient on without the [3,H,W] multiply by one.
+    exposure: a keyframe's [3,4] affine colour map (include/gsr.h, gsr_l1_ssim_loss_exposure), applied to the rendered image
+    inside the loss kernels; autograd then returns gradients for `rendered` and `exposure`."""
+    if exposure is not None:
+        return _FusedL1SSIMExposure.apply(rendered, gt, mask, lambda_dssim, is_root, exposure)
     return _FusedL1SSIM.apply(rendered, gt, mask, lambda_dssim, is_root)
+
+
+def apply_exposure(image, exposure):
+    """image_0 E[0][c] + image_1 E[1][c] + image_2 E[2][c] + E[c][3] per pixel of a [3,H,W] image (gsr_apply_exposure): what the
+    loss compares with the target, for evaluation renders of a keyframe with an exposure.  No clamping, no gradient."""
+    lib = _rp._lib()
+    _rp._check_device(lib, image, exposure)
+    if tuple(exposure.shape) != (3, 4) or image.dim() != 3 or image.size(0) != 3:
+        raise RuntimeError("apply_exposure takes a [3, H, W] image and a [3, 4] exposure")
+    r = image.detach().contiguous().float()
+    e = exposure.detach().contiguous().float()
+    out = torch.empty_like(r)
+    st = lib.gsr_apply_exposure(r.data_ptr(), e.data_ptr(), r.size(2), r.size(1), out.data_ptr(), _rp._stream_ptr(r))
+    from . import capi
+    capi.check(lib, st, "gsr_apply_exposure")
+    return out
 
 
 # Depth L1 loss of an RGB-D keyframe (csrc/train_ops.hip, gsr_depth_l1_loss):

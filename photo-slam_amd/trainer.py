@@ -250,21 +250,69 @@ class TrainStep:
         self.depth_loss_weight_ = 0.0
         self.depth_min_ = 0.0
         self.depth_max_ = float("inf")
+        # Per-keyframe exposure compensation (upstream 3DGS's per-image exposure): a keyframe that carries exposure_ -- a [3,4]
+        # affine colour map -- has it applied between render and loss, inside the loss kernels (gsr_l1_ssim_loss_exposure), in
+        # trainForOneIteration and refinePose.  optimize_exposure_: the keyframe of a train step gets the identity at first use
+        # and takes one Adam step on its 12 floats after every backward pass (gsr_adam_step, the model's betas and eps), at a
+        # learning rate that falls log-linearly from exposure_lr_init_ to exposure_lr_final_ over exposure_lr_max_steps_ of the
+        # keyframe's OWN steps.  refinePose applies a keyframe's exposure and never optimises it.
+        self.optimize_exposure_ = False
+        self.exposure_lr_init_ = 0.01
+        self.exposure_lr_final_ = 0.001
+        self.exposure_lr_max_steps_ = opt.iterations_
 
-    def render_view(self, viewpoint_cam, with_depth=False):
+    def exposureLearningRate(self, step):
+        """the learning rate of a keyframe's `step`-th exposure step (1-based): log-linear, float arithmetic as exponLrFunc"""
+        import numpy as _np
+        f32 = _np.float32
+        lr_init, lr_final = f32(self.exposure_lr_init_), f32(self.exposure_lr_final_)
+        if step < 0 or lr_init <= 0.0 or lr_final <= 0.0:
+            return 0.0
+        t = min(max(f32(step) / f32(max(int(self.exposure_lr_max_steps_), 1)), f32(0.0)), f32(1.0))
+        return float(_np.exp(_np.log(lr_init) * (f32(1) - t) + _np.log(lr_final) * t))
+
+    def _exposure_of(self, viewpoint_cam, create):
+        """the keyframe's exposure ([3,4] float32 on the model's device) or None; create: the identity at first use"""
+        e = getattr(viewpoint_cam, "exposure_", None)
+        if e is None and create:
+            e = viewpoint_cam.exposure_ = torch.eye(3, 4, dtype=torch.float32, device=self.gaussians_.xyz_.device)
+        if e is not None and (tuple(e.shape) != (3, 4) or e.dtype != torch.float32 or not e.is_contiguous()):
+            raise RuntimeError("a keyframe's exposure_ must be a contiguous float32 [3, 4] tensor")
+        return e
+
+    def _exposure_adam_step(self, viewpoint_cam, grad):
+        """one Adam step of the keyframe's exposure on its own moments and step count"""
+        from . import capi
+        from . import rasterize_points as rp
+        kf, e = viewpoint_cam, viewpoint_cam.exposure_
+        if kf.exposure_exp_avg_ is None:
+            kf.exposure_exp_avg_, kf.exposure_exp_avg_sq_ = torch.zeros_like(e), torch.zeros_like(e)
+        kf.exposure_step_ += 1
+        lr = self.exposureLearningRate(kf.exposure_step_)
+        lib = rp._lib()
+        g = grad.contiguous()
+        capi.check(lib, lib.gsr_adam_step(e.data_ptr(), g.data_ptr(), kf.exposure_exp_avg_.data_ptr(), kf.exposure_exp_avg_sq_.data_ptr(),
+                                          12, lr, 0.9, 0.999, 1e-15, kf.exposure_step_, 0, 0, lr, rp._stream_ptr(e)),
+                   "gsr_adam_step")
+
+    def render_view(self, viewpoint_cam, with_depth=False, apply_exposure=False):
         """A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe):
         forward-only (GSR_FORWARD_ONLY), into the trainer's second workspace, with lazily stepped SH rows read as they are --
         no flush, no counter advanced, nothing of the model or the training workspace touched.  Returns the [3,H,W] image;
-        with_depth: (image, depth, alpha), the [H,W] depth map sum z alpha T and alpha map 1 - T_final."""
+        with_depth: (image, depth, alpha), the [H,W] depth map sum z alpha T and alpha map 1 - T_final.  apply_exposure: the
+        image behind the keyframe's exposure_ (what the loss compares with the target), if it has one."""
         with torch.no_grad():
             out = GaussianRenderer.render(
                 viewpoint_cam, viewpoint_cam.image_height_, viewpoint_cam.image_width_, self.gaussians_, self.pipe_,
                 self.background_, cull_empty_tiles=self.cull_empty_tiles_,
                 workspace=self.view_workspace_ if self.persistent_workspace_ else None, forward_only=True,
                 render_depth=bool(with_depth), antialiasing=self.antialiasing_)
+        image = out[0]
+        if apply_exposure and getattr(viewpoint_cam, "exposure_", None) is not None:
+            image = loss_utils.apply_exposure(image, viewpoint_cam.exposure_)
         if with_depth:
-            return out[0], out[4], out[5]
-        return out[0]
+            return image, out[4], out[5]
+        return image
 
     def _frozen_map(self):
         """The model's tensors for a render that must not touch the model (refinePose): detached, and with lazily stepped SH rows
@@ -308,6 +356,9 @@ class TrainStep:
         cull = (env == "1") if env else self.cull_empty_tiles_
         means2D = torch.zeros_like(xyz)
         eff_mask = self._effective_mask(mask)
+        exposure = self._exposure_of(viewpoint_cam, create=False)   # applied, not optimised
+        if exposure is not None:
+            exposure = exposure.detach()
         losses = []
         for it in range(1, int(iterations) + 1):
             kf = pose.keyframe()
@@ -317,7 +368,7 @@ class TrainStep:
                 workspace_=self.view_workspace_ if self.persistent_workspace_ else None, render_depth_=use_depth,
                 antialiasing_=self.antialiasing_)
             out = GaussianRasterizer(s)(xyz, means2D, opacity, True, False, True, True, False, sh, None, scaling, rotation, None)
-            loss = loss_utils.fused_l1_ssim_loss(out[0], gt_image, eff_mask, opt.lambda_dssim_, is_root=True)
+            loss = loss_utils.fused_l1_ssim_loss(out[0], gt_image, eff_mask, opt.lambda_dssim_, is_root=True, exposure=exposure)
             if use_depth:
                 loss = loss + loss_utils.depth_l1_loss(out[2], gt_depth, self.depth_loss_weight_, self.depth_min_, self.depth_max_)
             (grad,) = torch.autograd.grad(loss, pose.xi_)
@@ -356,6 +407,9 @@ class TrainStep:
         use_depth = gt_depth is not None and self.depth_loss_weight_ != 0.0
         if use_depth and self.world_size_ > 1:
             raise RuntimeError("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)")
+        exposure = self._exposure_of(viewpoint_cam, create=self.optimize_exposure_)
+        if exposure is not None and self.world_size_ > 1:
+            raise RuntimeError("TrainStep: exposure compensation is not supported with a process group")
         g, opt = self.gaussians_, self.opt_
         self.iteration_ += 1
         it = self.iteration_
@@ -409,7 +463,11 @@ class TrainStep:
         finally:
             g._in_lazy_step = False
         # :692-698  masked L1 + lambda * (1 - SSIM), fused with its gradient (csrc/train_ops.hip)
-        loss = loss_utils.fused_l1_ssim_loss(rendered_image, gt_image, self._effective_mask(mask), opt.lambda_dssim_, is_root=True)
+        exposure_leaf = None
+        if exposure is not None:   # (a leaf of this step's graph: the keyframe's tensor itself is stepped in place below)
+            exposure_leaf = exposure.detach().requires_grad_(self.optimize_exposure_)
+        loss = loss_utils.fused_l1_ssim_loss(rendered_image, gt_image, self._effective_mask(mask), opt.lambda_dssim_, is_root=True,
+                                             exposure=exposure_leaf)
         if use_depth:   # (the sum's backward hands both terms the root's exact 1: is_root stays valid)
             loss = loss + loss_utils.depth_l1_loss(out[4], gt_depth, self.depth_loss_weight_, self.depth_min_, self.depth_max_)
         # :699 (the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward())
@@ -487,6 +545,9 @@ class TrainStep:
                 g.optimizer_.zero_grad(set_to_none=True)
             elif reduction is not None:
                 reduction.wait_all()
+            # the keyframe's exposure: its own Adam step, on densifying iterations too (it is not rebuilt)
+            if self.optimize_exposure_ and exposure_leaf is not None and it < opt.iterations_:
+                self._exposure_adam_step(viewpoint_cam, exposure_leaf.grad)
             if sync_loss:
                 # :705 (the reference's per-iteration host sync for the loss EMA) -- moved behind the optimizer launches, so
                 # that Adam is already queued behind backward while the host waits
