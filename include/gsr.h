@@ -145,6 +145,14 @@ typedef struct gsr_forward_args {
 	 * them untouched, as out_color.  Gradients: gsr_backward_args.dL_ddepth / dL_dalpha. */
 	float* out_depth;
 	float* out_alpha;
+	/* Extension (all NULL / 0 = the reference contract; read only with GSR_CONTRIBUTION in raw_params, see there): per-Gaussian
+	 * contribution statistics of this render. */
+	const float* pixel_weight;   /* [H,W] or NULL = all ones: w(p), every value finite and >= 0 */
+	float* out_weight_sum;       /* [P] or NULL */
+	float* out_weight_max;       /* [P] or NULL */
+	int* out_n_touched;          /* [P] or NULL */
+	int contribution_accumulate; /* 0: every element of the outputs is written.  1: sum += new (one float add), max = max(max, new),
+	                                n_touched += new: a scoring pass over K keyframes is K renders with nothing in between */
 } gsr_forward_args;
 
 #define GSR_RAW_OPACITY 1   /* opacities are logits */
@@ -213,6 +221,25 @@ typedef struct gsr_forward_args {
  * the depth / alpha maps and their gradients, the pose gradients, geom_adam, sh_adam and the view-factored exchange.  0 = the
  * reference's render, bit for bit, by the same kernels as before (the bit selects instantiations of its own). */
 #define GSR_ANTIALIAS 256
+/* ... and one that makes gsr_forward report what every Gaussian put into the image (ignored by gsr_backward).  radii > 0 says a
+ * Gaussian is inside the frustum with a non-empty footprint, not that any pixel blends it.  For Gaussian g take every pixel p that
+ * blends g in the colour blend -- the same list entries, the same power > 0 and alpha < 1/255 skips, the same T (1 - alpha) < 1e-4
+ * stop as out_color -- with alpha_g(p) the blended alpha (at most 0.99), T_g(p) the transmittance in front of g, and w(p) =
+ * gsr_forward_args.pixel_weight (NULL = 1):
+ *   out_weight_sum[g] = sum_p w(p) alpha_g(p) T_g(p)
+ *   out_weight_max[g] = max_p w(p) alpha_g(p) T_g(p), 0 if there is no such pixel
+ *   out_n_touched[g]  = the number of such pixels with w(p) != 0
+ * A Gaussian with radii == 0 gets 0 / 0 / 0.  Any subset of the three outputs may be NULL, but with the bit at least one is set;
+ * the bit without an output, or an output (or pixel_weight) without the bit, is GSR_ERR_INVALID_ARG.  contribution_accumulate:
+ * see the field.  The outputs are deterministic: the same inputs give the same bits on every run and in both GSR_BINNING_*
+ * arrangements (no atomics: per-(tile quad, instance) partial results in the binning buffer, summed per Gaussian in a fixed
+ * order); under GSR_CULL_EMPTY_TILES too.  sum_g out_weight_sum[g] = sum_p out_alpha[p] up to rounding when w = 1.
+ * Works with and without GSR_FORWARD_ONLY, in both GSR_BINNING_* arrangements, with GSR_CULL_EMPTY_TILES, GSR_ANTIALIAS,
+ * GSR_RAW_*, colors_precomp, cov3D_precomp, out_depth / out_alpha and the lazy sh_adam (read-only under GSR_FORWARD_ONLY);
+ * out_color, radii, *num_rendered and the depth / alpha maps are the same, bit for bit, as without the bit, and gsr_backward on
+ * the buffers of a training-form call gives the gradients it gives after a plain forward.  The binning buffer grows by 48 bytes
+ * per instance: gsr_binning_bytes_for(R, raw_params) is the size requested.  P == 0 leaves the outputs untouched. */
+#define GSR_CONTRIBUTION 512
 
 /* Rasterizer::forward, cuda_rasterizer/rasterizer_impl.cu:198-336.
  * Fills out_color and radii, returns the number of (tile, Gaussian) instances in

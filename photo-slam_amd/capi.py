@@ -32,7 +32,9 @@ class ForwardArgs(C.Structure):
                 ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p), ("cam_pos", C.c_void_p),
                 ("tan_fovx", C.c_float), ("tan_fovy", C.c_float), ("prefiltered", C.c_int),
                 ("out_color", C.c_void_p), ("radii", C.c_void_p), ("raw_params", C.c_int), ("sh_adam", C.c_void_p),
-                ("out_depth", C.c_void_p), ("out_alpha", C.c_void_p)]
+                ("out_depth", C.c_void_p), ("out_alpha", C.c_void_p),
+                ("pixel_weight", C.c_void_p), ("out_weight_sum", C.c_void_p), ("out_weight_max", C.c_void_p),
+                ("out_n_touched", C.c_void_p), ("contribution_accumulate", C.c_int)]
 
 
 SH_LAZY_WINDOW = 32   # GSR_SH_LAZY_WINDOW
@@ -133,6 +135,7 @@ class DensifyGatherArgs(C.Structure):
 RAW_OPACITY, RAW_SCALING, RAW_ROTATION = 1, 2, 4   # GSR_RAW_* of include/gsr.h
 CULL_EMPTY_TILES, FORWARD_ONLY = 8, 128             # GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY
 ANTIALIAS = 256                                     # GSR_ANTIALIAS: forward AND backward (the same value in both calls)
+CONTRIBUTION = 512                                  # GSR_CONTRIBUTION: per-Gaussian contribution statistics of a forward pass
 
 
 # every symbol include/gsr.h declares

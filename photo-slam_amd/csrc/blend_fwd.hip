@@ -16,12 +16,19 @@
 // DEPTH (gsr_forward_args.out_depth / out_alpha, either form): the depth map sum_j z_j alpha_j T_j and the alpha map 1 - T from
 // the same visits.  z_j, the view-space depth the lists are sorted by, is gathered at staging into the spare word of the LDS
 // record; the visit adds ONE v_fmac under the same EXEC mask as the colour channels.
+//
+// CONTRIB (GSR_CONTRIBUTION, either form, with or without DEPTH): per-Gaussian contribution statistics.  A (quad, list entry) pair
+// is visited exactly once, so the visit reduces wgt = [w(p)] alpha T over the lanes of upd_m to (sum, max, count of pixels with
+// w != 0) -- a DPP sum, a max on the bit patterns (non-negative floats order like their bits), one s_bcnt1 -- and parks the
+// triple in the registers of lane `bit`; at the end of the batch lane j stores entry j's triple to the entry's instance slot
+// (blend.h: slot = first + (ty - miny) w + (tx - minx), quad q at [slot][q]) with plain stores, if any pixel counted.  Slots nobody
+// writes were zeroed by the caller; contribution_reduce_kernel sums every Gaussian's run.  1 = all weights one, 2 = weight map.
 #include "blend.h"
 #include "kernels.h"
 
 namespace gsr {
 
-template <bool FWD_ONLY, bool DEPTH>
+template <bool FWD_ONLY, bool DEPTH, int CONTRIB = 0>
 __global__ void __launch_bounds__(64)
 blend_fwd_kernel(const BlendFwdParams p)
 {
@@ -52,6 +59,16 @@ blend_fwd_kernel(const BlendFwdParams p)
 	// pixel state predicates live as 64-bit lane masks in SGPR pairs; their logic is scalar
 	unsigned long long done_m = wave_ballot(!inside);
 
+	// CONTRIB: the pixel's weight, the lanes whose weight counts (one ballot per wave), and the triple of the entry this lane staged
+	float wpix = 1.f;
+	unsigned long long wnz_m = ~0ull;
+	float acc_sum = 0.f;
+	uint32_t acc_max = 0u, acc_cnt = 0u, my_slot = 0u;
+	if constexpr (CONTRIB == 2) {
+		wpix = inside ? p.pixel_weight[(size_t)py * p.W + px] : 0.f;
+		wnz_m = wave_ballot(wpix != 0.f);
+	}
+
 	uint32_t gid_next = (l < n) ? p.point_list[range.x + (uint32_t)l] : 0u;
 	for (int base = 0; base < n; base += 64) {
 		if (~done_m == 0ull) break;
@@ -63,7 +80,17 @@ blend_fwd_kernel(const BlendFwdParams p)
 		if (have) {
 			const float4 q0 = p.rec[3 * (size_t)gid + 0];
 			const float4 q1 = p.rec[3 * (size_t)gid + 1];
-			const float cb = p.rec[3 * (size_t)gid + 2].x;
+			float cb;
+			if constexpr (CONTRIB != 0) {
+				const float4 q2 = p.rec[3 * (size_t)gid + 2];
+				const uint32_t rmin = __float_as_uint(q2.y), rmax = __float_as_uint(q2.z);
+				const uint32_t minx = rmin & 0xFFFFu, miny = rmin >> 16, maxx = rmax & 0xFFFFu;
+				cb = q2.x;
+				my_slot = __float_as_uint(q2.w) + ((uint32_t)tile_y - miny) * (maxx - minx) + ((uint32_t)tile_x - minx);
+				acc_sum = 0.f; acc_max = 0u; acc_cnt = 0u;
+			} else {
+				cb = p.rec[3 * (size_t)gid + 2].x;
+			}
 			keep = quad_keep(q0, q1, (float)qx0, (float)qy0);
 			s_rec[l][0] = prescale_q0(q0);
 			s_rec[l][1] = make_float4(prescale_c(q1.x), q1.y, q1.z, q1.w);
@@ -115,6 +142,9 @@ blend_fwd_kernel(const BlendFwdParams p)
 #endif
 			}
 			done_m |= ok_m & below_m;
+			float cw = 0.f;   // CONTRIB: this lane's [w(p)] alpha T, formed before T moves on
+			if constexpr (CONTRIB != 0) cw = alpha * T;
+			if constexpr (CONTRIB == 2) cw *= wpix;
 #ifdef GSR_EMU
 			const float wgt = mask_select0_f32(upd_m, alpha * T);
 			Crg += (v2f){g1.z, g1.w} * (v2f){wgt, wgt};
@@ -158,6 +188,16 @@ blend_fwd_kernel(const BlendFwdParams p)
 				}
 			}
 #endif
+			if constexpr (CONTRIB != 0) {
+				cw = mask_select0_f32(upd_m, cw);
+				const float vsum = wave_readlane_f32(wave_sum_f32_lane63(cw), 63);
+				const uint32_t vmax = wave_max_u32(__float_as_uint(cw));
+				const uint32_t vcnt = (uint32_t)__popcll(CONTRIB == 2 ? (upd_m & wnz_m) : upd_m);
+				const bool mine = l == bit;
+				acc_sum = mine ? vsum : acc_sum;
+				acc_max = mine ? vmax : acc_max;
+				acc_cnt = mine ? vcnt : acc_cnt;
+			}
 			// (No test for "every pixel saturated" here: the rest of the batch then changes nothing -- ok_m excludes the saturated
 			// pixels -- and is at most a few dozen visits once per quad; the test cost every visit two scalar instructions.
 			// Tried and rejected: reading the NEXT entry's record from LDS while the current one is blended, unrolled by two so
@@ -167,6 +207,15 @@ blend_fwd_kernel(const BlendFwdParams p)
 		// the backward pass walks the same batches: it visits only the entries flagged here (15 % of the entries that survive the
 		// quad rejection blend into no pixel -- alpha below 1/255 at every pixel centre, or every such pixel saturated)
 		if (!FWD_ONLY && have) p.contrib[(size_t)quad * p.contrib_stride + range.x + (uint32_t)(base + l)] = (uint8_t)((contrib_m >> l) & 1ull);
+		if constexpr (CONTRIB != 0) {
+			// (an entry no pixel of the quad counts keeps the zeros its slot was given; my_slot < R by construction, checked anyway)
+			if (have && acc_cnt != 0u && my_slot < p.stats_slots) {
+				float* dst = p.stats + ((size_t)my_slot * QUADS_PER_TILE + (size_t)quad) * CONTRIB_WORDS;
+				dst[0] = acc_sum;
+				dst[1] = __uint_as_float(acc_max);
+				dst[2] = __uint_as_float(acc_cnt);
+			}
+		}
 		if (wave_done) break;
 		wave_fence();  // all lanes have read this batch before the next one overwrites the slice
 	}
@@ -190,10 +239,91 @@ blend_fwd_kernel(const BlendFwdParams p)
 	}
 }
 
+// The per-Gaussian end of the contribution statistics: sum each Gaussian's contiguous run of instance slots in a fixed order --
+// slots ascending, quads 0..3 inside a slot -- and write or accumulate the three outputs.  Lane = Gaussian for runs of up to
+// LONG_RUN slots; a longer run (a screen-filling splat) is then summed by the whole wave, lane l the k = ceil(cnt / 64) consecutive
+// slots [l k, (l + 1) k) and a fixed butterfly over the lanes, so that no lane walks thousands of slots alone (partials.h).  The
+// order depends on the run's length alone: the same bits in both binning arrangements, whose first slots differ.
+struct ContribTriple {
+	float sum;
+	uint32_t max, cnt;
+};
+__device__ __forceinline__ void contrib_add_slot(const float4* __restrict__ s4, ContribTriple& t)
+{
+	const float4 a = s4[0], b = s4[1], c = s4[2];   // (s0 m0 c0 s1) (m1 c1 s2 m2) (c2 s3 m3 c3)
+	t.sum += a.x; t.sum += a.w; t.sum += b.z; t.sum += c.y;
+	t.max = max(max(t.max, __float_as_uint(a.y)), max(__float_as_uint(b.x), max(__float_as_uint(b.w), __float_as_uint(c.z))));
+	t.cnt += __float_as_uint(a.z) + __float_as_uint(b.y) + __float_as_uint(c.x) + __float_as_uint(c.w);
+}
+
+__global__ void __launch_bounds__(64)
+contribution_reduce_kernel(const ContributionParams p)
+{
+	const int l = lane_id();
+	const int idx = (int)blockIdx.x * 64 + l;
+	const bool live = idx < p.P;
+	uint32_t cnt = live ? p.tiles_touched[idx] : 0u;
+	uint32_t first = cnt ? __float_as_uint(p.rec[3 * (size_t)idx + 2].w) : 0u;
+	if ((unsigned long long)first + cnt > (unsigned long long)p.stats_slots) cnt = 0u;   // (cannot happen: the emission's own layout)
+	const float4* s4 = reinterpret_cast<const float4*>(p.stats);
+	ContribTriple t = {0.f, 0u, 0u};
+	if (cnt <= LONG_RUN)
+		for (uint32_t k = 0; k < cnt; k++) contrib_add_slot(s4 + 3 * (size_t)(first + k), t);
+	unsigned long long long_m = wave_ballot(cnt > LONG_RUN);
+	while (long_m) {
+		const int src = __ffsll((long long)long_m) - 1;
+		long_m &= long_m - 1ull;
+		const uint32_t rf = wave_readlane_u32(first, src), rc = wave_readlane_u32(cnt, src);
+		const uint32_t k = (rc + 63u) >> 6;
+		const uint32_t lo = min(rc, (uint32_t)l * k), hi = min(rc, lo + k);
+		ContribTriple u = {0.f, 0u, 0u};
+		for (uint32_t j = lo; j < hi; j++) contrib_add_slot(s4 + 3 * (size_t)(rf + j), u);
+		const float rs = wave_readlane_f32(wave_sum_f32_lane63(u.sum), 63);
+		const uint32_t rm = wave_max_u32(u.max);
+		const uint32_t rn = wave_sum_u32(u.cnt);
+		if (l == src) { t.sum = rs; t.max = rm; t.cnt = rn; }
+	}
+	if (!live) return;
+	const float vmax = __uint_as_float(t.max);
+	if (p.accumulate) {
+		if (p.out_sum) p.out_sum[idx] += t.sum;
+		if (p.out_max) p.out_max[idx] = fmaxf(p.out_max[idx], vmax);
+		if (p.out_cnt) p.out_cnt[idx] += (int)t.cnt;
+	} else {
+		if (p.out_sum) p.out_sum[idx] = t.sum;
+		if (p.out_max) p.out_max[idx] = vmax;
+		if (p.out_cnt) p.out_cnt[idx] = (int)t.cnt;
+	}
+}
+
+int launch_contribution_reduce(const ContributionParams& p, hipStream_t stream)
+{
+	if (p.P <= 0) return GSR_OK;
+	GSR_LAUNCH(contribution_reduce_kernel, div_up(p.P, 64), 64, stream, p);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+template <int CONTRIB>
+static int launch_blend_fwd_contrib(const BlendFwdParams& p, bool depth, hipStream_t stream)
+{
+	if (p.forward_only && depth)
+		GSR_LAUNCH((blend_fwd_kernel<true, true, CONTRIB>), quad_grid(p.deal), 64, stream, p);
+	else if (p.forward_only)
+		GSR_LAUNCH((blend_fwd_kernel<true, false, CONTRIB>), quad_grid(p.deal), 64, stream, p);
+	else if (depth)
+		GSR_LAUNCH((blend_fwd_kernel<false, true, CONTRIB>), quad_grid(p.deal), 64, stream, p);
+	else
+		GSR_LAUNCH((blend_fwd_kernel<false, false, CONTRIB>), quad_grid(p.deal), 64, stream, p);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
 int launch_blend_fwd(const BlendFwdParams& p, hipStream_t stream)
 {
 	const bool depth = p.out_depth || p.out_alpha;
 	if (depth && !p.depth) return GSR_ERR_INVALID_ARG;
+	if (p.stats) return p.pixel_weight ? launch_blend_fwd_contrib<2>(p, depth, stream) : launch_blend_fwd_contrib<1>(p, depth, stream);
 	if (p.forward_only && depth)
 		GSR_LAUNCH((blend_fwd_kernel<true, true>), quad_grid(p.deal), 64, stream, p);
 	else if (p.forward_only)

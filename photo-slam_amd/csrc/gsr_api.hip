@@ -271,10 +271,10 @@ static inline size_t geometry_bytes(int P)
 	GeometryState::carve(nullptr, (size_t)P, &b);
 	return b;
 }
-static inline size_t binning_bytes(int R, bool forward_only = false)
+static inline size_t binning_bytes(int R, bool forward_only = false, bool contribution = false)
 {
 	size_t b = 0;
-	BinningState::carve(nullptr, (size_t)R, &b, forward_only);
+	BinningState::carve(nullptr, (size_t)R, &b, forward_only, contribution);
 	return b;
 }
 static inline size_t image_bytes(int W, int H, bool forward_only = false)
@@ -335,7 +335,10 @@ size_t gsr_geometry_bytes(int P) { return geometry_bytes(P < 0 ? 0 : P); }
 size_t gsr_binning_bytes(int R) { return binning_bytes(R < 0 ? 0 : R); }
 size_t gsr_pose_grad_scratch_bytes(int P) { return pose_slab_floats(P) * sizeof(float); }
 size_t gsr_image_bytes(int W, int H) { return (W <= 0 || H <= 0) ? 0 : image_bytes(W, H); }
-size_t gsr_binning_bytes_for(int R, int raw_params) { return binning_bytes(R < 0 ? 0 : R, (raw_params & GSR_FORWARD_ONLY) != 0); }
+size_t gsr_binning_bytes_for(int R, int raw_params)
+{
+	return binning_bytes(R < 0 ? 0 : R, (raw_params & GSR_FORWARD_ONLY) != 0, (raw_params & GSR_CONTRIBUTION) != 0);
+}
 size_t gsr_image_bytes_for(int W, int H, int raw_params) { return (W <= 0 || H <= 0) ? 0 : image_bytes(W, H, (raw_params & GSR_FORWARD_ONLY) != 0); }
 size_t gsr_knn_scratch_bytes(int P) { return knn_scratch_bytes(P < 0 ? 0 : P); }
 
@@ -370,6 +373,10 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	const bool fwd_only = (a->raw_params & GSR_FORWARD_ONLY) != 0;
 	// (the read-only lazy rows exist; a non-lazy sh_adam means the caller expected a step the forward pass never takes)
 	if (fwd_only && a->sh_adam && !a->sh_adam->lazy) return GSR_ERR_INVALID_ARG;
+	// GSR_CONTRIBUTION: the bit and at least one output, or neither (include/gsr.h)
+	const bool contribution = (a->raw_params & GSR_CONTRIBUTION) != 0;
+	if (contribution != (a->out_weight_sum || a->out_weight_max || a->out_n_touched)) return GSR_ERR_INVALID_ARG;
+	if (!contribution && a->pixel_weight) return GSR_ERR_INVALID_ARG;
 	t_last_forward_only = fwd_only ? 1 : 0;
 	int st = validate_common(a->P, a->D, a->M, a->width, a->height, a->shs, a->colors_precomp, a->scales, a->rotations,
 	                         a->cov3D_precomp);
@@ -497,9 +504,9 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	}
 	if (R64 > 0x7FFFFFFFull) return GSR_ERR_UNSUPPORTED;  // more than 2^31 instances
 	const int R = (int)R64;
-	char* bin_chunk = binningBuffer(binning_ctx, binning_bytes(R, fwd_only));
+	char* bin_chunk = binningBuffer(binning_ctx, binning_bytes(R, fwd_only, contribution));
 	if (!bin_chunk) return GSR_ERR_ALLOC;
-	BinningState bs = BinningState::carve(bin_chunk, (size_t)R, nullptr, fwd_only);
+	BinningState bs = BinningState::carve(bin_chunk, (size_t)R, nullptr, fwd_only, contribution);
 
 	// (im.ranges: zeroed by preprocess_fwd)
 	uint32_t* point_list = bs.vals_a;
@@ -551,7 +558,21 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	bp.forward_only = fwd_only ? 1 : 0;
 	bp.depth = reinterpret_cast<const float*>(g.depth_key);   // (the float bits of the view-space z: preprocess.hip)
 	bp.out_depth = a->out_depth; bp.out_alpha = a->out_alpha;
+	bp.stats = nullptr; bp.stats_slots = (uint32_t)R; bp.pixel_weight = nullptr;
+	if (contribution && R > 0) {
+		// the slots the blend never visits -- entries a quad rejects, instances GSR_CULL_EMPTY_TILES dropped, batches behind a wave's
+		// early exit -- read as zeros
+		GSR_HIP(hipMemsetAsync(bs.stats, 0, stats_floats((size_t)R) * sizeof(float), stream));
+		bp.stats = bs.stats; bp.pixel_weight = a->pixel_weight;
+	}
 	if ((st = launch_blend_fwd(bp, stream)) != GSR_OK) return st;
+	if (contribution) {
+		ContributionParams cp;
+		cp.P = P; cp.tiles_touched = g.tiles_touched; cp.rec = g.rec; cp.stats = R > 0 ? bs.stats : nullptr; cp.stats_slots = (uint32_t)R;
+		cp.out_sum = a->out_weight_sum; cp.out_max = a->out_weight_max; cp.out_cnt = a->out_n_touched;
+		cp.accumulate = a->contribution_accumulate ? 1 : 0;
+		if ((st = launch_contribution_reduce(cp, stream)) != GSR_OK) return st;
+	}
 	PROF_FWD(8);
 	t_prof.fwd_done = t_prof.on == 1;
 	*num_rendered = R;

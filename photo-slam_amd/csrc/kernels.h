@@ -95,8 +95,27 @@ struct BlendFwdParams {
 	const float* depth;     // [P] z per Gaussian: read only when out_depth or out_alpha is set
 	float* out_depth;       // [H,W] nullable
 	float* out_alpha;       // [H,W] nullable
+	// contribution statistics (GSR_CONTRIBUTION; stats null = the plain kernels): the per-(instance slot, quad) triples
+	float* stats;               // [stats_slots][4][CONTRIB_WORDS] (sum, bits of max, count), zeroed by the caller
+	uint32_t stats_slots;       // R
+	const float* pixel_weight;  // [H,W] nullable: w(p), finite and >= 0
 };
+constexpr int CONTRIB_WORDS = 3;
 int launch_blend_fwd(const BlendFwdParams& p, hipStream_t stream);
+
+// the per-Gaussian pass behind a forward blend with statistics (blend_fwd.hip: contribution_reduce_kernel)
+struct ContributionParams {
+	int P;
+	const uint32_t* tiles_touched;   // [P] length of the Gaussian's run of instance slots (0: culled)
+	const float4* rec;               // [3P] q2.w = the run's first slot
+	const float* stats;              // BlendFwdParams::stats
+	uint32_t stats_slots;
+	float* out_sum;                  // [P] nullable
+	float* out_max;                  // [P] nullable
+	int* out_cnt;                    // [P] nullable
+	int accumulate;                  // 0: write; 1: sum += new, max = max(max, new), count += new
+};
+int launch_contribution_reduce(const ContributionParams& p, hipStream_t stream);
 
 struct BlendBwdParams {
 	const uint2* ranges;

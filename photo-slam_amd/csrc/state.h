@@ -151,6 +151,7 @@ struct GeometryState {
 };
 
 static inline size_t touched_clear_bytes(size_t R) { return (R + 64 + 255) & ~(size_t)255; }
+static inline size_t stats_floats(size_t R) { return 12 * R; }   // 4 quads x (sum, max, count)
 struct BinningState {
 	uint32_t* keys_a;        // [R] tile id per instance (ping)
 	uint32_t* vals_a;        // [R] Gaussian id per instance (ping)
@@ -164,10 +165,15 @@ struct BinningState {
 	uint32_t* spare_words;   // [R] the tile-first per-tile depth sort's third spare array: the contrib planes (written only by the
 	                         // blend behind it), or -- forward-only layout -- an array of its own
 
+	float*    stats;         // [R][4][3] GSR_CONTRIBUTION only (else null): per (instance slot, quad) the forward blend's (sum, max, count)
+	                         // of the pixels that blend the instance (blend_fwd.hip), zeroed in front of the blend, summed per Gaussian behind it
+
 	// forward_only (GSR_FORWARD_ONLY): the lists and their sort tables at the same places as in the training layout (the tile sort
 	// and the tile-depth sort find their ping-pong arrays where they always do), then the spare words -- no gradient slots, no
 	// flags (partials / touched / contrib are null): 20 bytes per instance + the tables instead of ~70
-	static BinningState carve(char* chunk, size_t R, size_t* bytes = nullptr, bool forward_only = false)
+	// contribution (GSR_CONTRIBUTION): the statistics' triples BEHIND everything else, in either layout -- gsr_backward, which is not
+	// told about the bit, finds every array it reads where it always is
+	static BinningState carve(char* chunk, size_t R, size_t* bytes = nullptr, bool forward_only = false, bool contribution = false)
 	{
 		BinningState b;
 		Carver c(chunk);
@@ -181,6 +187,7 @@ struct BinningState {
 			b.touched = nullptr;
 			b.contrib = nullptr;
 			b.spare_words = c.take<uint32_t>(R + 16);
+			b.stats = contribution ? c.take<float>(stats_floats(R)) : nullptr;
 			if (bytes) *bytes = c.used(chunk) + 128;
 			return b;
 		}
@@ -190,6 +197,7 @@ struct BinningState {
 		b.touched = c.take<uint8_t>(touched_clear_bytes(R));
 		b.contrib = c.take<uint8_t>(4 * R + 64);
 		b.spare_words = reinterpret_cast<uint32_t*>(b.contrib);
+		b.stats = contribution ? c.take<float>(stats_floats(R)) : nullptr;
 		if (bytes) *bytes = c.used(chunk) + 128;
 		return b;
 	}

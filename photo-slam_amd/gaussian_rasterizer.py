@@ -55,6 +55,10 @@ class GaussianRasterizationSettings:
     # extension (GSR_ANTIALIAS, include/gsr.h): the opacity is compensated for the 0.3 px low-pass of the projected covariance
     # (upstream's `antialiasing`); forward and backward get the same value
     antialiasing_: bool = False
+    # extension (GSR_CONTRIBUTION, include/gsr.h), forward-only renders: dict(out_weight_sum, out_weight_max, out_n_touched -- [P]
+    # float32 / float32 / int32 tensors or None --, pixel_weight -- [H,W] or None --, accumulate) -- the render also leaves the
+    # per-Gaussian contribution statistics in the caller's tensors.  Not differentiable; nothing enters the autograd graph.
+    contribution_: dict = None
 
 
 def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth=None, alpha=None):
@@ -170,13 +174,16 @@ def _rasterize_forward_only(means3D, sh, colors_precomp, opacities, scales, rota
     if s.render_depth_:
         depth = torch.zeros((int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
         alpha = torch.zeros_like(depth)
+    c = s.contribution_ or {}
     with torch.no_grad():
         _, color, radii, _, _, _ = rp.RasterizeGaussiansCUDA(
             s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
             s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
             s.campos_, s.prefiltered_,
             s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0) | capi.FORWARD_ONLY, lazy, s.workspace_,
-            out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_)
+            out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_, pixel_weight=c.get("pixel_weight"),
+            out_weight_sum=c.get("out_weight_sum"), out_weight_max=c.get("out_weight_max"), out_n_touched=c.get("out_n_touched"),
+            contribution_accumulate=bool(c.get("accumulate", False)))
     if s.render_depth_:
         return color, radii, depth, alpha
     return color, radii
@@ -216,6 +223,8 @@ class GaussianRasterizer(torch.nn.Module):
         # no backward pass can follow (grad mode off, or nothing to differentiate), or the caller says none will: the forward pass
         # alone (GSR_FORWARD_ONLY -- the same image and radii, no scratch for a backward pass, no autograd node)
         s = self.raster_settings_
+        if s.contribution_ is not None and not (s.forward_only_ or not torch.is_grad_enabled()):
+            raise RuntimeError("contribution_ is an extension of forward-only renders (forward_only_, or torch.no_grad())")
         if s.forward_only_ or not torch.is_grad_enabled() or not any(
                 t is not None and t.requires_grad
                 for t in (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,

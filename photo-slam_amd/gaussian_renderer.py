@@ -95,7 +95,7 @@ class GaussianRenderer:
     def render(viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color=None,
                scaling_modifier=1.0, use_override_color=False, fuse_activations=True, sh_grad_view=None, sh_adam=None, view_stats=None,
                geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None, forward_only=False,
-               render_depth=False, antialiasing=False):
+               render_depth=False, antialiasing=False, contribution=None):
         """returns (render, viewspace_points, visibility_filter, radii), with render_depth (render, viewspace_points,
         visibility_filter, radii, depth, alpha)
 
@@ -121,7 +121,10 @@ class GaussianRenderer:
         antialiasing (extension; False = the reference's render): the opacity of every Gaussian is compensated for the 0.3 px
         low-pass of its projected covariance (GSR_ANTIALIAS, include/gsr.h; upstream's `antialiasing`), so that a Gaussian keeps
         its brightness across the resolutions a map is trained and viewed at.  A map is rendered with the value it was trained
-        with."""
+        with.
+
+        contribution (extension, forward-only renders): GaussianRasterizationSettings.contribution_ -- the per-Gaussian
+        contribution statistics of this render, left in the caller's tensors (TrainStep.score_contribution)."""
         env = os.environ.get("GSR_CULL_EMPTY_TILES")
         if env:
             cull_empty_tiles = env == "1"
@@ -155,7 +158,7 @@ class GaussianRenderer:
             sh_grad_view if sh_in_rasterizer else None, sh_adam if sh_in_rasterizer else None, view_stats,
             geom_adam if raw == 7 else None, bool((geom_adam is not None or training_outputs_only) and raw == 7),
             cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace, forward_only_=forward_only,
-            render_depth_=bool(render_depth), antialiasing_=bool(antialiasing))
+            render_depth_=bool(render_depth), antialiasing_=bool(antialiasing), contribution_=contribution)
         rasterizer = GaussianRasterizer(raster_settings)
         means3D = pc.getXYZ()
         means2D = screenspace_points

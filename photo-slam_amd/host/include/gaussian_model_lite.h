@@ -357,6 +357,18 @@ public:
 	                                                    torch::Tensor mask, int iterations, double lr_translation, double lr_rotation,
 	                                                    torch::Tensor gt_depth = torch::Tensor());
 	GaussianRasterizationExtensions viewExtensions();   // what the two calls above hand to GaussianRenderer
+	// What every Gaussian puts into the given keyframes' images (include/gsr.h: GSR_CONTRIBUTION): one forward-only render per keyframe
+	// through the second workspace, exactly as renderView -- lazily stepped SH rows read as they are, nothing of the model or the
+	// training workspace touched, cull_empty_tiles_ and antialiasing_ honoured -- with the three statistics accumulating over the
+	// keyframes inside the rasterizer.  pixel_weights: empty, or one [H,W] float32 map (finite, >= 0; undefined = ones) per keyframe.
+	// Returns (weight_sum, weight_max, n_touched, views_seen): the sum and the maximum over all pixels of all keyframes of
+	// w alpha T, the number of blending pixels with w != 0, and the number of keyframes with radii > 0.
+	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> scoreContribution(
+	    const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, const std::vector<torch::Tensor>& pixel_weights = {});
+	// Scores the keyframes and removes, through prunePoints, the Gaussians that at least min_views of them have in their frustum
+	// (radii > 0) and whose largest blending weight alpha T at any pixel of any of them stays below min_weight_max.  A Gaussian no
+	// given keyframe sees is kept: not observed is not useless.  Returns the number removed.  Not with a process group: throws.
+	int64_t pruneUncontributing(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, float min_weight_max, int min_views = 1);
 	bool early_gather_ = true;        // the exchange's all-gather waits for the colour gradients only, not for the whole backward pass
 	// The view-factored exchange in its PACKED form (include/gsr.h: gsr_pack_color_view): every rank sends only the rows its
 	// view sees -- 11.7 MB instead of 24 MB per rank and link at 2 M Gaussians.  The ranks agree on the message capacity by

@@ -110,6 +110,11 @@ struct GaussianRasterizationExtensions {
 	// sqrt(det Sigma / det(Sigma + 0.3 I)) of its projected covariance (upstream's `antialiasing`), in the forward pass, the
 	// forward-only path and the backward pass alike
 	bool antialiasing_ = false;
+	// GSR_CONTRIBUTION (include/gsr.h; rasterize_points.h: RasterForwardExtensions): the per-Gaussian contribution statistics of the
+	// render, left in the caller's [P] tensors (float32 / float32 / int32; any subset), with an optional [H,W] pixel weight map.
+	// Not differentiable: nothing enters the autograd graph.
+	torch::Tensor pixel_weight_, out_weight_sum_, out_weight_max_, out_n_touched_;
+	bool contribution_accumulate_ = false;
 };
 
 class GaussianRasterizerFunctionEx : public torch::autograd::Function<GaussianRasterizerFunctionEx> {

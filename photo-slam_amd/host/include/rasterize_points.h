@@ -69,6 +69,13 @@ struct RasterForwardExtensions {
 	// GSR_ANTIALIAS (include/gsr.h): the opacity is compensated for the 0.3 px low-pass of the projected covariance; the backward
 	// call must be given the same value
 	bool antialiasing_ = false;
+	// GSR_CONTRIBUTION (include/gsr.h; set by the call when one of the three outputs is defined): the per-Gaussian contribution
+	// statistics of this render -- caller-allocated contiguous [P] tensors on the device of means3D, float32 / float32 / int32:
+	// sum and maximum over the pixels that blend the Gaussian of w alpha T, and the number of those pixels with w != 0.
+	// pixel_weight: the [H,W] float32 map w (finite, >= 0), undefined = ones.  contribution_accumulate: add to / take the maximum
+	// with what the tensors hold instead of overwriting it.  Not differentiable: nothing enters the autograd graph.
+	torch::Tensor pixel_weight, out_weight_sum, out_weight_max, out_n_touched;
+	bool contribution_accumulate = false;
 };
 
 // ... and to the reference's backward parameter list
@@ -187,5 +194,8 @@ struct AdamMultiEntry {
 	float grad_scale = 1.0f;   // multiplies the gradient as it is read
 };
 void adamStepMulti(const std::vector<AdamMultiEntry>& entries, double beta1, double beta2, double eps);
+
+// |A & B| / |A | B| over the Gaussians two views blend ({n_touched > 0}, RasterForwardExtensions::out_n_touched); 0 for two empty sets
+double covisibility(const torch::Tensor& n_touched_a, const torch::Tensor& n_touched_b);
 
 torch::Tensor markVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix, torch::Tensor& projmatrix);

@@ -39,6 +39,11 @@ auto rasterize_forward(const torch::Tensor& means3D, const torch::Tensor& sh, co
 	f.out_depth = depth;
 	f.out_alpha = alpha;
 	f.antialiasing_ = e.antialiasing_;
+	f.pixel_weight = e.pixel_weight_;
+	f.out_weight_sum = e.out_weight_sum_;
+	f.out_weight_max = e.out_weight_max_;
+	f.out_n_touched = e.out_n_touched_;
+	f.contribution_accumulate = e.contribution_accumulate_;
 	return RasterizeGaussiansCUDA(s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
 	                              s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh,
 	                              s.sh_degree_, s.campos_, s.prefiltered_, f);

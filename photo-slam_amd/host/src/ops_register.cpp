@@ -66,6 +66,36 @@ std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_modes(torch::Tensor
 	                 colors_precomp, scales, rotations, cov3Ds_precomp);
 }
 
+// rasterize_gaussians_modes (ex) with the contribution statistics (GaussianRasterizationExtensions::out_weight_sum_ ...): stats =
+// {pixel_weight, out_weight_sum, out_weight_max, out_n_touched}, a tensor without elements = not given.  (image, radii)
+std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_contribution(
+    torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh, torch::Tensor colors_precomp, torch::Tensor opacities,
+    torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3Ds_precomp, torch::Tensor bg, double scale_modifier,
+    torch::Tensor viewmatrix, torch::Tensor projmatrix, double tanfovx, double tanfovy, int64_t image_height, int64_t image_width,
+    int64_t sh_degree, torch::Tensor campos, int64_t raw_params, bool extension_forward_only, std::vector<torch::Tensor> stats,
+    bool accumulate)
+{
+	TORCH_CHECK(stats.size() == 4, "stats: {pixel_weight, out_weight_sum, out_weight_max, out_n_touched}");
+	GaussianRasterizationSettings s((int)image_height, (int)image_width, (float)tanfovx, (float)tanfovy, bg,
+	                                (float)scale_modifier, viewmatrix, projmatrix, (int)sh_degree, campos, false);
+	auto has = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
+	torch::NoGradGuard guard;
+	GaussianRasterizationExtensions e;
+	e.raw_params_ = (int)raw_params & 7;
+	e.cull_empty_tiles_ = (raw_params & 8) != 0;
+	e.antialiasing_ = (raw_params & 256) != 0;
+	e.forward_only_ = extension_forward_only;
+	if (has(stats[0])) e.pixel_weight_ = stats[0];
+	if (has(stats[1])) e.out_weight_sum_ = stats[1];
+	if (has(stats[2])) e.out_weight_max_ = stats[2];
+	if (has(stats[3])) e.out_n_touched_ = stats[3];
+	e.contribution_accumulate_ = accumulate;
+	GaussianRasterizerEx r(s, e);
+	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
+	                 colors_precomp, scales, rotations, cov3Ds_precomp);
+}
+double covisibility_op(torch::Tensor a, torch::Tensor b) { return covisibility(a, b); }
+
 torch::Tensor mark_visible(torch::Tensor means3D, torch::Tensor viewmatrix, torch::Tensor projmatrix)
 {
 	return markVisible(means3D, viewmatrix, projmatrix);
@@ -236,6 +266,28 @@ std::tuple<torch::Tensor, torch::Tensor> trainer_refine_pose_exposure(int64_t h,
 	auto kf = make_kf(view, proj, campos, fovx, fovy, H, W);
 	if (exposure.numel()) kf->exposure_ = exposure;
 	return get(h)->refinePose(kf, gt, mask, (int)iterations, lr_translation, lr_rotation);
+}
+// the keyframes of the two ops below: views / projs [K,4,4], campos [K,3], one field of view and size for all
+std::vector<std::shared_ptr<GaussianKeyframe>> make_kfs(const torch::Tensor& views, const torch::Tensor& projs, const torch::Tensor& campos,
+                                                        double fovx, double fovy, int64_t H, int64_t W)
+{
+	std::vector<std::shared_ptr<GaussianKeyframe>> kfs;
+	for (int64_t i = 0; i < views.size(0); i++) kfs.push_back(make_kf(views[i].contiguous(), projs[i].contiguous(), campos[i].contiguous(), fovx, fovy, H, W));
+	return kfs;
+}
+// TrainStep::scoreContribution: (weight_sum, weight_max, n_touched, views_seen); pixel_weights: empty, or one map per keyframe (a
+// tensor without elements = ones)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> trainer_score_contribution(
+    int64_t h, torch::Tensor views, torch::Tensor projs, torch::Tensor campos, double fovx, double fovy, int64_t H, int64_t W,
+    std::vector<torch::Tensor> pixel_weights)
+{
+	return get(h)->scoreContribution(make_kfs(views, projs, campos, fovx, fovy, H, W), pixel_weights);
+}
+// TrainStep::pruneUncontributing: the number of Gaussians removed
+int64_t trainer_prune_uncontributing(int64_t h, torch::Tensor views, torch::Tensor projs, torch::Tensor campos, double fovx, double fovy,
+                                     int64_t H, int64_t W, double min_weight_max, int64_t min_views)
+{
+	return get(h)->pruneUncontributing(make_kfs(views, projs, campos, fovx, fovy, H, W), (float)min_weight_max, (int)min_views);
 }
 double trainer_exposure_lr(int64_t h, int64_t step) { return get(h)->exposureLearningRate((int)step); }
 // TrainStep::renderViewWithDepth: (image, depth, alpha) of a forward-only render into the second workspace
@@ -546,6 +598,10 @@ TORCH_LIBRARY(photoslam_amd, m)
 {
 	m.def("rasterize_gaussians", &rasterize_gaussians);
 	m.def("rasterize_gaussians_modes", &rasterize_gaussians_modes);
+	m.def("rasterize_gaussians_contribution", &rasterize_gaussians_contribution);
+	m.def("covisibility", &covisibility_op);
+	m.def("trainer_score_contribution", &trainer_score_contribution);
+	m.def("trainer_prune_uncontributing", &trainer_prune_uncontributing);
 	m.def("mark_visible", &mark_visible);
 	m.def("dist_cuda2", &dist_cuda2);
 	m.def("l1_ssim_loss", &l1_ssim_loss);

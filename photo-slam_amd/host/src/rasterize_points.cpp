@@ -115,7 +115,23 @@ float* map_ptr(const torch::Tensor& t, const torch::Tensor& means3D, int H, int 
 	return const_cast<float*>(t.data_ptr<float>());
 }
 
+// pointer of a [P] per-Gaussian output argument (out_weight_sum / out_weight_max / out_n_touched); undefined = nullptr
+void* row_ptr(const torch::Tensor& t, const torch::Tensor& means3D, int P, torch::ScalarType type, const char* name)
+{
+	if (!t.defined()) return nullptr;
+	if (t.dim() != 1 || t.size(0) != P || t.scalar_type() != type || !t.is_contiguous() || t.device() != means3D.device())
+		throw std::runtime_error(std::string(name) + " must be a contiguous (P,) tensor of its type on the device of means3D");
+	return t.data_ptr();
+}
+
 }  // namespace
+
+double covisibility(const torch::Tensor& n_touched_a, const torch::Tensor& n_touched_b)
+{
+	const auto a = n_touched_a > 0, b = n_touched_b > 0;
+	const int64_t uni = (a | b).sum().item<int64_t>();
+	return uni ? static_cast<double>((a & b).sum().item<int64_t>()) / static_cast<double>(uni) : 0.0;
+}
 
 // the reference's exact parameter lists (include/rasterize_points.h:18-37, :39-60): same mangled names
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(
@@ -210,6 +226,15 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
 		a.radii = radii.data_ptr<int>();
 		a.out_depth = map_ptr(ext.out_depth, means3D, H, W, "out_depth");
 		a.out_alpha = map_ptr(ext.out_alpha, means3D, H, W, "out_alpha");
+		a.out_weight_sum = static_cast<float*>(row_ptr(ext.out_weight_sum, means3D, P, torch::kFloat32, "out_weight_sum"));
+		a.out_weight_max = static_cast<float*>(row_ptr(ext.out_weight_max, means3D, P, torch::kFloat32, "out_weight_max"));
+		a.out_n_touched = static_cast<int*>(row_ptr(ext.out_n_touched, means3D, P, torch::kInt32, "out_n_touched"));
+		if (a.out_weight_sum || a.out_weight_max || a.out_n_touched)
+			a.raw_params |= GSR_CONTRIBUTION;
+		else if (ext.pixel_weight.defined() || ext.contribution_accumulate)
+			throw std::runtime_error("pixel_weight / contribution_accumulate need one of out_weight_sum, out_weight_max, out_n_touched");
+		a.pixel_weight = map_ptr(ext.pixel_weight, means3D, H, W, "pixel_weight");
+		a.contribution_accumulate = ext.contribution_accumulate ? 1 : 0;
 		gsr_sh_adam adam{};
 		gsr_sh_adam_lazy lazy{};
 		if (ext.sh_adam && ext.sh_adam->row_step.defined()) {   // lazy SH Adam: the forward pass brings visible rows up to date (in place)

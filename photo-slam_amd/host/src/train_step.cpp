@@ -211,6 +211,44 @@ torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf, bool a
 	return std::get<0>(pkg);
 }
 
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::scoreContribution(
+    const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, const std::vector<torch::Tensor>& pixel_weights)
+{
+	torch::NoGradGuard no_grad;
+	if (!pixel_weights.empty() && pixel_weights.size() != keyframes.size())
+		throw std::runtime_error("scoreContribution: one pixel weight map (or an undefined tensor) per keyframe");
+	const auto& xyz = gaussians_->xyz_;
+	const int64_t P = xyz.size(0);
+	const auto f32 = xyz.options().dtype(torch::kFloat32).requires_grad(false), i32 = xyz.options().dtype(torch::kInt32).requires_grad(false);
+	auto wsum = torch::zeros({P}, f32), wmax = torch::zeros({P}, f32);
+	auto touched = torch::zeros({P}, i32), seen = torch::zeros({P}, i32);
+	torch::Tensor override_color;
+	for (size_t i = 0; i < keyframes.size(); i++) {
+		const auto& kf = keyframes[i];
+		GaussianRasterizationExtensions ext = viewExtensions();
+		ext.out_weight_sum_ = wsum;
+		ext.out_weight_max_ = wmax;
+		ext.out_n_touched_ = touched;
+		ext.contribution_accumulate_ = true;
+		if (!pixel_weights.empty() && pixel_weights[i].defined() && pixel_weights[i].numel()) ext.pixel_weight_ = pixel_weights[i];
+		auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_, override_color, 1.0f,
+		                                    false, ext);
+		seen += (std::get<3>(pkg) > 0).to(torch::kInt32);
+	}
+	return std::make_tuple(wsum, wmax, touched, seen);
+}
+
+int64_t TrainStep::pruneUncontributing(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, float min_weight_max, int min_views)
+{
+	if (process_group_) throw std::runtime_error("TrainStep: pruneUncontributing is not supported with a process group");
+	torch::NoGradGuard no_grad;
+	auto score = scoreContribution(keyframes);
+	torch::Tensor mask = (std::get<3>(score) >= min_views) & (std::get<1>(score) < min_weight_max);
+	const int64_t n = mask.sum().item<int64_t>();
+	if (n) gaussians_->prunePoints(mask);
+	return n;
+}
+
 double TrainStep::exposureLearningRate(int step) const
 {
 	const float lr_init = exposure_lr_init_, lr_final = exposure_lr_final_;

@@ -107,7 +107,8 @@ class RasterWorkspace:
 def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                            viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                            prefiltered, raw_params=0, sh_adam=None, workspace=None, out_depth=None, out_alpha=None,
-                           antialiasing=False):
+                           antialiasing=False, pixel_weight=None, out_weight_sum=None, out_weight_max=None, out_n_touched=None,
+                           contribution_accumulate=False):
     """raw_params (extension, default 0 = reference contract): GSR_RAW_* mask -- opacity / scales / rotations are the
     model's raw parameters and are activated in-kernel (include/gsr.h).  With capi.FORWARD_ONLY in it the call renders the same
     image and radii without preparing anything for a backward pass: the returned buffers are then NOT valid input to
@@ -120,7 +121,13 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
     may be given alone.  The return tuple is the same.
     antialiasing (extension, default False = the reference's render): the opacity is compensated for the 0.3 px low-pass of the
     projected covariance (capi.ANTIALIAS in raw_params says the same; include/gsr.h: GSR_ANTIALIAS).  The backward call must be
-    given the same value."""
+    given the same value.
+    out_weight_sum / out_weight_max / out_n_touched (extension, default None): caller-allocated contiguous [P] tensors on the device
+    of means3D, float32 / float32 / int32, that receive the per-Gaussian contribution statistics of this render (include/gsr.h:
+    GSR_CONTRIBUTION -- any of them sets the bit): sum and maximum over the pixels that blend the Gaussian of w alpha T, and the
+    number of those pixels with w != 0.  pixel_weight: the [H, W] float32 map w (finite, >= 0), None = ones.
+    contribution_accumulate: add to / take the maximum with what the tensors hold instead of overwriting it.  Nothing of this is
+    differentiable; the return tuple is the same."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # AT_ERROR, rasterize_points.cu:57-59
     lib = _lib()
@@ -153,6 +160,15 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
         a.radii = radii.data_ptr()
         a.out_depth = _image_arg(out_depth, H, W, dev, "out_depth")
         a.out_alpha = _image_arg(out_alpha, H, W, dev, "out_alpha")
+        a.out_weight_sum = _row_arg(out_weight_sum, P, torch.float32, dev, "out_weight_sum")
+        a.out_weight_max = _row_arg(out_weight_max, P, torch.float32, dev, "out_weight_max")
+        a.out_n_touched = _row_arg(out_n_touched, P, torch.int32, dev, "out_n_touched")
+        if out_weight_sum is not None or out_weight_max is not None or out_n_touched is not None:
+            a.raw_params |= capi.CONTRIBUTION
+        elif pixel_weight is not None or contribution_accumulate:
+            raise RuntimeError("pixel_weight / contribution_accumulate need one of out_weight_sum, out_weight_max, out_n_touched")
+        a.pixel_weight = _image_arg(pixel_weight, H, W, dev, "pixel_weight")
+        a.contribution_accumulate = int(bool(contribution_accumulate))
         if sh_adam is not None and sh_adam.get("row_step") is not None:
             if sh is None or not sh.is_contiguous() or sh.dtype != torch.float32:
                 raise RuntimeError("lazy sh_adam needs a contiguous float32 sh tensor (it is updated in place)")
@@ -170,6 +186,23 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
         if workspace is not None:
             geomBuffer, binningBuffer, imgBuffer = workspace.bufs
     return rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer
+
+
+def _row_arg(t, P, dtype, dev, name):
+    """pointer of a [P] per-Gaussian output argument, None for None"""
+    if t is None:
+        return None
+    if t.shape != (P,) or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+        raise RuntimeError(f"{name} must be a contiguous {dtype} ({P},) tensor on the device of means3D")
+    return t.data_ptr()
+
+
+def covisibility(n_touched_a, n_touched_b):
+    """|A & B| / |A | B| over the Gaussians two views blend ({n_touched > 0}, RasterizeGaussiansCUDA's out_n_touched); 0 for two
+    empty sets"""
+    a, b = n_touched_a > 0, n_touched_b > 0
+    union = int((a | b).sum())
+    return float(int((a & b).sum())) / union if union else 0.0
 
 
 def _image_arg(t, H, W, dev, name):

@@ -314,6 +314,50 @@ class TrainStep:
             return image, out[4], out[5]
         return image
 
+    def score_contribution(self, keyframes, pixel_weights=None):
+        """What every Gaussian puts into the given keyframes' images (include/gsr.h: GSR_CONTRIBUTION): one forward-only render per
+        keyframe through the second workspace, exactly as render_view -- lazily stepped SH rows read as they are, nothing of the
+        model or the training workspace touched, cull_empty_tiles_ and antialiasing_ honoured -- with the three statistics
+        accumulating over the keyframes inside the rasterizer.  pixel_weights: one [H,W] float32 map (finite, >= 0) or None per
+        keyframe.  Returns (weight_sum, weight_max, n_touched, views_seen): the sum and the maximum over all pixels of all
+        keyframes of w alpha T, the number of blending pixels with w != 0, and the number of keyframes with radii > 0."""
+        dev = self.gaussians_.xyz_.device
+        P = self.gaussians_.xyz_.shape[0]
+        wsum, wmax = torch.zeros(P, device=dev), torch.zeros(P, device=dev)
+        touched, seen = torch.zeros(P, dtype=torch.int32, device=dev), torch.zeros(P, dtype=torch.int32, device=dev)
+        if pixel_weights is not None and len(pixel_weights) != len(keyframes):
+            raise RuntimeError("score_contribution: one pixel weight map (or None) per keyframe")
+        for i, kf in enumerate(keyframes):
+            c = dict(out_weight_sum=wsum, out_weight_max=wmax, out_n_touched=touched, accumulate=True,
+                     pixel_weight=pixel_weights[i] if pixel_weights is not None else None)
+            with torch.no_grad():
+                out = GaussianRenderer.render(kf, kf.image_height_, kf.image_width_, self.gaussians_, self.pipe_, self.background_,
+                                              cull_empty_tiles=self.cull_empty_tiles_,
+                                              workspace=self.view_workspace_ if self.persistent_workspace_ else None,
+                                              forward_only=True, antialiasing=self.antialiasing_, contribution=c)
+                seen += (out[3] > 0).to(torch.int32)
+        return wsum, wmax, touched, seen
+
+    def prune_uncontributing(self, keyframes, min_weight_max, min_views=1):
+        """Scores the keyframes (score_contribution) and removes, through prunePoints, the Gaussians that at least min_views of them
+        have in their frustum (radii > 0) and whose largest blending weight alpha T at any pixel of any of them stays below
+        min_weight_max.  A Gaussian no given keyframe sees is kept: not observed is not useless.  Returns the number removed."""
+        if self.world_size_ > 1:
+            raise RuntimeError("TrainStep: prune_uncontributing is not supported with a process group")
+        _, wmax, _, seen = self.score_contribution(keyframes)
+        mask = (seen >= int(min_views)) & (wmax < float(min_weight_max))
+        n = int(mask.sum())
+        if n:
+            with torch.no_grad():
+                self.gaussians_.prunePoints(mask)
+        return n
+
+    @staticmethod
+    def covisibility(n_touched_a, n_touched_b):
+        """rasterize_points.covisibility: |A & B| / |A | B| over the Gaussians two views blend"""
+        from . import rasterize_points as rp
+        return rp.covisibility(n_touched_a, n_touched_b)
+
     def _frozen_map(self):
         """The model's tensors for a render that must not touch the model (refinePose): detached, and with lazily stepped SH rows
         a caught-up COPY of the SH tensor (the zero-gradient steps the rows are behind, taken on clones: neither the tensor, its
