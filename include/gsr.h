@@ -104,6 +104,35 @@ typedef struct gsr_geom_adam {
 	double beta1, beta2, eps;
 } gsr_geom_adam;
 
+/* Extension: opacity, scale and isotropy regularisers on the Gaussians a view sees (see gsr_backward_args.geom_reg).  With V the
+ * Gaussians with radii > 0 in this view, o_i the activated opacity (the input, or its sigmoid under GSR_RAW_OPACITY; never the value
+ * GSR_ANTIALIAS compensates), s_ik the activated scale (the input, or its exp under GSR_RAW_SCALING; WITHOUT scale_modifier),
+ * m_i = (s_i0 + s_i1 + s_i2) / 3 and d_ik = s_ik - m_i:
+ *   loss[0] = w_opacity   * sum_{i in V} o_i                      (the opacity L1 of 3DGS-MCMC)
+ *   loss[1] = w_scale     * sum_{i in V} sum_k s_ik               (the scale L1 of 3DGS-MCMC)
+ *   loss[2] = w_isotropic * sum_{i in V} sum_k |d_ik|             (the isotropic loss of MonoGS)
+ *   dL/do_i  += w_opacity                                                   (* o (1 - o) under GSR_RAW_OPACITY)
+ *   dL/ds_ik += w_scale + w_isotropic * (sgn d_ik - (1/3) sum_j sgn d_ij)   (* s_ik under GSR_RAW_SCALING), sgn 0 = 0
+ * The terms join the opacity and scale gradients of the pass before those are written (dL_dopacity, dL_dscale) or consumed by the
+ * fused geom_adam step; culled rows get nothing and no other output of the pass changes.  Three equal scales give d = 0 exactly
+ * (d_ik is formed from the differences of the scales).  The weights are per Gaussian: a caller that wants MonoGS's mean over the
+ * visible Gaussians divides by gsr_last_visible_count() (and by 3 for the two scale terms), as both hosts do.
+ * loss: all three floats are written by every call that sets it (0 for P == 0 or a view that sees nothing), formed without atomics
+ * -- one entry per workgroup and sum in `scratch`, added in double in a fixed order by one small extra launch -- so the same inputs
+ * give the same bits on every run and in both GSR_BINNING_* arrangements.  loss == NULL: no entries, no extra launch, no scratch.
+ * A struct whose three weights are 0 and whose loss is NULL behaves as NULL.
+ * GSR_ERR_INVALID_ARG: a negative or non-finite weight; loss without scratch (or scratch not 4-byte aligned); w_scale or
+ * w_isotropic non-zero with cov3D_precomp (no scales to regularise).  GSR_ERR_UNSUPPORTED: together with dL_dcolor_view /
+ * packed_view (the multi-GPU exchange) or with the pose outputs.
+ * Works with GSR_RAW_* in any combination (without a raw bit the gradient is that of the activated input, like every gradient of
+ * this API), GSR_ANTIALIAS, dL_ddepth / dL_dalpha, sh_adam (eager and lazy), geom_adam, stat_*, colors_precomp and compact
+ * [P,M,3] SH. */
+typedef struct gsr_geom_reg {
+	float w_opacity, w_scale, w_isotropic;  /* finite, >= 0; weights per Gaussian, already normalised by the caller */
+	float* loss;                            /* [3] device floats or NULL: the three loss values of this view */
+	char* scratch;                          /* gsr_geom_reg_scratch_bytes(P) device bytes; required iff loss != NULL */
+} gsr_geom_reg;
+
 /* Rasterizer::forward parameter list, cuda_rasterizer/rasterizer.h:35-59, 1:1. */
 typedef struct gsr_forward_args {
 	int P, D, M;                 /* #Gaussians, active SH degree, SH coeffs per channel stored */
@@ -367,6 +396,9 @@ typedef struct gsr_backward_args {
 	float* dL_dprojmatrix;       /* [16], the layout of projmatrix */
 	float* dL_dcampos;           /* [3] */
 	char* pose_scratch;
+	/* Extension (NULL = the reference contract): regularisers on the Gaussians this view sees, added to the opacity and scale
+	 * gradients inside the pass -- see gsr_geom_reg. */
+	const gsr_geom_reg* geom_reg;
 } gsr_backward_args;
 
 /* Rasterizer::backward, cuda_rasterizer/rasterizer_impl.cu:340-433.
@@ -648,6 +680,7 @@ size_t gsr_binning_bytes_for(int num_rendered, int raw_params);
 size_t gsr_image_bytes_for(int width, int height, int raw_params);
 size_t gsr_knn_scratch_bytes(int P);
 size_t gsr_pose_grad_scratch_bytes(int P);   /* gsr_backward_args.pose_scratch */
+size_t gsr_geom_reg_scratch_bytes(int P);    /* gsr_geom_reg.scratch */
 
 /* Optional per-stage timing with HIP events recorded on the caller's stream (process-wide switch,
  * meant for single-stream benchmarking).

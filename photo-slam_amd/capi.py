@@ -98,6 +98,12 @@ def make_geom_adam(d):
     return g
 
 
+class GeomReg(C.Structure):
+    """gsr_geom_reg: the per-Gaussian weights of the opacity / scale / isotropy regularisers, the [3] loss tensor and its scratch"""
+    _fields_ = [("w_opacity", C.c_float), ("w_scale", C.c_float), ("w_isotropic", C.c_float), ("loss", C.c_void_p),
+                ("scratch", C.c_void_p)]
+
+
 class BackwardArgs(C.Structure):
     _fields_ = [("P", C.c_int), ("D", C.c_int), ("M", C.c_int), ("R", C.c_int), ("background", C.c_void_p),
                 ("width", C.c_int), ("height", C.c_int), ("means3D", C.c_void_p), ("shs", C.c_void_p),
@@ -115,7 +121,7 @@ class BackwardArgs(C.Structure):
                 ("packed_view", C.c_void_p), ("packed_capacity_rows", C.c_int),
                 ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p),
                 ("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p),
-                ("pose_scratch", C.c_void_p)]
+                ("pose_scratch", C.c_void_p), ("geom_reg", C.POINTER(GeomReg))]
 
 class DensifySelectArgs(C.Structure):
     _fields_ = [("P", C.c_int), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p), ("scaling", C.c_void_p),
@@ -151,6 +157,7 @@ EXPORTED_SYMBOLS = [
     "gsr_binning_bytes_for", "gsr_image_bytes_for", "gsr_last_forward_only",
     "gsr_depth_loss_scratch_bytes", "gsr_depth_l1_loss", "gsr_pose_grad_scratch_bytes",
     "gsr_loss_exposure_scratch_bytes", "gsr_l1_ssim_loss_exposure", "gsr_apply_exposure",
+    "gsr_geom_reg_scratch_bytes",
 ]
 
 _libs = {}
@@ -185,7 +192,7 @@ def load(path=None):
     L.gsr_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
     L.gsr_knn_mean_dist2.restype = i32
     L.gsr_knn_mean_dist2.argtypes = [i32, vp, vp, ALLOC_FN, vp, vp]
-    for n in ("gsr_geometry_bytes", "gsr_binning_bytes", "gsr_knn_scratch_bytes", "gsr_pose_grad_scratch_bytes"):
+    for n in ("gsr_geometry_bytes", "gsr_binning_bytes", "gsr_knn_scratch_bytes", "gsr_pose_grad_scratch_bytes", "gsr_geom_reg_scratch_bytes"):
         getattr(L, n).restype = sz
         getattr(L, n).argtypes = [i32]
     L.gsr_image_bytes.restype = sz

@@ -334,6 +334,7 @@ extern "C" {
 size_t gsr_geometry_bytes(int P) { return geometry_bytes(P < 0 ? 0 : P); }
 size_t gsr_binning_bytes(int R) { return binning_bytes(R < 0 ? 0 : R); }
 size_t gsr_pose_grad_scratch_bytes(int P) { return pose_slab_floats(P) * sizeof(float); }
+size_t gsr_geom_reg_scratch_bytes(int P) { return reg_slab_floats(P) * sizeof(float); }
 size_t gsr_image_bytes(int W, int H) { return (W <= 0 || H <= 0) ? 0 : image_bytes(W, H); }
 size_t gsr_binning_bytes_for(int R, int raw_params)
 {
@@ -589,7 +590,21 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	if (pose_ptrs != 0 && pose_ptrs != 4) return GSR_ERR_INVALID_ARG;
 	const bool pose = pose_ptrs == 4;
 	if (pose && (reinterpret_cast<uintptr_t>(a->pose_scratch) & 3)) return GSR_ERR_INVALID_ARG;
-	if (a->P == 0) return pose ? launch_pose_zero(a->dL_dviewmatrix, a->dL_dprojmatrix, a->dL_dcampos, (hipStream_t)stream_) : GSR_OK;
+	// the regularisers on the visible Gaussians (gsr.h: gsr_geom_reg); zero weights and no loss = NULL
+	bool reg = false;
+	if (const gsr_geom_reg* gr = a->geom_reg) {
+		const float ws[3] = {gr->w_opacity, gr->w_scale, gr->w_isotropic};
+		for (const float w : ws)
+			if (!std::isfinite(w) || w < 0.f) return GSR_ERR_INVALID_ARG;
+		if (gr->loss && (!gr->scratch || (reinterpret_cast<uintptr_t>(gr->scratch) & 3))) return GSR_ERR_INVALID_ARG;
+		if (a->cov3D_precomp && (gr->w_scale != 0.f || gr->w_isotropic != 0.f)) return GSR_ERR_INVALID_ARG;   // no scales to regularise
+		reg = gr->w_opacity != 0.f || gr->w_scale != 0.f || gr->w_isotropic != 0.f || gr->loss != nullptr;
+		if (reg && (a->dL_dcolor_view || a->packed_view || pose)) return GSR_ERR_UNSUPPORTED;   // no instantiations for these
+	}
+	if (a->P == 0) {
+		if (reg && a->geom_reg->loss) return launch_reg_zero(a->geom_reg->loss, (hipStream_t)stream_);
+		return pose ? launch_pose_zero(a->dL_dviewmatrix, a->dL_dprojmatrix, a->dL_dcampos, (hipStream_t)stream_) : GSR_OK;
+	}
 	if (st != GSR_OK) return st;
 	if (!a->background || !a->means3D || !a->viewmatrix || !a->projmatrix || !a->campos || !a->geom_buffer ||
 	    !a->image_buffer || !a->dL_dpix || !a->dL_dcolor || !a->dL_dmean3D || a->R < 0)
@@ -784,6 +799,12 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	pb.depth = (depth && R > 0) ? 1 : 0;
 	pb.pose_scratch = pose ? reinterpret_cast<float*>(a->pose_scratch) : nullptr;
 	pb.dL_dview = a->dL_dviewmatrix; pb.dL_dproj = a->dL_dprojmatrix; pb.dL_dcampos = a->dL_dcampos;
+	pb.reg_on = reg ? 1 : 0;
+	pb.reg_w_opacity = reg ? a->geom_reg->w_opacity : 0.f;
+	pb.reg_w_scale = reg ? a->geom_reg->w_scale : 0.f;
+	pb.reg_w_iso = reg ? a->geom_reg->w_isotropic : 0.f;
+	pb.reg_slab = (reg && a->geom_reg->loss) ? reinterpret_cast<float*>(a->geom_reg->scratch) : nullptr;
+	pb.reg_loss = reg ? a->geom_reg->loss : nullptr;
 	pb.notify_stream = nullptr; pb.notify_event = nullptr;
 	if (a->color_view_ready_stream && a->dL_dcolor_view) {
 		if ((st = t_sync.init_notify()) != GSR_OK) return fail(st);

@@ -221,7 +221,17 @@ struct PreprocessBwdParams {
 	float* dL_dview;          // [16]
 	float* dL_dproj;          // [16]
 	float* dL_dcampos;        // [3]
+	// opacity / scale / isotropy regularisers on the visible Gaussians (gsr_backward_args.geom_reg): the REG instantiations of
+	// preprocess_bwd_kernel add the terms to the opacity and scale gradients they hold in registers; with reg_slab set they also leave
+	// one entry per workgroup and loss sum there (reg_slab_floats below) and reg_final_sum_kernel adds them up into reg_loss
+	int reg_on;               // 0 = off (the other reg_* fields are then not read)
+	float reg_w_opacity, reg_w_scale, reg_w_iso;
+	float* reg_slab;          // null = the loss values are not wanted
+	float* reg_loss;          // [3]
 };
+// The regularisers' loss slab: 3 sums (opacity, scale, isotropy), component-major, one entry per workgroup of preprocess_bwd_kernel
+static inline size_t reg_slab_floats(int P) { return 3 * (((size_t)(P > 0 ? P : 0) + 127) / 128) + 4; }   // PRB_THREADS
+int launch_reg_zero(float* loss, hipStream_t stream);   // the three loss values of a call with P == 0
 // The pose slab: POSE_VP sums of preprocess_bwd_kernel (12 of the view matrix, 12 of the projection), component-major with one
 // entry per workgroup of it, then the 3 camera-centre sums with one entry per workgroup of the kernel that forms the SH direction
 // term (sh_bwd_rows_kernel on the two-kernel path, else preprocess_bwd_kernel).

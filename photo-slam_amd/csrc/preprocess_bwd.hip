@@ -299,11 +299,23 @@ __device__ __forceinline__ void pack_view_row(const PreprocessBwdParams& p, int 
 // gradient of the 2-D covariance BEFORE it is chained into T, Sigma and the mean, so cov3D, scale / rotation, the mean, the fused
 // steps and the pose sums all carry it without further code.  The opacity gradient then leaves behind computeCov2D instead of in
 // front of it.  An instantiation of its own: the kernels without it stay the same code.
-template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false>
+// REG: the opacity / scale / isotropy regularisers on the visible Gaussians (gsr_backward_args.geom_reg; include/gsr.h has the
+// definitions).  sigmoid(opacity) and exp(scaling) sit in registers here, so the terms join g_opacity and g_scale in front of the
+// store or the fused geom_adam step: one code path for both, no traffic.  With p.reg_slab set (kernel-uniform) the three loss terms
+// of the lane are summed over the wave, the waves meet in LDS in a fixed order and ONE slab entry per workgroup and sum leaves with
+// plain stores (kernels.h: reg_slab_floats); reg_final_sum_kernel adds the entries in double.  No atomics: the same bits every time.
+// Instantiated with PACKED = POSE = false only (launch_preprocess_bwd), and an instantiation of its own, so that the kernels
+// without it stay the same code.
+template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false, bool REG = false>
 __global__ void __launch_bounds__(PRB_THREADS)
 preprocess_bwd_kernel(const PreprocessBwdParams p)
 {
 	__shared__ float s_pose[POSE ? PRB_THREADS / 64 : 1][POSE ? POSE_VP + 3 : 1];
+	__shared__ float s_reg[REG ? PRB_THREADS / 64 : 1][REG ? 3 : 1];
+	float reg_l[REG ? 3 : 1];   // REG: this lane's terms of the three loss sums (opacity, scale, isotropy); 0 for a culled Gaussian
+	if constexpr (REG) {
+		reg_l[0] = reg_l[1] = reg_l[2] = 0.f;
+	}
 	// POSE: [3c + r] = dL/dW2C(r, c), r < 3; [12 + 3c + k] = dL/dProj(r, c), r = {0, 1, 3}[k]; this lane's terms
 	float pose_v[POSE ? POSE_VP : 1];
 	float pose_c[3] = {0.f, 0.f, 0.f};   // minus the SH direction term (formed here without sh_bwd_rows_kernel)
@@ -366,6 +378,10 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		} else {
 			// raw logit: d sigmoid = o (1 - o), o = the activated opacity kept in the blend record
 			if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o * (1.0f - o);
+			if constexpr (REG) {
+				g_opacity += (p.raw_params & GSR_RAW_OPACITY) ? p.reg_w_opacity * (o * (1.0f - o)) : p.reg_w_opacity;
+				reg_l[0] = o;
+			}
 		}
 	}
 	const float gcx = ga1.y, gcy = ga1.z, gcz = ga1.w;
@@ -524,6 +540,10 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 			const float dL_dh = g_opacity * o_act;
 			g_opacity = g_opacity * h;
 			if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o_act * (1.0f - o_act);
+			if constexpr (REG) {   // (the UNcompensated opacity)
+				g_opacity += (p.raw_params & GSR_RAW_OPACITY) ? p.reg_w_opacity * (o_act * (1.0f - o_act)) : p.reg_w_opacity;
+				reg_l[0] = o_act;
+			}
 			aa_dh2 = (h2 <= AA_H2_MIN) ? 0.f : dL_dh / (2.0f * h);
 		}
 		float dL_da = 0, dL_db = 0, dL_dc = 0;
@@ -677,6 +697,23 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		g_scale[0] = raw_s ? ds0 * sx : ds0;
 		g_scale[1] = raw_s ? ds1 * sy : ds1;
 		g_scale[2] = raw_s ? ds2 * sz : ds2;
+		if constexpr (REG) {
+			// the activated scales without scale_modifier.  d_k = s_k - mean, formed from the differences: three equal scales give
+			// exactly 0 (which (sx + sy + sz) / 3 does not return for every sx = sy = sz), and its sign is that of the exact value
+			const float sk[3] = {sx, sy, sz};
+			const float d[3] = {((sx - sy) + (sx - sz)) / 3.0f, ((sy - sx) + (sy - sz)) / 3.0f, ((sz - sx) + (sz - sy)) / 3.0f};
+			float sg[3];
+#pragma unroll
+			for (int k = 0; k < 3; k++) sg[k] = d[k] > 0.f ? 1.0f : (d[k] < 0.f ? -1.0f : 0.f);
+			const float sg_mean = (sg[0] + sg[1] + sg[2]) / 3.0f;
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				const float r = p.reg_w_scale + p.reg_w_iso * (sg[k] - sg_mean);
+				g_scale[k] += raw_s ? r * sk[k] : r;
+			}
+			reg_l[1] = sx + sy + sz;
+			reg_l[2] = fabsf(d[0]) + fabsf(d[1]) + fabsf(d[2]);
+		}
 		D00 *= s0; D01 *= s0; D02 *= s0;
 		D10 *= s1; D11 *= s1; D12 *= s1;
 		D20 *= s2; D21 *= s2; D22 *= s2;
@@ -731,6 +768,25 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 #pragma unroll
 			for (int k = 1; k < PRB_THREADS / 64; k++) sum += s_pose[k][t];
 			p.pose_scratch[(size_t)t * gridDim.x + blockIdx.x] = sum;
+		}
+	}
+	if constexpr (REG) {
+		if (p.reg_slab) {   // kernel-uniform
+			const int l = lane_id(), w = wave_id();
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				const float c = wave_sum_f32_lane63(reg_l[k]);
+				if (l == 63) s_reg[w][k] = c;
+			}
+			__syncthreads();
+			// one slab entry per workgroup and sum: the waves in a fixed order
+			const int t = (int)threadIdx.x;
+			if (t < 3) {
+				float sum = s_reg[0][t];
+#pragma unroll
+				for (int k = 1; k < PRB_THREADS / 64; k++) sum += s_reg[k][t];
+				p.reg_slab[(size_t)t * gridDim.x + blockIdx.x] = sum;
+			}
 		}
 	}
 }
@@ -925,6 +981,33 @@ int launch_pose_zero(float* dL_dview, float* dL_dproj, float* dL_dcampos, hipStr
 	return launch_pose_final_sum(nullptr, 0u, 0u, dL_dview, dL_dproj, dL_dcampos, stream);
 }
 
+// The regularisers' loss slab -> loss[3].  One workgroup per sum, the arrangement of pose_final_sum_kernel: each thread adds its
+// entries (t, t + 256, ...) in double, in index order, the 256 partial sums meet in a binary tree through LDS, the weight is applied
+// in double and the product rounded to float once.  n == 0 (P == 0) gives zeros.
+__global__ void __launch_bounds__(POSE_SUM_THREADS)
+reg_final_sum_kernel(const float* __restrict__ slab, unsigned n, float w_opacity, float w_scale, float w_iso, float* __restrict__ loss)
+{
+	__shared__ double s_sum[POSE_SUM_THREADS];
+	const int comp = (int)blockIdx.x, t = (int)threadIdx.x;
+	const float* src = slab + (size_t)comp * n;
+	double acc = 0.0;
+	for (unsigned i = (unsigned)t; i < n; i += POSE_SUM_THREADS) acc += (double)src[i];
+	s_sum[t] = acc;
+	__syncthreads();
+	for (int half = POSE_SUM_THREADS / 2; half > 0; half >>= 1) {
+		if (t < half) s_sum[t] += s_sum[t + half];
+		__syncthreads();
+	}
+	if (t == 0) loss[comp] = (float)((double)(comp == 0 ? w_opacity : (comp == 1 ? w_scale : w_iso)) * s_sum[0]);
+}
+
+int launch_reg_zero(float* loss, hipStream_t stream)
+{
+	GSR_LAUNCH(reg_final_sum_kernel, 3, POSE_SUM_THREADS, stream, (const float*)nullptr, 0u, 0.f, 0.f, 0.f, loss);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
 int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 {
 	if (p.partials && p.depth) GSR_LAUNCH(long_run_sums_kernel<true>, LRS_BLOCKS, 256, stream, p);
@@ -941,9 +1024,14 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 	unsigned pose_b_rows = 0u;   // entries of the camera centre's sums in the pose slab (kernels.h)
 	if (pose && (factored || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // no pose gradients through the multi-GPU exchange
 	const bool aa = (p.raw_params & GSR_ANTIALIAS) != 0;
+	const bool reg = p.reg_on != 0;
+	if (reg && (pose || factored || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // (keeps the number of instantiations down)
+	if (reg && !p.scales && (p.reg_w_scale != 0.f || p.reg_w_iso != 0.f)) return GSR_ERR_INVALID_ARG;
 #define GSR_PRB(RO, AAV)                                                                                                          \
 	do {                                                                                                                          \
-		if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, true, AAV>), grid, PRB_THREADS, stream, p);       \
+		if (reg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV, true>), grid, PRB_THREADS, stream, p);  \
+		else if (reg) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV, true>), grid, PRB_THREADS, stream, p);      \
+		else if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, true, AAV>), grid, PRB_THREADS, stream, p);       \
 		else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, true, AAV>), grid, PRB_THREADS, stream, p);            \
 		else if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, true, true, false, AAV>), grid, PRB_THREADS, stream, p); \
 		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<RO, true, false, false, AAV>), grid, PRB_THREADS, stream, p);    \
@@ -996,6 +1084,11 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 #undef GSR_PRB
 	GSR_CHECK_LAUNCH();
 	if (pose) return launch_pose_final_sum(p.pose_scratch, (unsigned)grid, pose_b_rows, p.dL_dview, p.dL_dproj, p.dL_dcampos, stream);
+	if (reg && p.reg_slab) {
+		GSR_LAUNCH(reg_final_sum_kernel, 3, POSE_SUM_THREADS, stream, (const float*)p.reg_slab, (unsigned)grid, p.reg_w_opacity, p.reg_w_scale,
+		           p.reg_w_iso, p.reg_loss);
+		GSR_CHECK_LAUNCH();
+	}
 	return GSR_OK;
 }
 

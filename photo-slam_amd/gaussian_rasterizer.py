@@ -59,6 +59,12 @@ class GaussianRasterizationSettings:
     # float32 / float32 / int32 tensors or None --, pixel_weight -- [H,W] or None --, accumulate) -- the render also leaves the
     # per-Gaussian contribution statistics in the caller's tensors.  Not differentiable; nothing enters the autograd graph.
     contribution_: dict = None
+    # extension (gsr_backward_args.geom_reg, include/gsr.h): dict(lambda_opacity, lambda_scale, lambda_isotropic, loss) -- backward adds
+    # the gradients of the opacity / scale / isotropy regularisers on the Gaussians this view sees to the opacity and scale gradients
+    # inside the pass (in front of the fused geom_adam_ step, if any).  The lambdas are those of a MEAN over the visible Gaussians:
+    # the per-Gaussian weights are lambda_opacity / V and lambda_scale / (3 V), lambda_isotropic / (3 V), V = max(visible count of
+    # the forward pass, 1).  loss: a float32 [3] tensor that receives the three loss values, or None (they are not formed).
+    geom_reg_: dict = None
 
 
 def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth=None, alpha=None):
@@ -70,6 +76,8 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
         s.workspace_, out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_)
     ctx.set_materialize_grads(False)   # (no zero tensor for the unused gradient of `radii`)
     ctx.num_rendered = num_rendered
+    # (the forward pass's one host synchronisation has produced the visible count: the regularisers' mean needs it)
+    ctx.visible_count = rp.lastVisibleCount() if s.geom_reg_ is not None else 0
     ctx.raster_settings = s
     ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
                           binningBuffer, imgBuffer)
@@ -89,6 +97,12 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None, pose=False)
     if grad_out_color is None:
         grad_out_color = torch.zeros((3, int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
     cont = lambda t: None if t is None else t.contiguous().float()
+    geom_reg = None
+    if s.geom_reg_ is not None:
+        V = float(max(int(ctx.visible_count), 1))
+        geom_reg = dict(w_opacity=float(s.geom_reg_.get("lambda_opacity", 0.0)) / V,
+                        w_scale=float(s.geom_reg_.get("lambda_scale", 0.0)) / (3.0 * V),
+                        w_isotropic=float(s.geom_reg_.get("lambda_isotropic", 0.0)) / (3.0 * V), loss=s.geom_reg_.get("loss"))
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
      dL_drotations, *dL_dcamera) = rp.RasterizeGaussiansBackwardCUDA(
         s.bg_, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier_, cov3Ds_precomp, s.viewmatrix_,
@@ -99,7 +113,8 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None, pose=False)
         # catch-up next to the blend kernel
         s.sh_adam_ if (s.sh_grad_view_ is None or (s.sh_adam_ or {}).get("row_step") is not None) else None, s.view_stats_,
         s.geom_adam_, s.training_outputs_only_, dL_ddepth=cont(grad_depth), dL_dalpha=cont(grad_alpha),
-        pose_grad=pose, workspace=s.workspace_ if pose else None, antialiasing=s.antialiasing_)
+        pose_grad=pose, workspace=s.workspace_ if (pose or geom_reg is not None) else None, antialiasing=s.antialiasing_,
+        geom_reg=geom_reg)
     # order of src/gaussian_rasterizer.cpp:159-179
     def g(t, like):   # (None where an extension took the gradient's place)
         return t if like.numel() and t is not None else None

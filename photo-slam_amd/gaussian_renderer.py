@@ -95,7 +95,7 @@ class GaussianRenderer:
     def render(viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color=None,
                scaling_modifier=1.0, use_override_color=False, fuse_activations=True, sh_grad_view=None, sh_adam=None, view_stats=None,
                geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None, forward_only=False,
-               render_depth=False, antialiasing=False, contribution=None):
+               render_depth=False, antialiasing=False, contribution=None, geom_reg=None):
         """returns (render, viewspace_points, visibility_filter, radii), with render_depth (render, viewspace_points,
         visibility_filter, radii, depth, alpha)
 
@@ -124,7 +124,10 @@ class GaussianRenderer:
         with.
 
         contribution (extension, forward-only renders): GaussianRasterizationSettings.contribution_ -- the per-Gaussian
-        contribution statistics of this render, left in the caller's tensors (TrainStep.score_contribution)."""
+        contribution statistics of this render, left in the caller's tensors (TrainStep.score_contribution).
+
+        geom_reg (extension): GaussianRasterizationSettings.geom_reg_ -- the opacity / scale / isotropy regularisers on the Gaussians
+        this view sees, added to the gradients inside the rasterizer's backward (TrainStep.opacity_reg_ ...)."""
         env = os.environ.get("GSR_CULL_EMPTY_TILES")
         if env:
             cull_empty_tiles = env == "1"
@@ -158,7 +161,8 @@ class GaussianRenderer:
             sh_grad_view if sh_in_rasterizer else None, sh_adam if sh_in_rasterizer else None, view_stats,
             geom_adam if raw == 7 else None, bool((geom_adam is not None or training_outputs_only) and raw == 7),
             cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace, forward_only_=forward_only,
-            render_depth_=bool(render_depth), antialiasing_=bool(antialiasing), contribution_=contribution)
+            render_depth_=bool(render_depth), antialiasing_=bool(antialiasing), contribution_=contribution,
+            geom_reg_=None if forward_only else geom_reg)
         rasterizer = GaussianRasterizer(raster_settings)
         means3D = pc.getXYZ()
         means2D = screenspace_points

@@ -272,6 +272,18 @@ public:
 	// the model's betas and eps; densifying iterations included), at a learning rate that falls log-linearly from exposure_lr_init_
 	// to exposure_lr_final_ over exposure_lr_max_steps_ (< 0: opt_.iterations_) of the keyframe's OWN steps.  refinePose applies
 	// a keyframe's exposure and never optimises it.  Not with a process group: throws.
+	// Regularisers on the Gaussians a view sees, added to the opacity and scale gradients inside the rasterizer's backward
+	// (gsr_backward_args.geom_reg; with fused_geom_adam_ in front of the fused step, so nothing reaches HBM for them):
+	//   opacity_reg_ * mean_V sigmoid(opacity) + scale_reg_ * mean_V,k exp(scaling)  (the L1 terms of 3DGS-MCMC, which push Gaussians
+	//   that explain nothing towards the pruning thresholds) + isotropic_reg_ * mean_V,k |s_k - mean_k s|  (MonoGS)
+	// over the V Gaussians with radii > 0 in the view.  All 0 = off: no struct is passed and the kernels are those without it.  Not
+	// with a process group: throws.  read_reg_losses_ (the C++ form of the Python host's sync_loss): the three loss values are
+	// formed and added to the loss renderAndBackward returns, and lastRegLosses() gives them ([3]; undefined otherwise).  refinePose
+	// ignores the three.
+	double opacity_reg_ = 0.0, scale_reg_ = 0.0, isotropic_reg_ = 0.0;
+	bool read_reg_losses_ = true;
+	torch::Tensor lastRegLosses() const { return last_reg_losses_; }
+	torch::Tensor last_reg_losses_;
 	bool optimize_exposure_ = false;
 	float exposure_lr_init_ = 0.01f, exposure_lr_final_ = 0.001f;
 	int exposure_lr_max_steps_ = -1;

@@ -115,6 +115,14 @@ struct GaussianRasterizationExtensions {
 	// Not differentiable: nothing enters the autograd graph.
 	torch::Tensor pixel_weight_, out_weight_sum_, out_weight_max_, out_n_touched_;
 	bool contribution_accumulate_ = false;
+	// the opacity / scale / isotropy regularisers on the Gaussians this view sees (gsr_backward_args.geom_reg, include/gsr.h): backward
+	// adds their gradients to the opacity and scale gradients inside the pass (in front of the fused geom_adam_ step, if any).  The
+	// lambdas are those of a MEAN over the visible Gaussians: the per-Gaussian weights are opacity_reg_ / V, scale_reg_ / (3 V) and
+	// isotropic_reg_ / (3 V), V = max(visible count of the forward pass, 1).  All 0 and no loss = off.  reg_loss_: a float32 [3]
+	// tensor that receives the three loss values; undefined = they are not formed.
+	double opacity_reg_ = 0.0, scale_reg_ = 0.0, isotropic_reg_ = 0.0;
+	torch::Tensor reg_loss_;
+	bool hasGeomReg() const { return opacity_reg_ != 0.0 || scale_reg_ != 0.0 || isotropic_reg_ != 0.0 || reg_loss_.defined(); }
 };
 
 class GaussianRasterizerFunctionEx : public torch::autograd::Function<GaussianRasterizerFunctionEx> {

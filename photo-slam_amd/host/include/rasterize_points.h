@@ -48,6 +48,16 @@ struct GeomAdamStep {
 struct RasterWorkspace {
 	torch::Tensor geom, binning, img;
 	torch::Tensor pose;   // the scratch of the pose gradients' sums (gsr_backward_args.pose_scratch): refinePose allocates nothing per iteration
+	torch::Tensor reg;    // the scratch of the regularisers' loss sums (gsr_geom_reg.scratch)
+};
+
+// Extension: the opacity / scale / isotropy regularisers on the Gaussians a view sees (gsr_backward_args.geom_reg, include/gsr.h),
+// added to the opacity and scale gradients inside the backward pass, in front of the fused geom_adam step if there is one.  The
+// weights are per Gaussian (the caller normalises them, e.g. by lastVisibleCount()).  loss: a contiguous float32 [3] tensor on the
+// device of means3D that receives the three loss values; undefined = they are not formed (no extra launch, no scratch).
+struct GeomRegStep {
+	float w_opacity = 0.0f, w_scale = 0.0f, w_isotropic = 0.0f;
+	torch::Tensor loss;
 };
 
 // Extension: the gradients of the loss with respect to the camera -- viewmatrix [4,4], projmatrix [4,4], campos [3] as the kernels
@@ -108,6 +118,9 @@ struct RasterBackwardExtensions {
 	RasterWorkspace* workspace = nullptr;
 	// GSR_ANTIALIAS: the value the forward call was given
 	bool antialiasing_ = false;
+	// the regularisers on the visible Gaussians: nullptr = off.  Not together with dL_dcolor_view or pose_grad.  workspace: when
+	// given, it owns the scratch of the loss sums (otherwise allocated per call)
+	const GeomRegStep* geom_reg = nullptr;
 };
 
 // (num_rendered, out_color[3,H,W], radii[P] i32, geomBuffer u8, binningBuffer u8, imgBuffer u8)

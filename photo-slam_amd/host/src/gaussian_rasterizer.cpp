@@ -21,6 +21,7 @@ struct SavedState : torch::CustomClassHolder {
 	GaussianRasterizationSettings settings;
 	GaussianRasterizationExtensions extensions;
 	int num_rendered = 0;
+	int visible_count = 0;   // the regularisers' mean is over the Gaussians the forward pass saw
 };
 
 // RasterizeGaussiansCUDA as both paths below call it.  more_raw_params: GSR_FORWARD_ONLY or 0; depth / alpha: defined = the
@@ -66,6 +67,8 @@ torch::autograd::tensor_list forward_impl(torch::autograd::AutogradContext* ctx,
 	}
 	auto r = rasterize_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, e, 0, depth, alpha);
 	state->num_rendered = std::get<0>(r);
+	// (the forward pass's one host synchronisation has produced the count)
+	if (e.hasGeomReg()) state->visible_count = lastVisibleCount();
 	// (no zero tensor for the unused gradient of `radii`: autograd would otherwise fill P ints per backward)
 	ctx->set_materialize_grads(false);
 	ctx->saved_data["state"] = c10::IValue::make_capsule(state);
@@ -118,6 +121,17 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 	PoseGradients camera;
 	if (pose) {
 		b.pose_grad = &camera;
+		b.workspace = e.workspace_;
+	}
+	GeomRegStep reg;
+	if (e.hasGeomReg()) {
+		// (double, then one rounding: the arithmetic of the Python host)
+		const double V = static_cast<double>(state->visible_count > 1 ? state->visible_count : 1);
+		reg.w_opacity = static_cast<float>(e.opacity_reg_ / V);
+		reg.w_scale = static_cast<float>(e.scale_reg_ / (3.0 * V));
+		reg.w_isotropic = static_cast<float>(e.isotropic_reg_ / (3.0 * V));
+		reg.loss = e.reg_loss_;
+		b.geom_reg = &reg;
 		b.workspace = e.workspace_;
 	}
 	auto v = ctx->get_saved_variables();

@@ -203,6 +203,12 @@ torch::Tensor trainer_render_and_backward_depth(int64_t h, torch::Tensor view, t
 {
 	return get(h)->renderAndBackward(make_kf(view, proj, campos, fovx, fovy, H, W), gt, mask, gt_depth).detach();
 }
+// TrainStep::lastRegLosses: the three regulariser terms of the last step ([3]), or an empty tensor when they were not formed
+torch::Tensor trainer_last_reg_losses(int64_t h)
+{
+	auto t = get(h);
+	return t->lastRegLosses().defined() ? t->lastRegLosses() : torch::empty({0}, t->gaussians_->xyz_.options().requires_grad(false));
+}
 // GaussianRenderer::render on the trainer's model with the pipeline flags of GaussianPipelineParams (convert_SHs_,
 // compute_cov3D_: src/gaussian_renderer.cpp:78-113): (image, radii); the image is attached to the model's leaves
 std::tuple<torch::Tensor, torch::Tensor> trainer_render(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos,
@@ -376,6 +382,10 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "exposure_lr_init") t->exposure_lr_init_ = static_cast<float>(v);
 		else if (k == "exposure_lr_final") t->exposure_lr_final_ = static_cast<float>(v);
 		else if (k == "exposure_lr_max_steps") t->exposure_lr_max_steps_ = (int)v;
+		else if (k == "opacity_reg") t->opacity_reg_ = v;
+		else if (k == "scale_reg") t->scale_reg_ = v;
+		else if (k == "isotropic_reg") t->isotropic_reg_ = v;
+		else if (k == "read_reg_losses") t->read_reg_losses_ = v != 0.0;
 		else if (k == "depth_loss_weight") t->depth_loss_weight_ = static_cast<float>(v);
 		else if (k == "depth_min") t->depth_min_ = static_cast<float>(v);
 		else if (k == "depth_max") t->depth_max_ = static_cast<float>(v);
@@ -643,6 +653,7 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("trainer_refine_pose", &trainer_refine_pose);
 	m.def("trainer_state", &trainer_state);
 	m.def("trainer_pose_gradient", &trainer_pose_gradient);
+	m.def("trainer_last_reg_losses", &trainer_last_reg_losses);
 	m.def("trainer_grads", &trainer_grads);
 	m.def("trainer_stats", &trainer_stats);
 	m.def("trainer_create_from_pcd", &trainer_create_from_pcd);

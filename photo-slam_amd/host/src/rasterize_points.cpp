@@ -433,7 +433,33 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 			a.dL_dcampos = a.dL_dviewmatrix + 32;
 			a.pose_scratch = reinterpret_cast<char*>(pose_scratch.data_ptr());
 		}
+		gsr_geom_reg reg{};
+		torch::Tensor reg_scratch;
+		if (ext.geom_reg) {
+			const GeomRegStep& r = *ext.geom_reg;
+			reg.w_opacity = r.w_opacity;
+			reg.w_scale = r.w_scale;
+			reg.w_isotropic = r.w_isotropic;
+			if (r.loss.defined()) {
+				if (r.loss.numel() != 3 || r.loss.scalar_type() != torch::kFloat32 || !r.loss.is_contiguous() || r.loss.device() != means3D.device())
+					throw std::runtime_error("geom_reg: loss must be a contiguous float32 tensor of 3 elements on the device of means3D");
+				const size_t bytes = gsr_geom_reg_scratch_bytes(P);
+				if (ext.workspace) {
+					torch::Tensor& ws = ext.workspace->reg;
+					if (!ws.defined() || ws.device() != means3D.device() || ws.scalar_type() != torch::kByte) ws = torch::empty({0}, means3D.options().dtype(torch::kByte));
+					grow_tensor(&ws, bytes);
+					reg_scratch = ws;
+				} else {
+					reg_scratch = torch::empty({static_cast<int64_t>(bytes)}, means3D.options().dtype(torch::kByte));
+				}
+				reg.loss = r.loss.data_ptr<float>();
+				reg.scratch = reinterpret_cast<char*>(reg_scratch.data_ptr());
+			}
+			a.geom_reg = &reg;
+		}
 		check(gsr_backward(&a, current_stream(means3D)), "RasterizeGaussiansBackwardCUDA");
+	} else if (ext.geom_reg && ext.geom_reg->loss.defined()) {
+		ext.geom_reg->loss.zero_();
 	}
 	if (ext.pose_grad) {
 		// (the [16] arrays hold element (r, c) at [4c + r]: exactly the row-major [4,4] tensors the host passes in)

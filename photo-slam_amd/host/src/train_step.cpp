@@ -389,6 +389,10 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	exposure_grad_ = torch::Tensor();
 	if ((kf->exposure_.defined() || optimize_exposure_) && process_group_)
 		throw std::runtime_error("TrainStep: exposure compensation is not supported with a process group");
+	const bool reg = opacity_reg_ != 0.0 || scale_reg_ != 0.0 || isotropic_reg_ != 0.0;
+	if (reg && (process_group_ || factored_exchange_))
+		throw std::runtime_error("TrainStep: the opacity / scale / isotropy regularisers are not supported with a process group");
+	last_reg_losses_ = torch::Tensor();
 	auto& g = gaussians_;
 	if (optimize_exposure_ && !kf->exposure_.defined())   // the identity at first use
 		kf->exposure_ = torch::eye(3, 4, g->xyz_.options().requires_grad(false));
@@ -440,6 +444,14 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
 	ext.antialiasing_ = antialiasing_;
 	ext.workspace_ = persistent_workspace_ ? &workspace_ : nullptr;
+	torch::Tensor reg_loss;
+	if (reg) {
+		ext.opacity_reg_ = opacity_reg_;
+		ext.scale_reg_ = scale_reg_;
+		ext.isotropic_reg_ = isotropic_reg_;
+		// (the loss values are formed only when somebody reads them)
+		if (read_reg_losses_) ext.reg_loss_ = reg_loss = torch::zeros({3}, g->xyz_.options().dtype(torch::kFloat32).requires_grad(false));
+	}
 	ShAdamStep& sh_adam = ext.sh_adam_;
 	const auto& o = g->opt_;
 	const bool rebuilds = densifyDue();
@@ -576,6 +588,11 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	// the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward()
 	if (!root_grad_.defined() || root_grad_.device() != loss.device()) root_grad_ = torch::ones_like(loss).detach();
 	loss.backward(root_grad_);
+	if (reg_loss.defined()) {
+		// the returned loss = photometric (+ depth) + the three terms the backward pass has just written
+		last_reg_losses_ = reg_loss;
+		loss = loss.detach() + reg_loss.sum();
+	}
 	if (optimize_exposure_ && exposure_leaf.defined()) {
 		exposure_kf_ = kf;
 		exposure_grad_ = exposure_leaf.grad();

@@ -86,12 +86,21 @@ class RasterWorkspace:
     def __init__(self):
         self.bufs = [None, None, None]   # geometry, binning, image
         self.pose = None                 # the pose gradients' scratch (gsr_backward_args.pose_scratch): refinePose allocates nothing per iteration
+        self.reg = None                  # the regularisers' loss scratch (gsr_geom_reg.scratch)
 
     def pose_scratch(self, nbytes, dev):
         b = self.pose
         if b is None or b.device != dev or b.numel() < int(nbytes):
             self.pose = b = None
             self.pose = b = torch.empty((int(nbytes) + int(nbytes) // 2,), dtype=torch.uint8, device=dev)
+        return b
+
+    def reg_scratch(self, nbytes, dev):
+        """the regularisers' loss scratch (gsr_geom_reg.scratch)"""
+        b = self.reg
+        if b is None or b.device != dev or b.numel() < int(nbytes):
+            self.reg = b = None
+            self.reg = b = torch.empty((int(nbytes) + int(nbytes) // 2,), dtype=torch.uint8, device=dev)
         return b
 
     def taker(self, i, dev):
@@ -218,7 +227,8 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                                    viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                    geomBuffer, R, binningBuffer, imageBuffer, raw_params=0, dL_dcolor_view=None, sh_adam=None,
                                    view_stats=None, geom_adam=None, training_outputs_only=False, packed_view=None,
-                                   dL_ddepth=None, dL_dalpha=None, pose_grad=False, workspace=None, antialiasing=False):
+                                   dL_ddepth=None, dL_dalpha=None, pose_grad=False, workspace=None, antialiasing=False,
+                                   geom_reg=None):
     """dL_dcolor_view (extension, default None = reference contract): a [P,3] float tensor that receives the clamp-masked
     colour gradient; dL_dsh is then NOT computed and None is returned in its place (view-factored gradient exchange,
     shGradFromViews below).
@@ -242,7 +252,13 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
     owns the scratch of the sums (otherwise allocated per call).
     antialiasing (extension, default False): the value the forward call was given (GSR_ANTIALIAS; capi.ANTIALIAS in raw_params says
     the same) -- dL_dopacity is then the gradient of the uncompensated opacity, and the compensation's own gradient reaches the
-    covariance, the scales / rotations, the positions and the camera."""
+    covariance, the scales / rotations, the positions and the camera.
+    geom_reg (extension, default None): dict(w_opacity, w_scale, w_isotropic, loss=None) -- the opacity / scale / isotropy
+    regularisers on the Gaussians this view sees (include/gsr.h: gsr_geom_reg) are added to the opacity and scale gradients inside
+    the pass, before they are returned or consumed by geom_adam.  The weights are per Gaussian (the caller normalises them, e.g. by
+    lastVisibleCount()); loss: a contiguous float32 [3] tensor on the device of means3D that receives the three loss values (its
+    scratch comes from `workspace`, or is allocated per call), None = they are not formed.  Not together with dL_dcolor_view or
+    pose_grad.  The return tuple is the same."""
     lib = _lib()
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
@@ -280,6 +296,14 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
         if factored:
             raise RuntimeError("pose_grad is not available through the view-factored exchange (dL_dcolor_view)")
         pose = torch.zeros((35,), **opts) if P == 0 else torch.empty((35,), **opts)
+    reg_loss = None
+    if geom_reg is not None:
+        reg_loss = geom_reg.get("loss")
+        if reg_loss is not None and (reg_loss.shape != (3,) or reg_loss.dtype != torch.float32 or not reg_loss.is_contiguous() or
+                                     reg_loss.device != dev):
+            raise RuntimeError("geom_reg['loss'] must be a contiguous float32 (3,) tensor on the device of means3D")
+        if P == 0 and reg_loss is not None:
+            reg_loss.zero_()
     if P != 0:
         keep = []
         a = capi.BackwardArgs()
@@ -339,6 +363,14 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
             pose_scratch = workspace.pose_scratch(lib_bytes, dev) if workspace is not None else torch.empty((lib_bytes,), dtype=torch.uint8, device=dev)
             a.dL_dviewmatrix, a.dL_dprojmatrix, a.dL_dcampos = pose.data_ptr(), pose.data_ptr() + 64, pose.data_ptr() + 128
             a.pose_scratch = pose_scratch.data_ptr()
+        if geom_reg is not None:
+            gr = capi.GeomReg(float(geom_reg.get("w_opacity", 0.0)), float(geom_reg.get("w_scale", 0.0)),
+                              float(geom_reg.get("w_isotropic", 0.0)), None, None)
+            if reg_loss is not None:
+                lib_bytes = int(lib.gsr_geom_reg_scratch_bytes(P))
+                reg_scratch = workspace.reg_scratch(lib_bytes, dev) if workspace is not None else torch.empty((lib_bytes,), dtype=torch.uint8, device=dev)
+                gr.loss, gr.scratch = reg_loss.data_ptr(), reg_scratch.data_ptr()
+            a.geom_reg = C.pointer(gr)
         st = lib.gsr_backward(C.byref(a), _stream_ptr(means3D))
         capi.check(lib, st, "RasterizeGaussiansBackwardCUDA")
         if not has_sh and dL_dsh is not None:

@@ -256,6 +256,16 @@ class TrainStep:
         # and takes one Adam step on its 12 floats after every backward pass (gsr_adam_step, the model's betas and eps), at a
         # learning rate that falls log-linearly from exposure_lr_init_ to exposure_lr_final_ over exposure_lr_max_steps_ of the
         # keyframe's OWN steps.  refinePose applies a keyframe's exposure and never optimises it.
+        # Regularisers on the Gaussians a view sees, added to the opacity and scale gradients inside the rasterizer's backward
+        # (gsr_backward_args.geom_reg; with fused_geom_adam_ in front of the fused step, so nothing reaches HBM for them):
+        #   opacity_reg_ * mean_V sigmoid(opacity) + scale_reg_ * mean_V,k exp(scaling) (the L1 terms of 3DGS-MCMC, which push
+        #   Gaussians that explain nothing towards the pruning thresholds) + isotropic_reg_ * mean_V,k |s_k - mean_k s| (MonoGS)
+        # over the V Gaussians with radii > 0 in the view.  All 0 = off: no struct is passed and the kernels are those without it.
+        # last_reg_losses: the three terms of the last step whose loss was read (sync_loss), a [3] tensor, else None.
+        self.opacity_reg_ = 0.0
+        self.scale_reg_ = 0.0
+        self.isotropic_reg_ = 0.0
+        self.last_reg_losses = None
         self.optimize_exposure_ = False
         self.exposure_lr_init_ = 0.01
         self.exposure_lr_final_ = 0.001
@@ -455,6 +465,15 @@ class TrainStep:
         if exposure is not None and self.world_size_ > 1:
             raise RuntimeError("TrainStep: exposure compensation is not supported with a process group")
         g, opt = self.gaussians_, self.opt_
+        geom_reg = None
+        if self.opacity_reg_ or self.scale_reg_ or self.isotropic_reg_:
+            if self.world_size_ > 1:
+                raise RuntimeError("TrainStep: the opacity / scale / isotropy regularisers are not supported with a process group")
+            # (the loss values are formed only on steps whose loss somebody reads)
+            geom_reg = dict(lambda_opacity=float(self.opacity_reg_), lambda_scale=float(self.scale_reg_),
+                            lambda_isotropic=float(self.isotropic_reg_),
+                            loss=torch.zeros(3, dtype=torch.float32, device=g.xyz_.device) if sync_loss else None)
+        self.last_reg_losses = None
         self.iteration_ += 1
         it = self.iteration_
         g.updateLearningRate(it if position_lr_step is None else min(int(position_lr_step), opt.position_lr_max_steps_))   # :661-674
@@ -502,7 +521,7 @@ class TrainStep:
                 sh_grad_view=sh_view, sh_adam=fwd_adam, view_stats=view_stats, geom_adam=geom_adam,
                 training_outputs_only=True,   # the statistics are fused (or over): nobody reads the viewspace gradient
                 cull_empty_tiles=self.cull_empty_tiles_, workspace=self.workspace_ if self.persistent_workspace_ else None,
-                render_depth=use_depth, antialiasing=self.antialiasing_)
+                render_depth=use_depth, antialiasing=self.antialiasing_, geom_reg=geom_reg)
             rendered_image, viewspace_point_tensor, visibility_filter, radii = out[:4]
         finally:
             g._in_lazy_step = False
@@ -518,6 +537,10 @@ class TrainStep:
         if getattr(self, "_root_grad", None) is None or self._root_grad.device != loss.device:
             self._root_grad = torch.ones_like(loss).detach()
         loss.backward(self._root_grad)
+        if geom_reg is not None and geom_reg["loss"] is not None:
+            # the returned loss = photometric (+ depth) + the three terms the backward pass has just written
+            self.last_reg_losses = geom_reg["loss"]
+            loss = loss.detach() + geom_reg["loss"].sum()
         if sh_adam is not None:
             g.optimizer_.end_fused_step(FEATURES_GROUP, sh_adam)
         with torch.no_grad():
