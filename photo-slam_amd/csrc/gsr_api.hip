@@ -8,7 +8,7 @@
 //      mapped host memory, event behind them -- the reference blocks on a copy here, :281) -> exclusive scan in depth order
 //   -> host waits for the event only now, sizes the binning buffer
 //   -> emit instances -> tile-id sort over R (ceil(msb(T)/8) passes) -> tile ranges -> blend.
-// Tile-first binning (binning_tile_first below; small and mid-size views): no depth sort of the Gaussians -- the visible ones are
+// Tile-first binning (binning_tile_first below; models of up to 2 Mi Gaussians): no depth sort of the Gaussians -- the visible ones are
 // compacted in id order (the count for the host by a one-workgroup launch in front of the compaction), and behind the tile sort
 // every tile's list is sorted by depth on its own (tile_depth_sort.hip): 12 launches instead of 20, the same lists bit for bit.
 #include <atomic>
@@ -211,19 +211,29 @@ static bool emit_hist()
 // Which binning: depth-first (sort the Gaussians by depth, emit in that order: nine launches for the sort whatever the size) or
 // tile-first (compact in id order, sort every tile's list by depth behind the tile sort).  gsr_forward_args.raw_params may force
 // either (GSR_BINNING_DEPTH_FIRST / GSR_BINNING_TILE_FIRST); GSR_BINNING=0/1 overrides (the A/B handle); otherwise by size.
-constexpr int TILE_FIRST_MAX_GAUSSIANS = 256 * 1024;
+constexpr int TILE_FIRST_MAX_GAUSSIANS = 2 * 1024 * 1024;
 static bool binning_tile_first(int raw_params, int P, int tiles)
 {
 	static const int env = env_int("GSR_BINNING", -1);
 	if (env >= 0) return env != 0;
 	if (raw_params & GSR_BINNING_TILE_FIRST) return true;
 	if (raw_params & GSR_BINNING_DEPTH_FIRST) return false;
-	// Measured (profiles/r06_c, r06_d; same box, alternating): the depth sort of the Gaussians is launch-bound up to ~0.5 M visible
-	// ones (60 us at 17 k keys, 62 us at 262 k), the per-tile sorts cost ~17-40 ns per thousand instances.  50 k Gaussians @ 640 x 480:
-	// the step 0.292 -> 0.259 ms tile-first; 500 k @ 1200 x 680: 0.696 -> 0.686; 2 M @ 1080p: 1.567 -> 1.569; 4 M @ 752 x 480: equal.
+	// Measured (profiles/r08_b, r08_c; same box, alternating runs, medians of 100 steps; depth-first / tile-first): the depth sort of
+	// the Gaussians and the offset scan cost 127 us at 2 M Gaussians (78 us at 500 k: launch-bound), the compaction that replaces them
+	// 41 (26); the per-tile sorts, with 9-bit digits and two passes + fix-up for lists in LDS, 83 us at 2 M @ 1080p (6.2 M instances, no
+	// list beyond 2 048 entries).  500 k @ 1200 x 680: the step 0.672 -> 0.639 ms; 2 M @ 1080p: 1.466 -> 1.445; 2 M @ 640 x 480: 0.844 ->
+	// 0.821; every tile-first run below every depth-first run (at 2 M @ 1080p on one box of three: two repeat sessions gave +4 and
+	// -25 us with overlapping runs, the binning stages 10-15 us shorter in all eleven pairs, EXPERIMENTS R8).  4 M @ 752 x 480 (lists of 2 755 entries on average: the chunked path,
+	// 144 us): 1.591 -> 1.580 over eight pairs whose runs overlap -- a tie, left depth-first.  (50 k @ 640 x 480: 0.292 -> 0.259, r06_c.)
 	// The instance count is not known when the choice is made: the model's size stands in for it.
 	(void)tiles;
 	return P <= TILE_FIRST_MAX_GAUSSIANS;
+}
+// GSR_TILE_SORT_FIXUP=0: the per-tile depth sort takes its exact passes always (the A/B handle of its two-pass form)
+static bool tile_sort_fixup()
+{
+	static const int env = env_int("GSR_TILE_SORT_FIXUP", 1);
+	return env != 0;
 }
 static int side_blocks(const gsr_sh_adam* o)
 {
@@ -540,7 +550,7 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 			// forward-only: an array of their own)
 			const bool in_a = point_list == bs.vals_a;
 			if ((st = launch_tile_depth_sort(im.ranges, tiles, g.depth_key, point_list, in_a ? bs.keys_b : bs.keys_a, in_a ? bs.vals_b : bs.vals_a,
-			                                 bs.spare_words, stream)) != GSR_OK)
+			                                 bs.spare_words, stream, tile_sort_fixup())) != GSR_OK)
 				return st;
 		}
 	} else {

@@ -290,8 +290,9 @@ int launch_compact_visible(const uint32_t* tiles_touched, const uint2* rect, con
                            uint32_t* long_counts = nullptr, uint32_t long_capacity = 0, uint32_t* visible_out = nullptr);
 // every tile's list [ranges[t].x, ranges[t].y) of point_list (ascending id on entry) sorted by depth_key[id], stable: one workgroup
 // per tile.  spare_keys / spare_vals / spare_words: three arrays as long as point_list; tile t uses its own segment of each.
+// fixup: lists in LDS with 19 .. 27 bits of key span take two passes and the fix-up (false: the exact passes always).
 int launch_tile_depth_sort(const uint2* ranges, int tiles, const uint32_t* depth_key, uint32_t* point_list, uint32_t* spare_keys,
-                           uint32_t* spare_vals, uint32_t* spare_words, hipStream_t stream);
+                           uint32_t* spare_vals, uint32_t* spare_words, hipStream_t stream, bool fixup = true);
 // A job that rides in the first two launches of a sort: add up n (a, b) pairs -- every histogram workgroup its share into
 // partials[block], an extra workgroup of the row-prefix launch the partials -- and store the totals, sum a as 64 bits in
 // host_out[0..1], sum b in host_out[2], into MAPPED HOST memory; `ready` (a hipEvent_t, nullable) is recorded right behind the

@@ -10,7 +10,17 @@
 //
 // Per pass the digits are ranked as in radix_scatter_kernel (sort.hip): per wave by ballots (wave_match_digit), across the
 // four waves and the digits by one block scan; only the bits in which the tile's keys differ are sorted (key - min over the
-// list: a tile that sees one wall sorts a dozen bits).
+// list: a tile that sees one wall sorts a dozen bits).  A pass costs its barriers, its counter clear and its scan whatever the
+// list's length, so the digits are as wide as the ballots allow: nine bits, 512 bins, two of them per thread -- a span of
+// 19 .. 27 bits takes three passes, 10 .. 18 bits two.
+//
+// Lists in LDS whose keys span 19 .. 27 bits take two passes and a fix-up instead of three passes: the two passes sort, exactly
+// and stably, on the top 18 bits of key - min.  Entries with equal 18-bit prefixes are then contiguous and in arrival (id) order;
+// with a thousand keys over 2^18 buckets such runs are rare and short (the 2 M-Gaussian view at 1080p: a dozen runs per list, none
+// longer than five).  Every entry finds its rank inside its run by comparing its key with up to TDS_CAP - 1 neighbours on either
+// side -- earlier entries with a larger key move behind it, later ones with a smaller key in front of it, equal keys keep their
+// order -- and is stored at its final place.  A list with a run of more than TDS_CAP entries takes the exact passes instead, from
+// the order the two passes left: a stable sort of a stably sorted list gives the same answer.
 #include "state.h"
 #include "wave64.h"
 #include "kernels.h"
@@ -20,31 +30,37 @@ namespace gsr {
 constexpr int TDS_THREADS = 256, TDS_WAVES = TDS_THREADS / 64;
 constexpr int TDS_CHUNK = 2048;                       // entries ranked at a time: eight per thread
 constexpr int TDS_ROUNDS = TDS_CHUNK / TDS_THREADS;   // rounds of 64 lane-consecutive entries per wave
-constexpr int TDS_BITS = 8, TDS_BINS = 1 << TDS_BITS;
-static_assert(TDS_BINS == TDS_THREADS, "thread d owns digit d");
+constexpr int TDS_BITS = 9, TDS_BINS = 1 << TDS_BITS;
+constexpr int TDS_CAP = 8;                            // the longest run of equal 18-bit prefixes the fix-up ranks
+static_assert(TDS_BINS == 2 * TDS_THREADS, "thread t owns digits 2 t and 2 t + 1");
+static_assert(TDS_CHUNK < 65536 && TDS_CHUNK / TDS_WAVES <= 65535, "counts and cursors are 16-bit");
+
+typedef uint32_t __attribute__((may_alias)) tds_pair_t;   // two neighbouring 16-bit counters read or written as one word
 
 struct TdsShared {
-	uint32_t whist[TDS_WAVES][TDS_BINS];   // per-wave digit counts, then per-wave write cursors
-	uint32_t gbase[TDS_BINS];              // long lists: destination of local element i of digit d = gbase[d] + i
+	// per-wave digit counts (a wave holds up to 512 entries), then per-wave write cursors (< 2 048): 16 bits each, so that 512
+	// bins take the 4 KB that 256 bins of 32 bits took -- the LDS footprint is unchanged (22.6 KB)
+	uint16_t whist[TDS_WAVES][TDS_BINS];
 	uint32_t cur[TDS_BINS];                // long lists: the pass's running cursor per digit
 	uint32_t keys[TDS_CHUNK];
 	uint32_t vals[TDS_CHUNK];
 	uint32_t wave[4];
 	uint32_t red[2 * TDS_WAVES];
+	uint32_t long_run;                     // the fix-up met a run of more than TDS_CAP entries
 };
 
 // Ranks the chunk the workgroup holds in registers -- wave w, round r, lane l holds local element w * span + r * 64 + l, `live`
 // bit r says whether it exists -- by the digit ((key - bias) >> shift) & mask, stable, and leaves it in S.keys / S.vals in that
-// order.  between(lstart, tot): called by thread d with digit d's first local position and count, after the scan and in front of
-// the barrier that precedes the placement.
-template <class Between>
+// order.  tot0 / tot1: the chunk's counts of the thread's two digits, 2 tid and 2 tid + 1.  On return S.whist[w][d] is wave w's
+// cursor BEHIND its last element of digit d: S.whist[TDS_WAVES - 1][d] is the first local position of digit d + 1.
 __device__ __forceinline__ void tds_rank_chunk(const uint32_t (&key)[TDS_ROUNDS], const uint32_t (&val)[TDS_ROUNDS], uint32_t live, int rounds,
-                                               uint32_t bias, int shift, int nbits, TdsShared& S, Between&& between)
+                                               uint32_t bias, int shift, int nbits, TdsShared& S, uint32_t& tot0, uint32_t& tot1)
 {
 	const int w = wave_id(), tid = (int)threadIdx.x;
 	const uint32_t dmask = (1u << nbits) - 1u;
+	tds_pair_t* const pairs = reinterpret_cast<tds_pair_t*>(&S.whist[0][0]);   // pairs[i * TDS_THREADS + t] = whist[i][2 t], [2 t + 1]
 #pragma unroll
-	for (int i = 0; i < TDS_WAVES; i++) S.whist[i][tid] = 0u;
+	for (int i = 0; i < TDS_WAVES; i++) pairs[i * TDS_THREADS + tid] = 0u;
 	__syncthreads();
 	uint32_t place[TDS_ROUNDS];   // rank inside the lane's digit group of the round (low byte) | group size << 8
 #pragma unroll
@@ -56,21 +72,30 @@ __device__ __forceinline__ void tds_rank_chunk(const uint32_t (&key)[TDS_ROUNDS]
 			const unsigned long long m = wave_match_digit(d, nbits, valid);
 			const uint32_t rank = (uint32_t)__popcll(m & lanemask_lt()), size = (uint32_t)__popcll(m);
 			place[r] = rank | (size << 8);
-			if (valid && rank == 0u) S.whist[w][d] += size;   // (the groups of one wave touch distinct bins)
+			if (valid && rank == 0u) S.whist[w][d] = (uint16_t)(S.whist[w][d] + size);   // (the groups of one wave touch distinct bins)
 			wave_fence();
 		}
 	}
 	__syncthreads();
 	{
-		const uint32_t c0 = S.whist[0][tid], c1 = S.whist[1][tid], c2 = S.whist[2][tid], c3 = S.whist[3][tid];
-		const uint32_t tot = c0 + c1 + c2 + c3;
+		uint32_t c[TDS_WAVES];
+		tot0 = 0u;
+		tot1 = 0u;
+#pragma unroll
+		for (int i = 0; i < TDS_WAVES; i++) {
+			c[i] = pairs[i * TDS_THREADS + tid];
+			tot0 += c[i] & 0xFFFFu;
+			tot1 += c[i] >> 16;
+		}
 		uint32_t all;
-		const uint32_t lstart = block_excl_scan_256(tot, &all, S.wave);
-		S.whist[0][tid] = lstart;
-		S.whist[1][tid] = lstart + c0;
-		S.whist[2][tid] = lstart + c0 + c1;
-		S.whist[3][tid] = lstart + c0 + c1 + c2;
-		between(lstart, tot);
+		uint32_t at0 = block_excl_scan_256(tot0 + tot1, &all, S.wave);
+		uint32_t at1 = at0 + tot0;
+#pragma unroll
+		for (int i = 0; i < TDS_WAVES; i++) {
+			pairs[i * TDS_THREADS + tid] = at0 | (at1 << 16);
+			at0 += c[i] & 0xFFFFu;
+			at1 += c[i] >> 16;
+		}
 	}
 	__syncthreads();
 #pragma unroll
@@ -85,7 +110,7 @@ __device__ __forceinline__ void tds_rank_chunk(const uint32_t (&key)[TDS_ROUNDS]
 			if (valid) {
 				S.keys[cursor + rank] = key[r];
 				S.vals[cursor + rank] = val[r];
-				if (rank == 0u) S.whist[w][d] = cursor + size;
+				if (rank == 0u) S.whist[w][d] = (uint16_t)(cursor + size);
 			}
 			wave_fence();
 		}
@@ -102,16 +127,18 @@ __device__ __forceinline__ void tds_block_min_max(uint32_t lo, uint32_t hi, TdsS
 		S.red[wave_id()] = wlo;
 		S.red[TDS_WAVES + wave_id()] = whi;
 	}
+	if (threadIdx.x == 0) S.long_run = 0u;
 	__syncthreads();
 	kmin = min(min(S.red[0], S.red[1]), min(S.red[2], S.red[3]));
 	kmax = max(max(S.red[TDS_WAVES], S.red[TDS_WAVES + 1]), max(S.red[TDS_WAVES + 2], S.red[TDS_WAVES + 3]));
 }
 
 // xk / xv: the tile sort's spare (key, value) arrays; yk: one more array of R words (the forward blend's flag planes, not yet
-// written).  Tile t only touches [ranges[t].x, ranges[t].y) of each.
+// written).  Tile t only touches [ranges[t].x, ranges[t].y) of each.  fixup: lists in LDS with 19 .. 27 bits of span take two
+// passes and the fix-up (0: the exact passes always).
 __global__ void __launch_bounds__(TDS_THREADS)
 tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles, const uint32_t* __restrict__ depth_key, uint32_t* point_list,
-                       uint32_t* xk, uint32_t* xv, uint32_t* yk)
+                       uint32_t* xk, uint32_t* xv, uint32_t* yk, int fixup)
 {
 	__shared__ TdsShared S;
 	const int tile = (int)blockIdx.x;
@@ -122,6 +149,7 @@ tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles, const uint32
 	const int w = wave_id(), l = lane_id(), tid = (int)threadIdx.x;
 	uint32_t* const pl = point_list + range.x;
 	uint32_t key[TDS_ROUNDS], val[TDS_ROUNDS];
+	uint32_t tot0, tot1;
 
 	if (n <= TDS_CHUNK) {
 		// ---- the list fits the workgroup's registers and LDS: every pass stays there
@@ -149,20 +177,72 @@ tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles, const uint32
 		tds_block_min_max(lo, hi, S, kmin, kmax);
 		if (kmax == kmin) return;   // (one depth: the id order the list arrived in is the answer)
 		const int bits = 32 - __builtin_clz(kmax - kmin);
+		// the chunk back into the registers in the order a pass left it: position e to wave w, round r, lane l
+		auto reload = [&]() {
+#pragma unroll
+			for (int r = 0; r < TDS_ROUNDS; r++)
+				if ((live >> r) & 1u) {
+					const int e = w * span + r * 64 + l;
+					key[r] = S.keys[e];
+					val[r] = S.vals[e];
+				}
+			// (the next pass writes S.keys only behind two more barriers)
+		};
+		if (fixup && bits > 2 * TDS_BITS && bits <= 3 * TDS_BITS) {
+			const int low = bits - 2 * TDS_BITS;   // 1 .. 9 bits below the prefix
+			for (int p = 0; p < 2; p++) {
+				tds_rank_chunk(key, val, live, rounds, kmin, low + p * TDS_BITS, TDS_BITS, S, tot0, tot1);
+				reload();
+			}
+			int pos[TDS_ROUNDS];
+			bool long_run = false;
+#pragma unroll
+			for (int r = 0; r < TDS_ROUNDS; r++) {
+				pos[r] = 0;
+				if (r < rounds) {   // (block-uniform: the ballot below is reached by whole waves)
+					const bool valid = (live >> r) & 1u;
+					const int e = w * span + r * 64 + l;
+					const uint32_t mine = key[r] - kmin;
+					pos[r] = e;
+					// (the trip count is at most TDS_CAP: a run is contiguous, so when no entry of the wave has a neighbour of its
+					// run at this distance none has one farther away)
+					for (int off = 1; off <= TDS_CAP; off++) {
+						const int a = e - off, b = e + off;
+						uint32_t ka = 0u, kb = 0u;
+						bool sa = false, sb = false;
+						if (valid && a >= 0) {
+							ka = S.keys[a] - kmin;
+							sa = (ka >> low) == (mine >> low);
+						}
+						if (valid && b < n) {
+							kb = S.keys[b] - kmin;
+							sb = (kb >> low) == (mine >> low);
+						}
+						if (wave_ballot(sa || sb) == 0ull) break;
+						if (off == TDS_CAP) {
+							long_run = long_run || sa || sb;   // the run has more than TDS_CAP entries
+						} else {
+							pos[r] -= (sa && ka > mine) ? 1 : 0;
+							pos[r] += (sb && kb < mine) ? 1 : 0;
+						}
+					}
+				}
+			}
+			if (long_run) S.long_run = 1u;
+			__syncthreads();
+			if (S.long_run == 0u) {   // (the same word in every thread)
+#pragma unroll
+				for (int r = 0; r < TDS_ROUNDS; r++)
+					if ((live >> r) & 1u) pl[pos[r]] = val[r];
+				return;
+			}
+			// the exact passes, from the order the two passes left in the registers
+		}
 		const int passes = (bits + TDS_BITS - 1) / TDS_BITS, bpp = (bits + passes - 1) / passes;
 		for (int p = 0; p < passes; p++) {
 			const int shift = p * bpp, nbits = min(bpp, bits - shift);
-			tds_rank_chunk(key, val, live, rounds, kmin, shift, nbits, S, [](uint32_t, uint32_t) {});
-			if (p + 1 < passes) {
-#pragma unroll
-				for (int r = 0; r < TDS_ROUNDS; r++)
-					if ((live >> r) & 1u) {
-						const int e = w * span + r * 64 + l;
-						key[r] = S.keys[e];
-						val[r] = S.vals[e];
-					}
-				// (the next pass writes S.keys only behind two more barriers)
-			}
+			tds_rank_chunk(key, val, live, rounds, kmin, shift, nbits, S, tot0, tot1);
+			if (p + 1 < passes) reload();
 		}
 		for (int i = tid; i < n; i += TDS_THREADS) pl[i] = S.vals[i];
 		return;
@@ -189,15 +269,17 @@ tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles, const uint32
 		const int shift = p * bpp, nbits = min(bpp, bits - shift);
 		const uint32_t dmask = (1u << nbits) - 1u;
 		// the pass's digit counts over the whole list -> the first position of every digit
-		S.cur[tid] = 0u;
+		S.cur[2 * tid] = 0u;
+		S.cur[2 * tid + 1] = 0u;
 		__syncthreads();
 		for (int i = tid; i < n; i += TDS_THREADS) atomicAdd(&S.cur[((ak[i] - kmin) >> shift) & dmask], 1u);
 		__syncthreads();
 		{
-			const uint32_t c = S.cur[tid];
+			const uint32_t c0 = S.cur[2 * tid], c1 = S.cur[2 * tid + 1];
 			uint32_t all;
-			const uint32_t ex = block_excl_scan_256(c, &all, S.wave);
-			S.cur[tid] = ex;
+			const uint32_t ex = block_excl_scan_256(c0 + c1, &all, S.wave);
+			S.cur[2 * tid] = ex;
+			S.cur[2 * tid + 1] = ex + c0;
 		}
 		__syncthreads();
 		for (int base = 0; base < n; base += TDS_CHUNK) {
@@ -214,17 +296,20 @@ tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles, const uint32
 					live |= 1u << r;
 				}
 			}
-			tds_rank_chunk(key, val, live, TDS_ROUNDS, kmin, shift, nbits, S, [&](uint32_t lstart, uint32_t tot) {
-				S.gbase[tid] = S.cur[tid] - lstart;
-				S.cur[tid] += tot;
-			});
+			tds_rank_chunk(key, val, live, TDS_ROUNDS, kmin, shift, nbits, S, tot0, tot1);
+			// local element i of digit d goes to cur[d] + i - (the first local position of digit d)
 			for (int i = tid; i < cn; i += TDS_THREADS) {
 				const uint32_t k = S.keys[i];
-				const uint32_t pos = S.gbase[((k - kmin) >> shift) & dmask] + (uint32_t)i;
+				const uint32_t d = ((k - kmin) >> shift) & dmask;
+				const uint32_t first = d ? (uint32_t)S.whist[TDS_WAVES - 1][d - 1u] : 0u;
+				const uint32_t pos = S.cur[d] + (uint32_t)i - first;
 				bk[pos] = k;
 				bv[pos] = S.vals[i];
 			}
-			// (the next chunk writes S.gbase / S.keys only behind the barriers of its own ranking)
+			__syncthreads();   // everyone has read the cursors; the next chunk's ranking clears S.whist at once
+			S.cur[2 * tid] += tot0;
+			S.cur[2 * tid + 1] += tot1;
+			// (read again only behind the barriers of the next chunk's ranking)
 		}
 		__syncthreads();   // the pass's output is complete (and visible to the workgroup) before it is read as the next input
 		uint32_t* t = ak; ak = bk; bk = t;
@@ -235,11 +320,12 @@ tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles, const uint32
 }
 
 int launch_tile_depth_sort(const uint2* ranges, int tiles, const uint32_t* depth_key, uint32_t* point_list, uint32_t* spare_keys,
-                           uint32_t* spare_vals, uint32_t* spare_words, hipStream_t stream)
+                           uint32_t* spare_vals, uint32_t* spare_words, hipStream_t stream, bool fixup)
 {
 	if (!ranges || !depth_key || !point_list || !spare_keys || !spare_vals || !spare_words) return GSR_ERR_INVALID_ARG;
 	if (tiles <= 0) return GSR_OK;
-	GSR_LAUNCH(tile_depth_sort_kernel, tiles, TDS_THREADS, stream, ranges, tiles, (const uint32_t*)depth_key, point_list, spare_keys, spare_vals, spare_words);
+	GSR_LAUNCH(tile_depth_sort_kernel, tiles, TDS_THREADS, stream, ranges, tiles, (const uint32_t*)depth_key, point_list, spare_keys, spare_vals, spare_words,
+	           fixup ? 1 : 0);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }
