@@ -647,6 +647,62 @@ typedef struct gsr_densify_gather_args {
 size_t gsr_densify_morton_scratch_bytes(int n_new);
 int gsr_densify_gather(const gsr_densify_gather_args* args, const char* scratch, void* stream);
 
+/* ---- fixed-budget maps: 3DGS-MCMC relocation, growth and position noise (Kheradmand et al. 2024) ----
+ * The other half of the method whose opacity / scale L1 terms are gsr_geom_reg: instead of cloning and splitting by a gradient
+ * threshold, dead Gaussians (sigmoid(opacity) <= min_opacity) are re-spawned on live ones drawn in proportion to their
+ * opacity, the model grows by 5 % per event up to a cap, and every step adds covariance-shaped noise to the positions.  The
+ * row count never changes on a relocation, so no tensor is rebuilt: gsr_mcmc_relocate works IN PLACE on the five raw
+ * parameter tensors and their ten Adam moments.  No host synchronisation, no floating-point atomics; the same inputs give
+ * the same bits on every run.
+ *
+ *   o_i = sigmoid(opacity_i) in fp32 (as gsr_densify_select forms it);  row i is dead iff o_i <= min_opacity
+ *   w_i = (uint32) lrintf(o_i * 2^24);  relocating (n_add == 0): w_i = 0 for dead rows;  growing: every row keeps its weight
+ *         (upstream's add_new_gs samples over all rows)
+ *   C   = inclusive prefix sum of w in uint64 (exact, independent of order)
+ *   destinations: relocating, the dead rows in index order, the k-th takes draws[k]; dead rows of rank >= n_draws stay as
+ *         they are.  Growing, row P + k takes draws[k], k < n_add.
+ *   source of a draw u: t = min((uint64)((double)u * (double)C[P-1]), C[P-1] - 1), the first s with C[s] > t.
+ *         C[P-1] == 0: nothing moves.
+ *   N_s = 1 + number of draws that chose s, capped at 51 in the formulas:
+ *         o'     = 1 - (1 - o_s)^(1/N), clamped to [min_opacity, 1 - 2^-24]
+ *         D      = sum_{i=1..N} sum_{k=0..i-1} C(i-1,k) (-1)^k o'^(k+1) / sqrt(k+1)          (both formed in double)
+ *         scale' = exp(scaling_s) * o_s / D
+ *   every source with N_s > 1 and every destination of it store opacity = logit(o'), scaling = log(scale'); a destination
+ *   also copies xyz, the SH row and the rotation of its source and inherits its exist_since_iter, and its three statistics
+ *   are zeroed.  The moments of all five tensors are zeroed at every destination and at every source with N_s > 1.
+ *   Every other row of every array is left untouched. */
+typedef struct gsr_mcmc_relocate_args {
+	int P;                      /* live rows */
+	int n_add;                  /* 0 = relocate; > 0 = grow: rows [P, P + n_add) of EVERY array below are destinations (the
+	                               caller guarantees the room) */
+	int n_draws;                /* >= n_add */
+	int features_row_floats;    /* 3 * M of the [.,M,3] SH tensor */
+	float min_opacity;          /* in (0, 1); 0.005 in both hosts */
+	/* index 0..4 = xyz [.,3], features [.,M,3], opacity [.,1], scaling [.,3], rotation [.,4] (the raw parameters), UPDATED IN
+	 * PLACE; the moments may be NULL, all ten together, when no optimizer state exists */
+	float* param[5];
+	float* exp_avg[5];
+	float* exp_avg_sq[5];
+	const float* draws;         /* [n_draws] uniform draws in [0, 1): the caller's, like samples of gsr_densify_gather */
+	int* exist_since_iter;      /* optional [.] int32 */
+	float* stats[3];            /* optional xyz_gradient_accum, denom, max_radii2D ([.] each); NULL = skip */
+	uint32_t* out_weights;      /* optional [P]: exactly the weights used */
+} gsr_mcmc_relocate_args;
+size_t gsr_mcmc_scratch_bytes(int P, int n_draws);
+/* counts: DEVICE int[8], written on the stream: [0] dead rows, [1] destinations written, [2] distinct sources with N > 1,
+ * [3] the largest N (uncapped; 0 when nothing moved), the rest zero.  scratch: gsr_mcmc_scratch_bytes(P, n_draws) device
+ * bytes.  P == 0 writes zeros to counts and nothing else. */
+int gsr_mcmc_relocate(const gsr_mcmc_relocate_args* args, char* scratch, int* counts, void* stream);
+
+/* The position noise of 3DGS-MCMC's Langevin step, on the raw parameters, one launch:
+ *   o_i = sigmoid(opacity_i);  g_i = 1 / (1 + expf(100 * (o_i - 0.005)))   (upstream's sigmoid(100 * ((1 - o) - 0.995)); an
+ *         opaque Gaussian gets exactly 0: the exponential overflows to +inf and the quotient stays finite)
+ *   Sigma_i = R(q_i) diag(exp(scaling_i)^2) R(q_i)^T, q normalised as under GSR_RAW_ROTATION, built as gsr_forward builds it
+ *   xyz_i += Sigma_i * (z_i * (g_i * noise_scale))
+ * z: [P,3] STANDARD normal draws, the caller's.  xyz is UPDATED IN PLACE. */
+int gsr_mcmc_add_noise(int P, float* xyz, const float* opacity, const float* scaling, const float* rotation, const float* z,
+                       float noise_scale, void* stream);
+
 /* ---- Photo-SLAM's point-cloud kernels ----
  * transformPoints (src/operate_points.cu:73-93): out = M[:3,:4] * (p, 1), M = transformmatrix[16] with
  * element (r,c) at [4c+r] (transformPoint4x3). */

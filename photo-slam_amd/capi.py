@@ -138,6 +138,13 @@ class DensifyGatherArgs(C.Structure):
                 ("exist_since_iter_out", C.c_void_p), ("morton_scratch", C.c_void_p)]
 
 
+class McmcRelocateArgs(C.Structure):
+    """gsr_mcmc_relocate_args"""
+    _fields_ = [("P", C.c_int), ("n_add", C.c_int), ("n_draws", C.c_int), ("features_row_floats", C.c_int),
+                ("min_opacity", C.c_float), ("param", C.c_void_p * 5), ("exp_avg", C.c_void_p * 5), ("exp_avg_sq", C.c_void_p * 5),
+                ("draws", C.c_void_p), ("exist_since_iter", C.c_void_p), ("stats", C.c_void_p * 3), ("out_weights", C.c_void_p)]
+
+
 RAW_OPACITY, RAW_SCALING, RAW_ROTATION = 1, 2, 4   # GSR_RAW_* of include/gsr.h
 CULL_EMPTY_TILES, FORWARD_ONLY = 8, 128             # GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY
 ANTIALIAS = 256                                     # GSR_ANTIALIAS: forward AND backward (the same value in both calls)
@@ -158,6 +165,7 @@ EXPORTED_SYMBOLS = [
     "gsr_depth_loss_scratch_bytes", "gsr_depth_l1_loss", "gsr_pose_grad_scratch_bytes",
     "gsr_loss_exposure_scratch_bytes", "gsr_l1_ssim_loss_exposure", "gsr_apply_exposure",
     "gsr_geom_reg_scratch_bytes",
+    "gsr_mcmc_scratch_bytes", "gsr_mcmc_relocate", "gsr_mcmc_add_noise",
 ]
 
 _libs = {}
@@ -242,6 +250,12 @@ def load(path=None):
     L.gsr_densify_morton_scratch_bytes.argtypes = [i32]
     L.gsr_densify_gather.restype = i32
     L.gsr_densify_gather.argtypes = [C.POINTER(DensifyGatherArgs), vp, vp]
+    L.gsr_mcmc_scratch_bytes.restype = sz
+    L.gsr_mcmc_scratch_bytes.argtypes = [i32, i32]
+    L.gsr_mcmc_relocate.restype = i32
+    L.gsr_mcmc_relocate.argtypes = [C.POINTER(McmcRelocateArgs), vp, vp, vp]
+    L.gsr_mcmc_add_noise.restype = i32
+    L.gsr_mcmc_add_noise.argtypes = [i32, vp, vp, vp, vp, vp, f32, vp]
     L.gsr_transform_points.restype = i32
     L.gsr_transform_points.argtypes = [i32, vp, vp, vp, vp]
     L.gsr_scale_transform_points.restype = i32

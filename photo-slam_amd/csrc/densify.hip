@@ -285,6 +285,353 @@ densify_plan_positions_kernel(int n_new, const uint32_t* __restrict__ src_of, co
 
 static inline int densify_blocks(int P) { return div_up(P, DS_BLOCK); }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// 3DGS-MCMC relocation / growth (include/gsr.h).  Sampling in proportion to opacity is made exact and order-independent by
+// integer weights w = lrintf(o * 2^24) and their uint64 prefix C: a draw's source is a binary search in C.
+//
+//   mcmc_weight_kernel : o, dead flag, w per row; block totals of w (uint64) and of the dead flags
+//   mcmc_spine_kernel  : exclusive scan of both over the blocks (one workgroup, chunks of 1024 as densify_spine_kernel),
+//                        counts[0] = dead rows, counts[1] = destinations
+//   mcmc_prefix_kernel : C per row; the dead rows ranked with ballots -> dest_of[k] (as densify_plan_kernel ranks its flags)
+//   mcmc_sample_kernel : one thread per destination: t, binary search, src_of[k]; draws per source counted with an integer
+//                        atomicAdd (the totals do not depend on the order)
+//   mcmc_source_kernel : every source with N > 1: o', D in double, opacity and scale rewritten, its moments zeroed
+//   mcmc_move_kernel   : one work item per unit of a destination row: copies xyz / SH / rotation and the source's NEW opacity
+//                        and scale (destinations and sources are disjoint: relocating, dead rows have weight 0; growing, the
+//                        destinations are rows >= P), zero moments and statistics, exist_since_iter of the source
+//   mcmc_finish_kernel : counts[2], counts[3] from the per-block results of mcmc_source_kernel
+constexpr int MCMC_NMAX = 51;
+
+struct McmcBinom {
+	double c[MCMC_NMAX][MCMC_NMAX];   // c[n][k] = C(n, k), n < 51: exact in double (C(50,25) = 1.26e14 < 2^53)
+};
+constexpr McmcBinom mcmc_make_binom()
+{
+	McmcBinom b{};
+	for (int n = 0; n < MCMC_NMAX; n++) {
+		b.c[n][0] = 1.0;
+		for (int k = 1; k <= n; k++) b.c[n][k] = b.c[n - 1][k - 1] + (k <= n - 1 ? b.c[n - 1][k] : 0.0);
+	}
+	return b;
+}
+#ifdef GSR_EMU
+static const McmcBinom mcmc_binom = mcmc_make_binom();
+#else
+__constant__ McmcBinom mcmc_binom = mcmc_make_binom();
+#endif
+
+struct McmcRelocate {
+	int P, n_add, n_draws;
+	float min_opacity;
+	int row_floats[5];
+	float* param[5];
+	float* m1[5];
+	float* m2[5];
+	const float* draws;
+	int* exist;
+	float* stats[3];
+	uint32_t* out_weights;
+	// scratch
+	uint32_t* w;           // [P]
+	unsigned long long* C; // [P]
+	uint32_t* cnt;         // [P] draws per source (zeroed by the host call)
+	uint32_t* dest_of;     // [P] k-th dead row (relocating)
+	uint32_t* src_of;      // [n_draws]
+	unsigned long long* blk_w;   // [nblocks] block totals of w -> exclusive offsets
+	uint32_t* blk_dead;    // [nblocks] likewise for the dead flags
+	uint32_t* blk_nsrc;    // [nblocks] sources with N > 1
+	uint32_t* blk_maxn;    // [nblocks] largest N
+	long long items_before[7];   // work items of mcmc_move_kernel per destination row: t[0..4], statistics + exist, end
+};
+
+__device__ __forceinline__ float mcmc_opacity(float logit) { return 1.0f / (1.0f + expf(-logit)); }
+
+__global__ void __launch_bounds__(DS_BLOCK)
+mcmc_weight_kernel(const McmcRelocate p)
+{
+	__shared__ unsigned long long s_w[DS_BLOCK / 64];
+	__shared__ uint32_t s_dead[DS_BLOCK / 64];
+	const int i = (int)blockIdx.x * DS_BLOCK + (int)threadIdx.x;
+	uint32_t w = 0;
+	bool dead = false;
+	if (i < p.P) {
+		const float o = mcmc_opacity(p.param[2][i]);
+		dead = o <= p.min_opacity;
+		w = (dead && p.n_add == 0) ? 0u : (uint32_t)lrintf(o * 16777216.0f);
+		p.w[i] = w;
+		if (p.out_weights) p.out_weights[i] = w;
+	}
+	// 64 weights of at most 2^24: the wave's total fits 32 bits, the block's needs 33
+	const uint32_t wsum = wave_sum_u32(w);
+	const unsigned long long m = wave_ballot(dead);
+	if (lane_id() == 0) {
+		s_w[wave_id()] = wsum;
+		s_dead[wave_id()] = (uint32_t)__popcll(m);
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long t = 0;
+		uint32_t d = 0;
+		for (int k = 0; k < DS_BLOCK / 64; k++) {
+			t += s_w[k];
+			d += s_dead[k];
+		}
+		p.blk_w[blockIdx.x] = t;
+		p.blk_dead[blockIdx.x] = d;
+	}
+}
+
+// exclusive scan over the blocks.  A block total of w is at most 2^32: it is scanned inside a wave as two 32-bit halves of 16
+// and 17 bits (64 lanes: no overflow), and across the waves and the chunks in 64 bits.
+__global__ void __launch_bounds__(1024)
+mcmc_spine_kernel(const McmcRelocate p, int nblocks, int* __restrict__ counts)
+{
+	__shared__ unsigned long long s_wave_w[16];
+	__shared__ uint32_t s_wave_d[16];
+	__shared__ unsigned long long s_carry_w;
+	__shared__ uint32_t s_carry_d;
+	if (threadIdx.x == 0) {
+		s_carry_w = 0;
+		s_carry_d = 0;
+	}
+	__syncthreads();
+	for (int base = 0; base < nblocks; base += 1024) {
+		const int i = base + (int)threadIdx.x;
+		const unsigned long long v = i < nblocks ? p.blk_w[i] : 0ull;
+		const uint32_t d = i < nblocks ? p.blk_dead[i] : 0u;
+		const uint32_t lo = wave_incl_scan_u32((uint32_t)(v & 0xFFFFull)), hi = wave_incl_scan_u32((uint32_t)(v >> 16));
+		const unsigned long long incl_w = ((unsigned long long)hi << 16) + lo;
+		const uint32_t incl_d = wave_incl_scan_u32(d);
+		if (lane_id() == 63) {
+			s_wave_w[wave_id()] = incl_w;
+			s_wave_d[wave_id()] = incl_d;
+		}
+		__syncthreads();
+		unsigned long long off_w = s_carry_w;
+		uint32_t off_d = s_carry_d;
+		for (int k = 0; k < wave_id(); k++) {
+			off_w += s_wave_w[k];
+			off_d += s_wave_d[k];
+		}
+		if (i < nblocks) {
+			p.blk_w[i] = off_w + incl_w - v;
+			p.blk_dead[i] = off_d + incl_d - d;
+		}
+		__syncthreads();
+		if (threadIdx.x == 1023) {
+			s_carry_w = off_w + incl_w;
+			s_carry_d = off_d + incl_d;
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		const uint32_t dead = s_carry_d;
+		uint32_t n_dest = p.n_add > 0 ? (uint32_t)p.n_add : min(dead, (uint32_t)p.n_draws);
+		if (s_carry_w == 0) n_dest = 0;   // no weight anywhere: nothing moves
+		counts[0] = (int)dead;
+		counts[1] = (int)n_dest;
+		for (int k = 2; k < 8; k++) counts[k] = 0;
+	}
+}
+
+__global__ void __launch_bounds__(DS_BLOCK)
+mcmc_prefix_kernel(const McmcRelocate p)
+{
+	__shared__ uint32_t s_w[DS_BLOCK / 64];
+	__shared__ uint32_t s_dead[DS_BLOCK / 64];
+	const int i = (int)blockIdx.x * DS_BLOCK + (int)threadIdx.x;
+	const bool in = i < p.P;
+	const uint32_t w = in ? p.w[i] : 0u;
+	const bool dead = in && mcmc_opacity(p.param[2][i]) <= p.min_opacity;
+	const uint32_t incl = wave_incl_scan_u32(w);
+	const unsigned long long m = wave_ballot(dead);
+	if (lane_id() == 63) s_w[wave_id()] = incl;
+	if (lane_id() == 0) s_dead[wave_id()] = (uint32_t)__popcll(m);
+	__syncthreads();
+	unsigned long long off = p.blk_w[blockIdx.x];
+	uint32_t rank = p.blk_dead[blockIdx.x] + (uint32_t)__popcll(m & lanemask_lt());
+	for (int k = 0; k < wave_id(); k++) {
+		off += s_w[k];
+		rank += s_dead[k];
+	}
+	if (!in) return;
+	p.C[i] = off + incl;
+	if (dead && p.n_add == 0) p.dest_of[rank] = (uint32_t)i;
+}
+
+__global__ void __launch_bounds__(256)
+mcmc_sample_kernel(const McmcRelocate p, const int* __restrict__ counts)
+{
+	const int k = (int)blockIdx.x * 256 + (int)threadIdx.x;
+	if (k >= counts[1]) return;
+	const unsigned long long total = p.C[p.P - 1];
+	unsigned long long t = (unsigned long long)((double)p.draws[k] * (double)total);
+	if (t > total - 1) t = total - 1;
+	// the first s with C[s] > t (C[P-1] = total > t: it exists)
+	int lo = 0, hi = p.P - 1;
+	while (lo < hi) {
+		const int mid = lo + ((hi - lo) >> 1);
+		if (p.C[mid] > t) hi = mid; else lo = mid + 1;
+	}
+	p.src_of[k] = (uint32_t)lo;
+	atomicAdd(&p.cnt[lo], 1u);
+}
+
+// o' and scale' of a source drawn n - 1 times (n >= 2), from its fp32 activated opacity: logit(o') and log(scale' / scale)
+__device__ __forceinline__ void mcmc_new_values(float o_f, uint32_t n_draws_of, float min_opacity, float& new_logit, double& log_ratio)
+{
+	const int N = (int)min(n_draws_of, (uint32_t)MCMC_NMAX);
+	const double o = (double)o_f;
+	double on = 1.0 - pow(1.0 - o, 1.0 / (double)N);
+	on = fmin(fmax(on, (double)min_opacity), 1.0 - 1.0 / 16777216.0);
+	double D = 0.0;
+	for (int i = 1; i <= N; i++) {
+		double pw = on, sgn = 1.0;
+		for (int k = 0; k < i; k++) {
+			D += mcmc_binom.c[i - 1][k] * sgn * pw / sqrt((double)(k + 1));
+			pw *= on;
+			sgn = -sgn;
+		}
+	}
+	new_logit = (float)log(on / (1.0 - on));
+	log_ratio = log(o / D);
+}
+
+__global__ void __launch_bounds__(DS_BLOCK)
+mcmc_source_kernel(const McmcRelocate p)
+{
+	__shared__ uint32_t s_n[DS_BLOCK / 64], s_max[DS_BLOCK / 64];
+	const int i = (int)blockIdx.x * DS_BLOCK + (int)threadIdx.x;
+	const uint32_t n = i < p.P ? p.cnt[i] + 1u : 0u;
+	const bool src = n > 1u;
+	if (src) {
+		float nl;
+		double lr;
+		mcmc_new_values(mcmc_opacity(p.param[2][i]), n, p.min_opacity, nl, lr);
+		p.param[2][i] = nl;
+		float* s = p.param[3] + 3 * (size_t)i;
+		// log(exp(s) * o / D) = s + log(o / D), summed in double and rounded once
+		for (int c = 0; c < 3; c++) s[c] = (float)((double)s[c] + lr);
+		if (p.m1[0]) {
+			for (int t = 0; t < 5; t++) {
+				float* a = p.m1[t] + (size_t)p.row_floats[t] * i;
+				float* b = p.m2[t] + (size_t)p.row_floats[t] * i;
+				for (int c = 0; c < p.row_floats[t]; c++) {
+					a[c] = 0.f;
+					b[c] = 0.f;
+				}
+			}
+		}
+	}
+	const unsigned long long m = wave_ballot(src);
+	const uint32_t mx = wave_max_u32(src ? n : 0u);
+	if (lane_id() == 0) {
+		s_n[wave_id()] = (uint32_t)__popcll(m);
+		s_max[wave_id()] = mx;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint32_t a = 0, b = 0;
+		for (int k = 0; k < DS_BLOCK / 64; k++) {
+			a += s_n[k];
+			b = max(b, s_max[k]);
+		}
+		p.blk_nsrc[blockIdx.x] = a;
+		p.blk_maxn[blockIdx.x] = b;
+	}
+}
+
+__global__ void __launch_bounds__(256)
+mcmc_move_kernel(const McmcRelocate p, const int* __restrict__ counts)
+{
+	const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+	const long long per_row = p.items_before[6];
+	const long long k = item / per_row;
+	if (k >= (long long)counts[1]) return;
+	const long long e = item - k * per_row;
+	const size_t src = p.src_of[k];
+	const size_t dst = p.n_add > 0 ? (size_t)p.P + (size_t)k : (size_t)p.dest_of[k];
+	if (e >= p.items_before[5]) {
+		const int a = (int)(e - p.items_before[5]);
+		if (a == 3) {
+			if (p.exist) p.exist[dst] = p.exist[src];
+		} else if (p.stats[a]) {
+			p.stats[a][dst] = 0.f;
+		}
+		return;
+	}
+	int ti = 0;
+#pragma unroll
+	for (int j = 1; j < 5; j++) ti += e >= p.items_before[j];
+	const int u = (int)(e - p.items_before[ti]);
+	const int rf = p.row_floats[ti];
+	if ((rf & 3) == 0) {   // rows of whole float4s: features, rotation
+		const int units = rf / 4;
+		const size_t so = src * units + u, dn = dst * units + u;
+		reinterpret_cast<float4*>(p.param[ti])[dn] = reinterpret_cast<const float4*>(p.param[ti])[so];
+		if (p.m1[ti]) {
+			const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+			reinterpret_cast<float4*>(p.m1[ti])[dn] = zero;
+			reinterpret_cast<float4*>(p.m2[ti])[dn] = zero;
+		}
+		return;
+	}
+	const size_t so = src * rf + u, dn = dst * rf + u;
+	p.param[ti][dn] = p.param[ti][so];
+	if (p.m1[ti]) {
+		p.m1[ti][dn] = 0.f;
+		p.m2[ti][dn] = 0.f;
+	}
+}
+
+__global__ void __launch_bounds__(256)
+mcmc_finish_kernel(const McmcRelocate p, int nblocks, int* __restrict__ counts)
+{
+	__shared__ uint32_t s_n[4], s_max[4];
+	uint32_t a = 0, b = 0;
+	for (int i = (int)threadIdx.x; i < nblocks; i += 256) {
+		a += p.blk_nsrc[i];
+		b = max(b, p.blk_maxn[i]);
+	}
+	a = wave_sum_u32(a);
+	b = wave_max_u32(b);
+	if (lane_id() == 0) {
+		s_n[wave_id()] = a;
+		s_max[wave_id()] = b;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		counts[2] = (int)(s_n[0] + s_n[1] + s_n[2] + s_n[3]);
+		counts[3] = (int)max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+	}
+}
+
+// The Langevin position noise (include/gsr.h: gsr_mcmc_add_noise).  One thread per Gaussian, 56 bytes read and 12 written; the
+// fourteen loads are independent and stand in front of the first use.
+__global__ void __launch_bounds__(256)
+mcmc_noise_kernel(int P, float* __restrict__ xyz, const float* __restrict__ opacity, const float* __restrict__ scaling,
+                  const float* __restrict__ rotation, const float* __restrict__ z, float noise_scale)
+{
+	const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+	if (i >= P) return;
+	const size_t i3 = 3 * (size_t)i;
+	const float px = xyz[i3], py = xyz[i3 + 1], pz = xyz[i3 + 2];
+	const float zx = z[i3], zy = z[i3 + 1], zz = z[i3 + 2];
+	const float lo = opacity[i];
+	float c3[6];
+	compute_cov3D(scaling, rotation, (size_t)i, 1.0f, GSR_RAW_SCALING | GSR_RAW_ROTATION, c3);
+	const float o = mcmc_opacity(lo);
+	// expf overflows to +inf for an opaque Gaussian: the quotient is then exactly 0
+	const float g = 1.0f / (1.0f + expf(100.0f * (o - 0.005f)));
+	const float f = g * noise_scale;
+	const float vx = zx * f, vy = zy * f, vz = zz * f;
+	xyz[i3] = px + (c3[0] * vx + c3[1] * vy + c3[2] * vz);
+	xyz[i3 + 1] = py + (c3[1] * vx + c3[3] * vy + c3[4] * vz);
+	xyz[i3 + 2] = pz + (c3[2] * vx + c3[4] * vy + c3[5] * vz);
+}
+
+static inline int mcmc_move_units(int row_floats) { return (row_floats & 3) == 0 ? row_floats / 4 : row_floats; }
+
 }  // namespace gsr
 
 using namespace gsr;
@@ -386,6 +733,93 @@ int gsr_densify_gather(const gsr_densify_gather_args* a, const char* scratch, vo
 	}
 
 	GSR_LAUNCH(densify_gather_kernel, (int)blocks, 256, (hipStream_t)stream_, p);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+size_t gsr_mcmc_scratch_bytes(int P, int n_draws)
+{
+	if (P < 0) P = 0;
+	if (n_draws < 0) n_draws = 0;
+	const size_t nb = (size_t)densify_blocks(P);
+	// w, cnt, dest_of [P], C [P] (64-bit), src_of [n_draws], four per-block arrays (one of them 64-bit)
+	return 3 * align_up((size_t)P * sizeof(uint32_t), 128) + align_up((size_t)P * sizeof(unsigned long long), 128) +
+	       align_up((size_t)n_draws * sizeof(uint32_t), 128) + align_up(nb * sizeof(unsigned long long), 128) +
+	       3 * align_up(nb * sizeof(uint32_t), 128) + 256;
+}
+
+int gsr_mcmc_relocate(const gsr_mcmc_relocate_args* a, char* scratch, int* counts, void* stream_)
+{
+	if (!a || !counts || a->P < 0 || a->n_add < 0 || a->n_draws < 0 || a->n_add > a->n_draws) return GSR_ERR_INVALID_ARG;
+	if (!(a->min_opacity > 0.f && a->min_opacity < 1.f)) return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	if (a->P == 0) {
+		GSR_HIP(hipMemsetAsync(counts, 0, 8 * sizeof(int), stream));
+		return GSR_OK;
+	}
+	if (!scratch || (a->n_draws > 0 && !a->draws)) return GSR_ERR_INVALID_ARG;
+	static const int row_floats[5] = {3, 0, 1, 3, 4};
+	McmcRelocate p;
+	p.P = a->P; p.n_add = a->n_add; p.n_draws = a->n_draws;
+	p.min_opacity = a->min_opacity;
+	int n_moments = 0;
+	long long items = 0;
+	for (int i = 0; i < 5; i++) {
+		p.row_floats[i] = i == 1 ? a->features_row_floats : row_floats[i];
+		if (p.row_floats[i] <= 0) return GSR_ERR_INVALID_ARG;
+		p.param[i] = a->param[i]; p.m1[i] = a->exp_avg[i]; p.m2[i] = a->exp_avg_sq[i];
+		if (!p.param[i]) return GSR_ERR_INVALID_ARG;
+		n_moments += (p.m1[i] != nullptr) + (p.m2[i] != nullptr);
+		if ((p.row_floats[i] & 3) == 0) {   // float4 rows need 16-byte aligned bases
+			const uintptr_t m = reinterpret_cast<uintptr_t>(p.param[i]) | reinterpret_cast<uintptr_t>(p.m1[i]) | reinterpret_cast<uintptr_t>(p.m2[i]);
+			if (m & 15) return GSR_ERR_UNSUPPORTED;
+		}
+		p.items_before[i] = items;
+		items += mcmc_move_units(p.row_floats[i]);
+	}
+	if (n_moments != 0 && n_moments != 10) return GSR_ERR_INVALID_ARG;   // all ten moments or none
+	p.items_before[5] = items;
+	items += 4;   // the three statistics and exist_since_iter
+	p.items_before[6] = items;
+	p.draws = a->draws;
+	p.exist = a->exist_since_iter;
+	for (int k = 0; k < 3; k++) p.stats[k] = a->stats[k];
+	p.out_weights = a->out_weights;
+	const int nb = densify_blocks(a->P);
+	Carver c(scratch);
+	p.w = c.take<uint32_t>((size_t)a->P);
+	p.cnt = c.take<uint32_t>((size_t)a->P);
+	p.dest_of = c.take<uint32_t>((size_t)a->P);
+	p.C = c.take<unsigned long long>((size_t)a->P);
+	p.src_of = c.take<uint32_t>((size_t)a->n_draws);
+	p.blk_w = c.take<unsigned long long>((size_t)nb);
+	p.blk_dead = c.take<uint32_t>((size_t)nb);
+	p.blk_nsrc = c.take<uint32_t>((size_t)nb);
+	p.blk_maxn = c.take<uint32_t>((size_t)nb);
+	// the most destinations there can be: every draw, and when relocating no more than the rows
+	const int max_dest = a->n_add > 0 ? a->n_add : (a->n_draws < a->P ? a->n_draws : a->P);
+	const long long move_blocks = ((long long)max_dest * items + 255) / 256;
+	if (move_blocks > 0x7FFFFFFFll) return GSR_ERR_UNSUPPORTED;
+	GSR_HIP(hipMemsetAsync(p.cnt, 0, (size_t)a->P * sizeof(uint32_t), stream));
+	GSR_LAUNCH(mcmc_weight_kernel, nb, DS_BLOCK, stream, p);
+	GSR_LAUNCH(mcmc_spine_kernel, 1, 1024, stream, p, nb, counts);
+	GSR_LAUNCH(mcmc_prefix_kernel, nb, DS_BLOCK, stream, p);
+	if (max_dest > 0) GSR_LAUNCH(mcmc_sample_kernel, div_up(max_dest, 256), 256, stream, p, (const int*)counts);
+	GSR_LAUNCH(mcmc_source_kernel, nb, DS_BLOCK, stream, p);
+	if (max_dest > 0) GSR_LAUNCH(mcmc_move_kernel, (int)move_blocks, 256, stream, p, (const int*)counts);
+	GSR_LAUNCH(mcmc_finish_kernel, 1, 256, stream, p, nb, counts);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+int gsr_mcmc_add_noise(int P, float* xyz, const float* opacity, const float* scaling, const float* rotation, const float* z,
+                       float noise_scale, void* stream_)
+{
+	if (P < 0) return GSR_ERR_INVALID_ARG;
+	if (P == 0) return GSR_OK;
+	if (!xyz || !opacity || !scaling || !rotation || !z) return GSR_ERR_INVALID_ARG;
+	if (reinterpret_cast<uintptr_t>(rotation) & 15) return GSR_ERR_UNSUPPORTED;   // read as float4 rows
+	GSR_LAUNCH(mcmc_noise_kernel, div_up(P, 256), 256, (hipStream_t)stream_, P, xyz, opacity, scaling, rotation, z, noise_scale);
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

@@ -661,6 +661,84 @@ class GaussianModel:
         pruned = (P - n_split - n_keep) + (n_clone_sel - n_clone) + 2 * (n_split - n_child)
         return dict(cloned=n_clone_sel, split=n_split, pruned=pruned, points=n_new, children_kept=2 * n_child)
 
+    # ------------------------------------------------------------------ fixed-budget maps: 3DGS-MCMC (include/gsr.h: gsr_mcmc_*)
+    # The other half of the method whose L1 terms are TrainStep.opacity_reg_ / scale_reg_: dead Gaussians are re-spawned on live
+    # ones, the model grows by 5 % per event to a cap and no further, the positions take a covariance-shaped noise step.  A
+    # relocation works in place: no leaf is replaced, no count is read, nothing is rebuilt.
+    def _mcmc_call(self, P, n_add, draws, min_opacity):
+        lib = rp._lib()
+        dev = self.xyz_.device
+        a = capi.McmcRelocateArgs()
+        a.P, a.n_add, a.n_draws, a.min_opacity = P, n_add, int(draws.numel()), float(min_opacity)
+        a.features_row_floats = int(self._features.shape[1] * self._features.shape[2])
+        opt = self.optimizer_
+        leaves = self.params_raw()
+        if opt is not None and any(id(p) in opt.state for p in leaves):
+            for p in leaves:   # (a group that has not stepped yet: zero moments, as its first step would create them)
+                if id(p) not in opt.state:
+                    opt.state[id(p)] = dict(exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p), step=0)
+        for i, p in enumerate(leaves):
+            assert p.is_contiguous()
+            a.param[i] = p.data_ptr()
+            if opt is not None and id(p) in opt.state:
+                st = opt.state[id(p)]
+                a.exp_avg[i], a.exp_avg_sq[i] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+        a.draws = draws.data_ptr() if draws.numel() else None
+        if self.exist_since_iter_ is not None:
+            assert self.exist_since_iter_.is_contiguous() and self.exist_since_iter_.dtype == torch.int32
+            a.exist_since_iter = self.exist_since_iter_.data_ptr()
+        for k, t in enumerate((self.xyz_gradient_accum_, self.denom_, self.max_radii2D_)):
+            assert t.is_contiguous()
+            a.stats[k] = t.data_ptr()
+        nbytes = lib.gsr_mcmc_scratch_bytes(P, int(draws.numel()))
+        scratch = getattr(self, "_mcmc_scratch", None)
+        if scratch is None or scratch.numel() < nbytes or scratch.device != dev:
+            scratch = self._mcmc_scratch = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev)
+        counts = torch.empty(8, dtype=torch.int32, device=dev)
+        capi.check(lib, lib.gsr_mcmc_relocate(C.byref(a), scratch.data_ptr(), counts.data_ptr(), rp._stream_ptr(self.xyz_)),
+                   "gsr_mcmc_relocate")
+        return counts
+
+    def relocateDead(self, min_opacity=0.005, generator=None):
+        """3DGS-MCMC's relocate_gs: every dead Gaussian (sigmoid(opacity) <= min_opacity) becomes a copy of a live one drawn in
+        proportion to its opacity; the source and its copies share the opacity and scale that leave the render unchanged, and
+        their Adam moments are zeroed.  In place: no leaf is replaced and no count is read.  Returns the DEVICE counts tensor
+        (int32 [8]: dead rows, destinations written, sources drawn, the largest N)."""
+        _ = self.features_           # lazy SH Adam: every row up to date before rows of the tensor and its moments move
+        P = self.xyz_.shape[0]
+        with torch.no_grad():
+            draws = torch.rand(P, generator=generator, device=self.xyz_.device)
+            return self._mcmc_call(P, 0, draws, min_opacity)
+
+    def addNew(self, cap_max, generator=None, min_opacity=0.005):
+        """3DGS-MCMC's add_new_gs: the model grows to min(cap_max, floor(1.05 P)) rows (105 P / 100 in integers: both hosts agree),
+        the new rows drawn like relocateDead's but over ALL rows.  The count is formed on the host; nothing is read back.
+        Returns the number of rows added (0: nothing happened)."""
+        P = self.xyz_.shape[0]
+        n_add = min(int(cap_max), (105 * P) // 100) - P
+        if n_add <= 0:
+            return 0
+        dev = self.xyz_.device
+        with torch.no_grad():
+            shapes = dict(xyz_=(3,), features_=tuple(self.features_.shape[1:]), opacity_=(1,), scaling_=(3,), rotation_=(4,))
+            # (the rows' content comes from the kernel; _append_rows only makes the room and the optimizer state)
+            self._append_rows({n: torch.zeros((n_add,) + s, device=dev) for n, s in shapes.items()}, 0)
+            draws = torch.rand(n_add, generator=generator, device=dev)
+            self._mcmc_call(P, n_add, draws, min_opacity)
+        return n_add
+
+    def addPositionNoise(self, noise_scale, generator=None):
+        """3DGS-MCMC's Langevin noise: xyz += Sigma (z sigmoid(100 ((1 - o) - 0.995)) noise_scale), z ~ N(0, 1), in place."""
+        lib = rp._lib()
+        P = self.xyz_.shape[0]
+        if P == 0:
+            return
+        with torch.no_grad():
+            z = torch.empty((P, 3), device=self.xyz_.device).normal_(generator=generator)
+            capi.check(lib, lib.gsr_mcmc_add_noise(P, self.xyz_.data_ptr(), self.opacity_.data_ptr(), self.scaling_.data_ptr(),
+                                                   self.rotation_.data_ptr(), z.data_ptr(), float(noise_scale),
+                                                   rp._stream_ptr(self.xyz_)), "gsr_mcmc_add_noise")
+
     def resetOpacity(self, clamp_to=None):
         """src/gaussian_model.cpp:556-565 exactly as shipped: opacities_new = inverse_sigmoid(min(sigmoid(o), ones_like(sigmoid(o)
         * 0.01))) -- the 0.01 sits INSIDE ones_like, so the clamp is against 1 and never binds: the values survive (up to the

@@ -98,6 +98,20 @@ public:
 	DensifyResult densifyAndPrune(float max_grad, float min_opacity, float extent, int max_screen_size,
 	                              c10::optional<at::Generator> generator = c10::nullopt);
 
+	// Fixed-budget maps: 3DGS-MCMC (include/gsr.h: gsr_mcmc_relocate / gsr_mcmc_add_noise), the other half of the method whose L1
+	// terms are TrainStep::opacity_reg_ / scale_reg_.
+	// relocateDead: every dead Gaussian (sigmoid(opacity) <= min_opacity) becomes a copy of a live one drawn in proportion to its
+	// opacity; the source and its copies share the opacity and scale that leave the render unchanged, their Adam moments are zeroed.
+	// IN PLACE: no leaf is replaced and no count is read.  Returns the DEVICE counts (int32 [8]: dead rows, destinations written,
+	// sources drawn, the largest N).
+	torch::Tensor relocateDead(float min_opacity = 0.005f, c10::optional<at::Generator> generator = c10::nullopt);
+	// addNew: the model grows to min(cap_max, floor(1.05 P)) rows (105 P / 100 in integers), the new rows drawn like relocateDead's
+	// but over ALL rows; appended through the arena as increasePcd's rows are.  The count is formed on the host, nothing is read
+	// back.  Returns the number of rows added (0: nothing happened).
+	int64_t addNew(int64_t cap_max, c10::optional<at::Generator> generator = c10::nullopt, float min_opacity = 0.005f);
+	// addPositionNoise: xyz += Sigma (z sigmoid(100 ((1 - o) - 0.995)) noise_scale), z ~ N(0, 1) from the generator, in place
+	void addPositionNoise(float noise_scale, c10::optional<at::Generator> generator = c10::nullopt);
+
 	// activations, src/gaussian_model.cpp:48-71
 	torch::Tensor getXYZ() { return xyz_; }
 	torch::Tensor getScalingActivation() { return torch::exp(scaling_); }
@@ -202,6 +216,8 @@ public:
 	void releaseArena();
 private:
 	torch::Tensor densify_scratch_;
+	torch::Tensor mcmc_scratch_;
+	torch::Tensor mcmcCall(int64_t P, int64_t n_add, const torch::Tensor& draws, float min_opacity);
 };
 
 // GaussianMapper::trainForOneIteration (src/gaussian_mapper.cpp:614-774) without the SLAM keyframe
@@ -284,6 +300,16 @@ public:
 	bool read_reg_losses_ = true;
 	torch::Tensor lastRegLosses() const { return last_reg_losses_; }
 	torch::Tensor last_reg_losses_;
+	// Fixed-budget maps (3DGS-MCMC): with mcmc_ on and densify_ set, the iterations that rebuild today run relocateDead + addNew
+	// instead of densifyAndPrune -- the count grows by 5 % per event to exactly mcmc_cap_max_ and then stays, no tensor is rebuilt
+	// on a relocation, that iteration's update is skipped as a rebuild's is, and the opacity is never reset -- and every step adds
+	// position noise of scale mcmc_noise_lr_ * the current xyz learning rate behind the optimizer update (finishEnd()).  Not with
+	// a process group: throws.  Off = nothing changes.
+	bool mcmc_ = false;
+	int64_t mcmc_cap_max_ = 0;
+	double mcmc_noise_lr_ = 5e5;   // (upstream's noise_lr)
+	float mcmc_min_opacity_ = 0.005f;
+	torch::Tensor last_mcmc_counts_;   // the device counts of the last relocateDead
 	bool optimize_exposure_ = false;
 	float exposure_lr_init_ = 0.01f, exposure_lr_final_ = 0.001f;
 	int exposure_lr_max_steps_ = -1;

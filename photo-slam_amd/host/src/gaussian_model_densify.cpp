@@ -463,3 +463,79 @@ GaussianModel::DensifyResult GaussianModel::densifyAndPrune(float max_grad, floa
 	res.points = c[5];
 	return res;
 }
+
+// ---- fixed-budget maps: 3DGS-MCMC (csrc/densify.hip, include/gsr.h: gsr_mcmc_relocate / gsr_mcmc_add_noise) -------------------
+
+torch::Tensor GaussianModel::mcmcCall(int64_t P, int64_t n_add, const torch::Tensor& draws, float min_opacity)
+{
+	gsr_mcmc_relocate_args a{};
+	a.P = static_cast<int>(P);
+	a.n_add = static_cast<int>(n_add);
+	a.n_draws = static_cast<int>(draws.numel());
+	a.features_row_floats = static_cast<int>(features_.size(1) * features_.size(2));
+	a.min_opacity = min_opacity;
+	const bool have_state = groups_.size() == 5;
+	for (int i = 0; i < 5; i++) {
+		auto& p = paramByIndex(i);
+		TORCH_CHECK(p.is_contiguous(), "mcmc: the parameter tensors must be contiguous");
+		a.param[i] = p.data_ptr<float>();
+		if (have_state) {
+			a.exp_avg[i] = groups_[i].exp_avg.data_ptr<float>();
+			a.exp_avg_sq[i] = groups_[i].exp_avg_sq.data_ptr<float>();
+		}
+	}
+	a.draws = draws.numel() ? draws.data_ptr<float>() : nullptr;
+	if (exist_since_iter_.defined()) {
+		TORCH_CHECK(exist_since_iter_.is_contiguous() && exist_since_iter_.scalar_type() == torch::kInt32, "mcmc: exist_since_iter_ must be contiguous int32");
+		a.exist_since_iter = exist_since_iter_.data_ptr<int>();
+	}
+	torch::Tensor* stats[3] = {&xyz_gradient_accum_, &denom_, &max_radii2D_};
+	for (int k = 0; k < 3; k++)
+		if (stats[k]->defined()) {
+			TORCH_CHECK(stats[k]->is_contiguous(), "mcmc: the statistics must be contiguous");
+			a.stats[k] = stats[k]->data_ptr<float>();
+		}
+	const auto bytes = static_cast<int64_t>(gsr_mcmc_scratch_bytes(a.P, a.n_draws));
+	if (!mcmc_scratch_.defined() || mcmc_scratch_.numel() < bytes || mcmc_scratch_.device() != xyz_.device())
+		mcmc_scratch_ = torch::empty({bytes + bytes / 4 + 256}, xyz_.options().dtype(torch::kUInt8).requires_grad(false));
+	auto counts = torch::empty({8}, xyz_.options().dtype(torch::kInt32).requires_grad(false));
+	check_gsr(gsr_mcmc_relocate(&a, reinterpret_cast<char*>(mcmc_scratch_.data_ptr<uint8_t>()), counts.data_ptr<int>(), hostStream(xyz_)),
+	          "gsr_mcmc_relocate");
+	return counts;
+}
+
+torch::Tensor GaussianModel::relocateDead(float min_opacity, c10::optional<at::Generator> generator)
+{
+	torch::NoGradGuard ng;
+	syncFeatures();   // rows of features_ and of its moments move: none may be behind (lazy SH Adam)
+	const int64_t P = xyz_.size(0);
+	auto draws = torch::empty({P}, xyz_.options().requires_grad(false)).uniform_(0.0, 1.0, generator);
+	return mcmcCall(P, 0, draws, min_opacity);
+}
+
+int64_t GaussianModel::addNew(int64_t cap_max, c10::optional<at::Generator> generator, float min_opacity)
+{
+	torch::NoGradGuard ng;
+	const int64_t P = xyz_.size(0);
+	const int64_t n_add = std::min<int64_t>(cap_max, (105 * P) / 100) - P;
+	if (n_add <= 0) return 0;
+	syncFeatures();
+	const auto o = xyz_.options().requires_grad(false);
+	// (the rows' content comes from the kernel; appendRows only makes the room and the optimizer state)
+	appendRows({torch::zeros({n_add, 3}, o), torch::zeros({n_add, features_.size(1), features_.size(2)}, o), torch::zeros({n_add, 1}, o),
+	            torch::zeros({n_add, 3}, o), torch::zeros({n_add, 4}, o)}, 0);
+	auto draws = torch::empty({n_add}, o).uniform_(0.0, 1.0, generator);
+	mcmcCall(P, n_add, draws, min_opacity);
+	return n_add;
+}
+
+void GaussianModel::addPositionNoise(float noise_scale, c10::optional<at::Generator> generator)
+{
+	torch::NoGradGuard ng;
+	const int64_t P = xyz_.size(0);
+	if (P == 0) return;
+	auto z = torch::empty({P, 3}, xyz_.options().requires_grad(false)).normal_(0.0, 1.0, generator);
+	check_gsr(gsr_mcmc_add_noise(static_cast<int>(P), xyz_.data_ptr<float>(), opacity_.data_ptr<float>(), scaling_.data_ptr<float>(),
+	                             rotation_.data_ptr<float>(), z.data_ptr<float>(), noise_scale, hostStream(xyz_)),
+	          "gsr_mcmc_add_noise");
+}

@@ -386,6 +386,10 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "scale_reg") t->scale_reg_ = v;
 		else if (k == "isotropic_reg") t->isotropic_reg_ = v;
 		else if (k == "read_reg_losses") t->read_reg_losses_ = v != 0.0;
+		else if (k == "mcmc") t->mcmc_ = v != 0.0;
+		else if (k == "mcmc_cap_max") t->mcmc_cap_max_ = (int64_t)v;
+		else if (k == "mcmc_noise_lr") t->mcmc_noise_lr_ = v;
+		else if (k == "mcmc_min_opacity") t->mcmc_min_opacity_ = (float)v;
 		else if (k == "depth_loss_weight") t->depth_loss_weight_ = static_cast<float>(v);
 		else if (k == "depth_min") t->depth_min_ = static_cast<float>(v);
 		else if (k == "depth_max") t->depth_max_ = static_cast<float>(v);
@@ -423,6 +427,27 @@ std::vector<int64_t> trainer_densify_and_prune(int64_t h, double max_grad, doubl
 	auto r = g->densifyAndPrune((float)max_grad, (float)min_opacity, (float)extent, (int)max_screen_size,
 	                            make_generator(g->xyz_.device(), seed));
 	return {r.cloned, r.split, r.pruned, r.points};
+}
+// GaussianModel::relocateDead / addNew / addPositionNoise with a generator seeded as given; TrainStep::last_mcmc_counts_
+torch::Tensor trainer_relocate_dead(int64_t h, double min_opacity, int64_t seed)
+{
+	auto g = get(h)->gaussians_;
+	return g->relocateDead((float)min_opacity, make_generator(g->xyz_.device(), seed));
+}
+int64_t trainer_add_new(int64_t h, int64_t cap_max, int64_t seed)
+{
+	auto g = get(h)->gaussians_;
+	return g->addNew(cap_max, make_generator(g->xyz_.device(), seed));
+}
+void trainer_add_position_noise(int64_t h, double noise_scale, int64_t seed)
+{
+	auto g = get(h)->gaussians_;
+	g->addPositionNoise((float)noise_scale, make_generator(g->xyz_.device(), seed));
+}
+torch::Tensor trainer_last_mcmc_counts(int64_t h)
+{
+	auto t = get(h);
+	return t->last_mcmc_counts_.defined() ? t->last_mcmc_counts_ : torch::empty({0}, t->gaussians_->xyz_.options().dtype(torch::kInt32).requires_grad(false));
 }
 torch::Tensor trainer_reorder_along_z_curve(int64_t h) { return get(h)->gaussians_->reorderAlongZCurve(); }
 std::vector<int64_t> trainer_last_densify(int64_t h)
@@ -660,6 +685,10 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("trainer_set_options", &trainer_set_options);
 	m.def("trainer_densify_and_prune", &trainer_densify_and_prune);
 	m.def("trainer_reorder_along_z_curve", &trainer_reorder_along_z_curve);
+	m.def("trainer_relocate_dead", &trainer_relocate_dead);
+	m.def("trainer_add_new", &trainer_add_new);
+	m.def("trainer_add_position_noise", &trainer_add_position_noise);
+	m.def("trainer_last_mcmc_counts", &trainer_last_mcmc_counts);
 	m.def("trainer_last_densify", &trainer_last_densify);
 	m.def("trainer_save_ply", &trainer_save_ply);
 	m.def("trainer_create_from_ply", &trainer_create_from_ply);

@@ -392,6 +392,8 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	const bool reg = opacity_reg_ != 0.0 || scale_reg_ != 0.0 || isotropic_reg_ != 0.0;
 	if (reg && (process_group_ || factored_exchange_))
 		throw std::runtime_error("TrainStep: the opacity / scale / isotropy regularisers are not supported with a process group");
+	if (mcmc_ && (process_group_ || factored_exchange_))
+		throw std::runtime_error("TrainStep: mcmc_ is not supported with a process group");
 	last_reg_losses_ = torch::Tensor();
 	auto& g = gaussians_;
 	if (optimize_exposure_ && !kf->exposure_.defined())   // the identity at first use
@@ -520,7 +522,7 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	GeomAdamStep& geom_adam = ext.geom_adam_;
 	// (an iteration that resets the opacity replaces that leaf AFTER backward: the reference's optimizer step then skips it -- no
 	// gradient -- while a step fused into backward would already have been taken: src/gaussian_mapper.cpp:732-735)
-	const bool resets = densify_ && iteration_ < o.densify_until_iter_ && o.opacity_reset_interval_ &&
+	const bool resets = densify_ && !mcmc_ && iteration_ < o.densify_until_iter_ && o.opacity_reset_interval_ &&
 	                    iteration_ % o.opacity_reset_interval_ == 0;
 	if (fused_geom_adam_ && !factored_exchange_ && sh_adam.exp_avg.defined() && g->groups_.size() == 5 && !pipe.compute_cov3D_ && !resets) {
 		// xyz, opacity, scaling, rotation = groups 0, 2, 3, 4 (trainingSetup); their steps happen inside backward, and
@@ -744,6 +746,8 @@ void TrainStep::finishEnd()
 {
 	finishFeaturesFromViews();   // (a driver that forgot the slice: the lazy state stays consistent)
 	if (iteration_ < gaussians_->opt_.iterations_) gaussians_->zeroGrad();
+	if (mcmc_ && iteration_ < gaussians_->opt_.iterations_ && !gaussians_->groups_.empty())
+		gaussians_->addPositionNoise(static_cast<float>(mcmc_noise_lr_ * gaussians_->groups_[0].lr * gaussians_->lr_scale_), generator_);
 	finishExposure();   // the keyframe's exposure takes its own step, on densifying iterations too (it is not rebuilt)
 }
 
@@ -764,10 +768,15 @@ void TrainStep::finishBegin()
 		if (densifyDue()) {
 			const int size_threshold = iteration_ > prune_big_point_after_iter_ ? 20 : 0;   // src/gaussian_mapper.cpp:723
 			g->zeroGrad();   // shapes change; this step's update is skipped
-			last_densify_ = g->densifyAndPrune(o.densify_grad_threshold_, densify_min_opacity_, cameras_extent_, size_threshold,
-			                                   generator_);
+			if (mcmc_) {
+				last_mcmc_counts_ = g->relocateDead(mcmc_min_opacity_, generator_);
+				g->addNew(mcmc_cap_max_, generator_, mcmc_min_opacity_);
+			} else {
+				last_densify_ = g->densifyAndPrune(o.densify_grad_threshold_, densify_min_opacity_, cameras_extent_, size_threshold,
+				                                   generator_);
+			}
 		}
-		if (o.opacity_reset_interval_ && iteration_ % o.opacity_reset_interval_ == 0) g->resetOpacity();
+		if (!mcmc_ && o.opacity_reset_interval_ && iteration_ % o.opacity_reset_interval_ == 0) g->resetOpacity();
 	}
 	if (iteration_ < g->opt_.iterations_) g->beginOptimizerStep();
 }

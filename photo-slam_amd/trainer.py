@@ -266,6 +266,15 @@ class TrainStep:
         self.scale_reg_ = 0.0
         self.isotropic_reg_ = 0.0
         self.last_reg_losses = None
+        # Fixed-budget maps (3DGS-MCMC, the other half of opacity_reg_ / scale_reg_): with mcmc_ on and densify set, the iterations
+        # that rebuild today run relocateDead + addNew instead of densifyAndPrune -- the count grows by 5 % per event to exactly
+        # mcmc_cap_max_ and then stays, no tensor is rebuilt on a relocation and the opacity is never reset -- and every step adds
+        # position noise of scale mcmc_noise_lr_ * the current xyz learning rate after the optimizer update.
+        self.mcmc_ = False
+        self.mcmc_cap_max_ = 0
+        self.mcmc_noise_lr_ = 5e5       # (upstream's noise_lr)
+        self.mcmc_min_opacity_ = 0.005
+        self.last_mcmc_counts_ = None   # the device counts of the last relocateDead
         self.optimize_exposure_ = False
         self.exposure_lr_init_ = 0.01
         self.exposure_lr_final_ = 0.001
@@ -465,6 +474,8 @@ class TrainStep:
         if exposure is not None and self.world_size_ > 1:
             raise RuntimeError("TrainStep: exposure compensation is not supported with a process group")
         g, opt = self.gaussians_, self.opt_
+        if self.mcmc_ and self.world_size_ > 1:
+            raise RuntimeError("TrainStep: mcmc_ is not supported with a process group")
         geom_reg = None
         if self.opacity_reg_ or self.scale_reg_ or self.isotropic_reg_:
             if self.world_size_ > 1:
@@ -493,7 +504,7 @@ class TrainStep:
             sh_adam = g.optimizer_.begin_fused_step(FEATURES_GROUP, self.lazy_sh_adam_window_)
             # (an iteration that resets the opacity replaces that leaf AFTER backward: the reference's optimizer step then
             # skips it -- no gradient -- while a step fused into backward would already have been taken: src/gaussian_mapper.cpp:732-735)
-            resets = bool(self.densify_ and it < opt.densify_until_iter_ and opt.opacity_reset_interval_ and
+            resets = bool(self.densify_ and not self.mcmc_ and it < opt.densify_until_iter_ and opt.opacity_reset_interval_ and
                           it % opt.opacity_reset_interval_ == 0)
             if self.fused_geom_adam_ and len(g.optimizer_.param_groups) == 5 and not self.pipe_.compute_cov3D_ and not resets:
                 # xyz, opacity, scaling, rotation = groups 0, 2, 3, 4 (GaussianModel.trainingSetup)
@@ -569,10 +580,14 @@ class TrainStep:
                             dist.all_reduce(g.max_radii2D_, op=dist.ReduceOp.MAX)
                         size_threshold = 20 if it > self.prune_big_point_after_iter_ else 0   # :723
                         g.optimizer_.zero_grad(set_to_none=True)   # shapes change; this step's update is skipped
-                        self.last_densify_ = g.densifyAndPrune(opt.densify_grad_threshold_, self.densify_min_opacity_,
-                                                               self.cameras_extent_, size_threshold,
-                                                               generator=self.generator_)
-                    if opt.opacity_reset_interval_ and it % opt.opacity_reset_interval_ == 0:      # :732-735
+                        if self.mcmc_:
+                            self.last_mcmc_counts_ = g.relocateDead(self.mcmc_min_opacity_, generator=self.generator_)
+                            g.addNew(self.mcmc_cap_max_, generator=self.generator_, min_opacity=self.mcmc_min_opacity_)
+                        else:
+                            self.last_densify_ = g.densifyAndPrune(opt.densify_grad_threshold_, self.densify_min_opacity_,
+                                                                   self.cameras_extent_, size_threshold,
+                                                                   generator=self.generator_)
+                    if not self.mcmc_ and opt.opacity_reset_interval_ and it % opt.opacity_reset_interval_ == 0:      # :732-735
                         g.resetOpacity()
             if it < opt.iterations_:                                       # :769-772
                 if reduction is None:
@@ -610,6 +625,9 @@ class TrainStep:
                             reduction.wait(i)
                             g.optimizer_.step_group(i)
                 g.optimizer_.zero_grad(set_to_none=True)
+                if self.mcmc_:
+                    g.addPositionNoise(self.mcmc_noise_lr_ * g.optimizer_.param_groups[0]["lr"] * g.optimizer_.lr_scale,
+                                       generator=self.generator_)
             elif reduction is not None:
                 reduction.wait_all()
             # the keyframe's exposure: its own Adam step, on densifying iterations too (it is not rebuilt)
