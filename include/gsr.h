@@ -399,6 +399,18 @@ typedef struct gsr_backward_args {
 	/* Extension (NULL = the reference contract): regularisers on the Gaussians this view sees, added to the opacity and scale
 	 * gradients inside the pass -- see gsr_geom_reg. */
 	const gsr_geom_reg* geom_reg;
+	/* Extension (NULL = off: the kernels and arguments of a call without it): absolute screen-space gradients, AbsGS's
+	 * "homodirectional" densification statistic (gsplat: absgrad).  [P,2]; every row is written, zeros for culled Gaussians.  With
+	 * g_p the contribution of pixel p alone to dL_dmean2D[g] (dL_dmean2D[g] = sum_p g_p),
+	 *   dL_dmean2D_abs[g] = (sum_p |g_p.x|, sum_p |g_p.y|)
+	 * in the units of dL_dmean2D (the W/2 and H/2 factors included), so that abs >= |dL_dmean2D| componentwise, with equality for a
+	 * Gaussian one pixel blends.  dL_ddepth / dL_dalpha count towards it: they are part of dL/dalpha.  The sums are formed per pixel
+	 * inside the backward blend (its ABS instantiations) -- they do not factor through the per-Gaussian reduction that dL_dmean2D
+	 * takes -- and travel in two spare words of the per-instance slots.  dL_dmean2D itself is unchanged and may still be NULL.
+	 * Together with stat_*: stat_grad_accum += the norm of THIS pair instead of |dL_dmean2D.xy|; stat_denom and stat_max_radii as
+	 * before.  Works with geom_adam, sh_adam, geom_reg, the pose gradients, GSR_ANTIALIAS and both GSR_BINNING_* arrangements; not
+	 * together with dL_dcolor_view / packed_view (the multi-GPU exchange): GSR_ERR_UNSUPPORTED. */
+	float* dL_dmean2D_abs;
 } gsr_backward_args;
 
 /* Rasterizer::backward, cuda_rasterizer/rasterizer_impl.cu:340-433.
@@ -580,6 +592,10 @@ int gsr_adam_step_multi(int count, const gsr_adam_multi_tensor* tensors, double 
  * dL_dmean2D is the [P,3] viewspace gradient; accum/denom are [P] ([P,1]) floats, max_radii2D [P] floats. */
 int gsr_densify_stats(int P, const float* dL_dmean2D, const int* radii, float* xyz_gradient_accum, float* denom,
                       float* max_radii2D, void* stream);
+/* The same from the absolute pair (gsr_backward_args.dL_dmean2D_abs, [P,2]): xyz_gradient_accum += |dL_dmean2D_abs| -- for a caller
+ * that keeps the statistics pass apart from the backward pass.  The bits of the fused form (stat_* next to dL_dmean2D_abs). */
+int gsr_densify_stats_abs(int P, const float* dL_dmean2D_abs, const int* radii, float* xyz_gradient_accum, float* denom,
+                          float* max_radii2D, void* stream);
 
 /* ---- densification / pruning as stream compaction ----
  * GaussianModel::densifyAndPrune = densifyAndClone + densifyAndSplit (N = 2) + the final prunePoints

@@ -121,7 +121,8 @@ class BackwardArgs(C.Structure):
                 ("packed_view", C.c_void_p), ("packed_capacity_rows", C.c_int),
                 ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p),
                 ("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p),
-                ("pose_scratch", C.c_void_p), ("geom_reg", C.POINTER(GeomReg))]
+                ("pose_scratch", C.c_void_p), ("geom_reg", C.POINTER(GeomReg)),
+                ("dL_dmean2D_abs", C.c_void_p)]
 
 class DensifySelectArgs(C.Structure):
     _fields_ = [("P", C.c_int), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p), ("scaling", C.c_void_p),
@@ -156,7 +157,7 @@ EXPORTED_SYMBOLS = [
     "gsr_forward", "gsr_backward", "gsr_mark_visible", "gsr_knn_mean_dist2", "gsr_geometry_bytes", "gsr_binning_bytes",
     "gsr_image_bytes", "gsr_knn_scratch_bytes", "gsr_sh_grad_from_views", "gsr_sh_adam_from_views", "gsr_sh_adam_flush", "gsr_sh_adam_lazy_slice", "gsr_adam_step_multi", "gsr_strerror", "gsr_last_hip_error", "gsr_last_hip_error_string",
     "gsr_backend", "gsr_profile_enable", "gsr_profile_stage_count", "gsr_profile_stage_name", "gsr_profile_read",
-    "gsr_loss_scratch_bytes", "gsr_l1_ssim_loss", "gsr_adam_step", "gsr_densify_stats", "gsr_densify_scratch_bytes",
+    "gsr_loss_scratch_bytes", "gsr_l1_ssim_loss", "gsr_adam_step", "gsr_densify_stats", "gsr_densify_stats_abs", "gsr_densify_scratch_bytes",
     "gsr_densify_select", "gsr_densify_gather", "gsr_transform_points", "gsr_scale_transform_points", "gsr_reproject_depth_pinhole",
     "gsr_neighborhood_depth_pinhole", "gsr_packed_view_words", "gsr_pack_scratch_bytes", "gsr_pack_color_view", "gsr_pack_view_plan",
     "gsr_sh_grad_from_packed_views", "gsr_sh_adam_from_packed_views", "gsr_last_visible_count", "gsr_check_packed_views", "gsr_depth_resort_count",
@@ -242,6 +243,8 @@ def load(path=None):
     L.gsr_adam_step.argtypes = [vp, vp, vp, vp, C.c_longlong, f64, f64, f64, f64, i32, i32, i32, f64, vp]
     L.gsr_densify_stats.restype = i32
     L.gsr_densify_stats.argtypes = [i32, vp, vp, vp, vp, vp, vp]
+    L.gsr_densify_stats_abs.restype = i32
+    L.gsr_densify_stats_abs.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     L.gsr_densify_scratch_bytes.restype = sz
     L.gsr_densify_scratch_bytes.argtypes = [i32]
     L.gsr_densify_select.restype = i32

@@ -109,7 +109,7 @@ __device__ __forceinline__ bool rect_keep(const float4 q0, const float4 q1, floa
 __device__ __forceinline__ bool quad_keep(const float4 q0, const float4 q1, float x0, float y0) { return rect_keep(q0, q1, x0, y0, 7.0f); }
 
 // Gradient hand-off without global atomics.  Every (tile, Gaussian) instance owns one 48-byte slot
-//   [0..2] dL_dcolor  [3..4] sum w*dx, sum w*dy  [5..7] sum w*dx*dx, w*dx*dy, w*dy*dy  [8] sum w  [9..11] unused
+//   [0..2] dL_dcolor  [3..4] sum w*dx, sum w*dy  [5..7] sum w*dx*dx, w*dx*dy, w*dy*dy  [8] sum w  [9] dL/dz (DEPTH)  [10..11] the absolute mean2D sums (ABS), else unused
 // with w = dL_dalpha * G per contributing pixel: components 3..7 are stored WITHOUT their per-Gaussian
 // constants (-opacity*W/2, -opacity*H/2 and the conic for the mean2D pair, -opacity/2 for the conic terms):
 // preprocess_bwd (partials.h) applies them once per Gaussian instead of once per pixel pair

@@ -51,6 +51,15 @@
 // the tenth sum is accumulated in s_rec[i][2].z (zeroed at staging), reduced like the ninth -- row sums of 16 lanes, merged by four
 // more lanes of the same ds_add_f32 -- and written to slot word [9].
 //
+// ABS (gsr_backward_args.dL_dmean2D_abs): the absolute screen-space gradients of AbsGS.  The mean2D pair above is reduced as
+// sum(w dx), sum(w dy) and gets its conic per Gaussian; a sum of ABSOLUTE values does not factor that way, so it is formed here, per
+// pixel: two more products per visit, |w (2 A' dx + B' dy)| and |w (B' dx + 2 C' dy)| with w = dL_dG G and the prescaled conic of
+// s_rec (the positive constants -- opacity, ln 2 for the prescale, W/2 and H/2 -- factor out of the absolute value: preprocess_bwd),
+// the two pixels of a lane summed in the lane, reduced like the ninth and tenth -- row sums, delivered by eight more lanes of the
+// same ds_add_f32 -- and written to slot words [10], [11].  The colour-only form keeps the two sums in s_rec[i][2].w and .y: no
+// LDS.  ABS x DEPTH needs four values for the three spare words: that instantiation alone carries s_absy (+ 4 bytes per entry:
+// 11.9 / 23.8 KB, 13 / 6 workgroups per CU against 14 / 7).  An instantiation of its own: the kernels without it stay the same code.
+//
 #include "blend.h"
 #include "kernels.h"
 
@@ -71,7 +80,7 @@ struct BwdPixel {
 	uint32_t last;
 };
 
-template <int WAVES, bool DEPTH>
+template <int WAVES, bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(64 * WAVES)
 blend_bwd_kernel(const BlendBwdParams p)
 {
@@ -82,6 +91,7 @@ blend_bwd_kernel(const BlendBwdParams p)
 	__shared__ float4 s_rec[BWD_SEG][3];   // per entry of the segment: (x, y, A', B') (C', opacity, r, g) (b, z, sum dL/dz, -)
 	                                       // (DEPTH only: z and the tenth sum)
 	__shared__ float s_acc[9][BWD_SEG];
+	__shared__ float s_absy[ABS && DEPTH ? BWD_SEG : 1];   // ABS x DEPTH only: the one sum s_rec has no spare word for (file header)
 	__shared__ uint32_t s_slot[BWD_SEG];
 	__shared__ uint8_t s_flag[BWD_SEG];    // bit q: quad q of the tile blends the entry
 	__shared__ uint32_t s_wmax[QUADS_PER_TILE];
@@ -146,6 +156,11 @@ blend_bwd_kernel(const BlendBwdParams p)
 	const bool red_tenth = DEPTH && (l & 15) == 2;
 	float* const red_base = red_tenth ? &s_rec[0][2].z : &s_acc[0][0] + red_off;
 	const int red_stride = red_tenth ? 12 : 1;
+	// ABS: lanes 3, 19, 35, 51 add the four row sums of sum |g_p.x| to s_rec[entry][2].w, lanes 4, 20, 36, 52 those of sum |g_p.y| to
+	// s_rec[entry][2].y (with DEPTH, where z sits there: to s_absy[entry])
+	const bool red_ax = ABS && (l & 15) == 3, red_ay = ABS && (l & 15) == 4;
+	float* const red_abs_base = red_ax ? &s_rec[0][2].w : (red_ay ? (DEPTH ? &s_absy[0] : &s_rec[0][2].y) : red_base);
+	const int red_abs_stride = red_ax ? 12 : (red_ay ? (DEPTH ? 1 : 12) : red_stride);
 
 	const int seg_first = (int)((bmax + BWD_SEG - 1) / BWD_SEG) - 1, seg_last = 0;
 	// The segment's records are staged ONCE per tile, by all the workgroup's threads (thread i: list entry seg_lo + i), and only
@@ -196,8 +211,9 @@ blend_bwd_kernel(const BlendBwdParams p)
 		v2f c01, t, m56;
 		float c3, t7, wG;
 		float z9;   // DEPTH: alpha T dL/ddepth
+		float ax, ay;   // ABS: |w G (2 A' dx + B' dy)|, |w G (B' dx + 2 C' dy)|
 	};
-	auto terms = [](BwdPixel& s, const Hit& h, const float4 g1, float gb, float gz) -> Terms {
+	auto terms = [](BwdPixel& s, const Hit& h, const float4 g1, float gb, float gz, float a2, float bp) -> Terms {
 		const float rinv = __builtin_amdgcn_rcpf(1.f - h.alpha);
 		const float Tn = s.T * rinv;   // the transmittance in FRONT of this entry
 		// dL/dalpha = T_j (c_j . dpix) - B_{j+1} / (1 - alpha_j)   (the running scalar: file header; DEPTH: z_j dD is one more channel)
@@ -215,6 +231,10 @@ blend_bwd_kernel(const BlendBwdParams p)
 		r.c3 = dcol * s.dpb;
 		r.t7 = r.t[1] * h.dxy[1];                    // w dy dy
 		if constexpr (DEPTH) r.z9 = dcol * s.dD;
+		if constexpr (ABS) {   // a2 = 2 A', bp = B', g1.x = C': the pixel's own mean2D terms, before their signs can cancel
+			r.ax = fabsf(r.wG * (a2 * h.dxy[0] + bp * h.dxy[1]));
+			r.ay = fabsf(r.wG * (bp * h.dxy[0] + (g1.x + g1.x) * h.dxy[1]));
+		}
 		s.T = PAIRS ? mask_select_f32(h.ok, Tn, s.T) : (h.okl ? Tn : s.T);
 		s.B += dcol * cdp;   // (dcol is zero where the entry is not blended)
 		return r;
@@ -252,6 +272,11 @@ blend_bwd_kernel(const BlendBwdParams p)
 			s_slot[tid] = slot;
 			s_flag[tid] = (uint8_t)f;
 			if constexpr (DEPTH) s_rec[tid][2].z = 0.f;   // the tenth sum
+			if constexpr (ABS) {                          // the two absolute sums
+				s_rec[tid][2].w = 0.f;
+				if constexpr (DEPTH) s_absy[tid] = 0.f;
+				else s_rec[tid][2].y = 0.f;
+			}
 		}
 		__syncthreads();
 
@@ -281,6 +306,7 @@ blend_bwd_kernel(const BlendBwdParams p)
 					gb = rec_b[bit][2].x;
 				}
 				// only the flagged quads of the pair are tested (wave-uniform branches on the two flag bits)
+				const float a2 = ABS ? g0.z + g0.z : 0.f, bp = g0.w;
 				Hit ha, hb;
 				unsigned long long oka = 0ull, okb = 0ull;
 				if ((ma >> bit) & 1ull) {
@@ -299,7 +325,7 @@ blend_bwd_kernel(const BlendBwdParams p)
 				// (half tile, entry).
 				Terms r;
 				if (PAIRS && oka && okb) {
-					const Terms ra = terms(A, ha, g1, gb, gz), rb = terms(Bp, hb, g1, gb, gz);
+					const Terms ra = terms(A, ha, g1, gb, gz, a2, bp), rb = terms(Bp, hb, g1, gb, gz, a2, bp);
 					r.c01 = ra.c01 + rb.c01;
 					r.t = ra.t + rb.t;
 					r.m56 = ra.m56 + rb.m56;
@@ -307,10 +333,14 @@ blend_bwd_kernel(const BlendBwdParams p)
 					r.t7 = ra.t7 + rb.t7;
 					r.wG = ra.wG + rb.wG;
 					if constexpr (DEPTH) r.z9 = ra.z9 + rb.z9;
+					if constexpr (ABS) {
+						r.ax = ra.ax + rb.ax;
+						r.ay = ra.ay + rb.ay;
+					}
 				} else if (oka) {
-					r = terms(A, ha, g1, gb, gz);
+					r = terms(A, ha, g1, gb, gz, a2, bp);
 				} else if (PAIRS && okb) {
-					r = terms(Bp, hb, g1, gb, gz);
+					r = terms(Bp, hb, g1, gb, gz, a2, bp);
 				} else {
 					continue;   // wave-uniform
 				}
@@ -325,7 +355,23 @@ blend_bwd_kernel(const BlendBwdParams p)
 				v[7] = r.t7;
 				v[8] = r.wG;
 				float packed, ninth_row;
-				if constexpr (DEPTH) {   // the tenth (dL/dz) is reduced like the ninth: row sums, four more lanes of the same ds_add_f32
+				if constexpr (ABS) {   // the two absolute sums (behind the tenth, with DEPTH) are reduced like the ninth: row sums,
+				                       // delivered by further lanes of the same ds_add_f32
+					constexpr int K = DEPTH ? 3 : 2;
+					float e[K], e_row[K];
+					if constexpr (DEPTH) e[0] = r.z9;
+					e[K - 2] = r.ax;
+					e[K - 1] = r.ay;
+					wave_reduce9_rows_swap_f32<K>(v, e, packed, ninth_row, e_row);
+					GSR_OPAQUE_F32(packed);
+					GSR_OPAQUE_F32(ninth_row);
+#pragma unroll
+					for (int k = 0; k < K; k++) GSR_OPAQUE_F32(e_row[k]);
+					float val = red_ninth ? ninth_row : packed;
+					if constexpr (DEPTH) val = red_tenth ? e_row[0] : val;
+					val = red_ax ? e_row[K - 2] : (red_ay ? e_row[K - 1] : val);
+					if (red_lane || red_tenth || red_ax || red_ay) atomicAdd(red_abs_base + ((int)pos - (int)seg_lo) * red_abs_stride, val);
+				} else if constexpr (DEPTH) {   // the tenth (dL/dz) is reduced like the ninth: row sums, four more lanes of the same ds_add_f32
 					float v10[10];
 #pragma unroll
 					for (int c = 0; c < 9; c++) v10[c] = v[c];
@@ -354,13 +400,20 @@ blend_bwd_kernel(const BlendBwdParams p)
 #pragma unroll
 			for (int c = 0; c < 9; c++) any += fabsf(s_acc[c][i]);
 			if constexpr (DEPTH) any += fabsf(s_rec[i][2].z);
+			float abs_x = 0.f, abs_y = 0.f;
+			if constexpr (ABS) {   // (an entry whose only non-zero sums are these is touched too)
+				abs_x = s_rec[i][2].w;
+				abs_y = DEPTH ? s_absy[i] : s_rec[i][2].y;
+				any += abs_x + abs_y;
+			}
 			if (slot != 0xFFFFFFFFu && any != 0.f) {   // untouched / all-zero entries stay unflagged: the per-Gaussian sum skips them
 				p.touched[slot] = 1;
 				float4* dst = reinterpret_cast<float4*>(p.partials + (size_t)slot * (4 * SLOT_F4));
 				// slot order (partials.h): colour r g b, w dx, w dy, w dx dx, w dx dy, w dy dy, w
 				dst[0] = make_float4(s_acc[0][i], s_acc[4][i], s_acc[3][i], s_acc[1][i]);
 				dst[1] = make_float4(s_acc[5][i], s_acc[2][i], s_acc[6][i], s_acc[7][i]);
-				if constexpr (DEPTH) *reinterpret_cast<float2*>(dst + 2) = make_float2(s_acc[8][i], s_rec[i][2].z);   // + [9] dL/dz
+				if constexpr (ABS) dst[2] = make_float4(s_acc[8][i], DEPTH ? s_rec[i][2].z : 0.f, abs_x, abs_y);   // + [10], [11]: the absolute sums
+				else if constexpr (DEPTH) *reinterpret_cast<float2*>(dst + 2) = make_float2(s_acc[8][i], s_rec[i][2].z);   // + [9] dL/dz
 				else reinterpret_cast<float*>(dst + 2)[0] = s_acc[8][i];
 			}
 		}
@@ -372,7 +425,16 @@ int launch_blend_bwd(const BlendBwdParams& p, hipStream_t stream)
 {
 	const bool depth = p.dL_ddepth || p.dL_dalpha;
 	if (depth && !p.depth) return GSR_ERR_INVALID_ARG;
-	if (p.half_tiles && depth)
+	if (p.abs_sums) {
+		if (p.half_tiles && depth)
+			GSR_LAUNCH((blend_bwd_kernel<2, true, true>), tile_grid(p.deal), 128, stream, p);
+		else if (p.half_tiles)
+			GSR_LAUNCH((blend_bwd_kernel<2, false, true>), tile_grid(p.deal), 128, stream, p);
+		else if (depth)
+			GSR_LAUNCH((blend_bwd_kernel<4, true, true>), tile_grid(p.deal), 256, stream, p);
+		else
+			GSR_LAUNCH((blend_bwd_kernel<4, false, true>), tile_grid(p.deal), 256, stream, p);
+	} else if (p.half_tiles && depth)
 		GSR_LAUNCH((blend_bwd_kernel<2, true>), tile_grid(p.deal), 128, stream, p);
 	else if (p.half_tiles)
 		GSR_LAUNCH((blend_bwd_kernel<2, false>), tile_grid(p.deal), 128, stream, p);

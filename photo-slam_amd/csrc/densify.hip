@@ -632,11 +632,41 @@ mcmc_noise_kernel(int P, float* __restrict__ xyz, const float* __restrict__ opac
 
 static inline int mcmc_move_units(int row_floats) { return (row_floats & 3) == 0 ? row_floats / 4 : row_floats; }
 
+// The densification statistics of one view from the absolute screen-space pair (gsr_backward_args.dL_dmean2D_abs, [P,2]): the
+// arithmetic of densify_stats_kernel (train_ops.hip) on the norm of that pair.  It lives in this translation unit because it is
+// built without FMA contraction like preprocess_bwd.hip, whose fused form (stat_* next to dL_dmean2D_abs) it has to match bit for bit.
+__global__ void __launch_bounds__(256)
+densify_stats_abs_kernel(int P, const float* __restrict__ abs2, const int* __restrict__ radii, float* __restrict__ accum,
+                         float* __restrict__ denom, float* __restrict__ max_radii)
+{
+	const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	if (i >= P) return;
+	const int r = radii[i];
+	if (r > 0) {
+		const float gx = abs2[2 * (size_t)i], gy = abs2[2 * (size_t)i + 1];
+		accum[i] += sqrtf(gx * gx + gy * gy);
+		denom[i] += 1.0f;
+		max_radii[i] = fmaxf(max_radii[i], (float)r);
+	}
+}
+
 }  // namespace gsr
 
 using namespace gsr;
 
 extern "C" {
+
+int gsr_densify_stats_abs(int P, const float* dL_dmean2D_abs, const int* radii, float* xyz_gradient_accum, float* denom,
+                          float* max_radii2D, void* stream_)
+{
+	if (P < 0) return GSR_ERR_INVALID_ARG;
+	if (P == 0) return GSR_OK;
+	if (!dL_dmean2D_abs || !radii || !xyz_gradient_accum || !denom || !max_radii2D) return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	GSR_LAUNCH(densify_stats_abs_kernel, div_up(P, 256), 256, stream, P, dL_dmean2D_abs, radii, xyz_gradient_accum, denom, max_radii2D);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
 
 size_t gsr_densify_morton_scratch_bytes(int n_new) { return knn_scratch_bytes(n_new < 0 ? 0 : n_new); }
 

@@ -620,6 +620,7 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	    !a->image_buffer || !a->dL_dpix || !a->dL_dcolor || !a->dL_dmean3D || a->R < 0)
 		return GSR_ERR_INVALID_ARG;
 	if (pose && (a->dL_dcolor_view || a->packed_view)) return GSR_ERR_UNSUPPORTED;   // not through the multi-GPU exchange
+	if (a->dL_dmean2D_abs && (a->dL_dcolor_view || a->packed_view)) return GSR_ERR_UNSUPPORTED;   // likewise
 	if (!a->dL_dopacity && !a->geom_adam) return GSR_ERR_INVALID_ARG;   // (dL_dmean2D / dL_dcov3D: nullable, see gsr.h)
 	if (a->shs && !a->dL_dsh && !a->dL_dcolor_view && !a->sh_adam) return GSR_ERR_INVALID_ARG;
 	if ((a->stat_grad_accum != nullptr) != (a->stat_denom != nullptr) || (a->stat_denom != nullptr) != (a->stat_max_radii != nullptr))
@@ -765,6 +766,7 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 		bp.half_tiles = blend_bwd_half_tiles(tiles) ? 1 : 0;
 		bp.depth = reinterpret_cast<const float*>(g.depth_key);
 		bp.dL_ddepth = a->dL_ddepth; bp.dL_dalpha = a->dL_dalpha;
+		bp.abs_sums = a->dL_dmean2D_abs ? 1 : 0;
 		if ((st = launch_blend_bwd(bp, stream)) != GSR_OK) return fail(st);
 	}
 	PROF_BWD(2);
@@ -815,6 +817,7 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	pb.reg_w_iso = reg ? a->geom_reg->w_isotropic : 0.f;
 	pb.reg_slab = (reg && a->geom_reg->loss) ? reinterpret_cast<float*>(a->geom_reg->scratch) : nullptr;
 	pb.reg_loss = reg ? a->geom_reg->loss : nullptr;
+	pb.dL_dmean2D_abs = a->dL_dmean2D_abs;
 	pb.notify_stream = nullptr; pb.notify_event = nullptr;
 	if (a->color_view_ready_stream && a->dL_dcolor_view) {
 		if ((st = t_sync.init_notify()) != GSR_OK) return fail(st);

@@ -137,6 +137,9 @@ struct BlendBwdParams {
 	const float* depth;     // [P] z per Gaussian (GeometryState::depth_key as floats)
 	const float* dL_ddepth; // [H,W] nullable
 	const float* dL_dalpha; // [H,W] nullable
+	// gsr_backward_args.dL_dmean2D_abs: the ABS instantiations also leave sum |w G (2 A' dx + B' dy)| and sum |w G (B' dx + 2 C' dy)|
+	// over the entry's pixels in slot words [10] and [11] (and write word [9], zero without the depth / alpha gradients); 0 = off
+	int abs_sums;
 };
 int launch_blend_bwd(const BlendBwdParams& p, hipStream_t stream);
 
@@ -228,6 +231,10 @@ struct PreprocessBwdParams {
 	float reg_w_opacity, reg_w_scale, reg_w_iso;
 	float* reg_slab;          // null = the loss values are not wanted
 	float* reg_loss;          // [3]
+	// absolute screen-space gradients (gsr_backward_args.dL_dmean2D_abs): the backward blend left the per-pixel absolute mean2D sums in
+	// slot words [10], [11]; the ABS instantiations carry them through the run sums, apply the positive per-Gaussian constants and
+	// write [P,2]; with stat_accum set the statistic is the norm of this pair.  null = off
+	float* dL_dmean2D_abs;
 };
 // The regularisers' loss slab: 3 sums (opacity, scale, isotropy), component-major, one entry per workgroup of preprocess_bwd_kernel
 static inline size_t reg_slab_floats(int P) { return 3 * (((size_t)(P > 0 ? P : 0) + 127) / 128) + 4; }   // PRB_THREADS

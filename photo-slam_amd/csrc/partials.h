@@ -8,20 +8,24 @@
 // their work.
 //   a[0..2] dL_dcolor   a[3], a[4] sum w dx, sum w dy   a[5..7] sum w dx dx, w dx dy, w dy dy   a[8] sum w
 //   a[9] dL/dz (the depth / alpha maps' backward, blend_bwd.hip: DEPTH) -- carried by the forms over float[10] / DEPTH only
+//   a[10], a[11] sum |w (2 A' dx + B' dy)|, sum |w (B' dx + 2 C' dy)| per pixel (blend_bwd.hip: ABS) -- carried by the forms over
+//   float[12] / ABS only, which take words [8..11] as one 16-byte load (the ABS blend writes word [9] too, zero without DEPTH)
 #pragma once
 #include "state.h"
 #include "wave64.h"
 
 namespace gsr {
 
-// U touched slots of a run in one trip: the loads first, the sums in slot order.  N = 10: word [9] too (one 8-byte load)
+// U touched slots of a run in one trip: the loads first, the sums in slot order.  N = 10: word [9] too (one 8-byte load);
+// N = 12: words [9..11] too (one 16-byte load)
 template <int U, int N>
 __device__ __forceinline__ void sum_slots_trip(const float4* src, unsigned long long& live, float (&a)[N])
 {
-	static_assert(N == 9 || N == 10, "nine sums, or ten with dL/dz");
+	static_assert(N == 9 || N == 10 || N == 12, "nine sums, ten with dL/dz, or twelve with the absolute mean2D sums");
 	int idx[U];
 	float4 x[U], y[U];
 	float z[U], zd[U];
+	float zx[U], zy[U];   // N == 12
 #pragma unroll
 	for (int j = 0; j < U; j++) {
 		idx[j] = __ffsll((long long)live) - 1;
@@ -31,7 +35,13 @@ __device__ __forceinline__ void sum_slots_trip(const float4* src, unsigned long 
 	for (int j = 0; j < U; j++) {
 		x[j] = src[SLOT_F4 * (size_t)idx[j]];
 		y[j] = src[SLOT_F4 * (size_t)idx[j] + 1];
-		if constexpr (N == 10) {
+		if constexpr (N == 12) {
+			const float4 t = src[SLOT_F4 * (size_t)idx[j] + 2];
+			z[j] = t.x;
+			zd[j] = t.y;
+			zx[j] = t.z;
+			zy[j] = t.w;
+		} else if constexpr (N == 10) {
 			const float2 t = *reinterpret_cast<const float2*>(src + SLOT_F4 * (size_t)idx[j] + 2);
 			z[j] = t.x;
 			zd[j] = t.y;
@@ -44,7 +54,11 @@ __device__ __forceinline__ void sum_slots_trip(const float4* src, unsigned long 
 		a[0] += x[j].x; a[1] += x[j].y; a[2] += x[j].z; a[3] += x[j].w;
 		a[4] += y[j].x; a[5] += y[j].y; a[6] += y[j].z; a[7] += y[j].w;
 		a[8] += z[j];
-		if constexpr (N == 10) a[9] += zd[j];
+		if constexpr (N >= 10) a[9] += zd[j];
+		if constexpr (N == 12) {
+			a[10] += zx[j];
+			a[11] += zy[j];
+		}
 	}
 }
 
@@ -81,7 +95,14 @@ __device__ __forceinline__ void wave_sum_partial_runs(uint32_t cnt, uint32_t fir
 	// a longer run was summed by long_run_sums_kernel (one wave per run), which left the total in the run's FIRST slot
 	if (cnt > LONG_RUN && touched[first]) {
 		const float4 x = part4[SLOT_F4 * (size_t)first], y = part4[SLOT_F4 * (size_t)first + 1];
-		const float z = part4[SLOT_F4 * (size_t)first + 2].x;
+		float z;
+		if constexpr (N == 12) {
+			const float4 t = part4[SLOT_F4 * (size_t)first + 2];
+			z = t.x;
+			a[9] = t.y; a[10] = t.z; a[11] = t.w;
+		} else {
+			z = part4[SLOT_F4 * (size_t)first + 2].x;
+		}
 		a[0] = x.x; a[1] = x.y; a[2] = x.z; a[3] = x.w;
 		a[4] = y.x; a[5] = y.y; a[6] = y.z; a[7] = y.w;
 		a[8] = z;
@@ -92,11 +113,11 @@ __device__ __forceinline__ void wave_sum_partial_runs(uint32_t cnt, uint32_t fir
 // One wave per listed run: sum its touched slots in a fixed order, store the total in the run's first slot and flag it.  Lane l owns
 // the k = ceil(cnt / 64) CONSECUTIVE slots [l k, (l + 1) k): 16-byte flag loads, then only the touched slots, four per trip.
 // (Rounds 2-5 also carried two lane-strided forms behind GSR_LRS_MODE; this one measured fastest -- 20 -> 14 us at C3 -- and stayed.)
-// DEPTH: word [9] (dL/dz) too, summed by a tenth full-wave reduction.
-template <bool DEPTH>
+// DEPTH: word [9] (dL/dz) too, summed by a tenth full-wave reduction.  ABS: words [9..11], three more reductions.
+template <bool DEPTH, bool ABS = false>
 __device__ __forceinline__ void wave_sum_long_run(uint32_t first, uint32_t cnt, float* __restrict__ partials, uint8_t* __restrict__ touched)
 {
-	constexpr int N = DEPTH ? 10 : 9;
+	constexpr int N = ABS ? 12 : (DEPTH ? 10 : 9);
 	const int l = lane_id();
 	float4* part4 = reinterpret_cast<float4*>(partials);
 	float v[N];
@@ -120,13 +141,21 @@ __device__ __forceinline__ void wave_sum_long_run(uint32_t first, uint32_t cnt, 
 	}
 	const bool some = wave_ballot(any) != 0ull;
 	float v9 = 0.f;
+	// (ABS without DEPTH: word [9] rides in the 16-byte load of words [8..11] and is zero -- the ABS blend writes it -- so it is
+	// neither reduced nor needed: v9 stays 0)
 	if constexpr (DEPTH) v9 = wave_sum_f32_lane63(v[9]);
+	float v10 = 0.f, v11 = 0.f;
+	if constexpr (ABS) {
+		v10 = wave_sum_f32_lane63(v[10]);
+		v11 = wave_sum_f32_lane63(v[11]);
+	}
 	float (&v_nine)[9] = *reinterpret_cast<float (*)[9]>(&v[0]);
 	wave_reduce9_f32(v_nine);  // totals in lane 63; every lane has read its slots by now (the reduction is a rendezvous)
 	if (l == 63) {
 		part4[SLOT_F4 * (size_t)first] = make_float4(v[0], v[1], v[2], v[3]);
 		part4[SLOT_F4 * (size_t)first + 1] = make_float4(v[4], v[5], v[6], v[7]);
-		if constexpr (DEPTH) *reinterpret_cast<float2*>(part4 + SLOT_F4 * (size_t)first + 2) = make_float2(v[8], v9);
+		if constexpr (ABS) part4[SLOT_F4 * (size_t)first + 2] = make_float4(v[8], v9, v10, v11);
+		else if constexpr (DEPTH) *reinterpret_cast<float2*>(part4 + SLOT_F4 * (size_t)first + 2) = make_float2(v[8], v9);
 		else reinterpret_cast<float*>(part4 + SLOT_F4 * (size_t)first + 2)[0] = v[8];
 		touched[first] = some ? 1 : 0;
 	}

@@ -306,7 +306,13 @@ __device__ __forceinline__ void pack_view_row(const PreprocessBwdParams& p, int 
 // plain stores (kernels.h: reg_slab_floats); reg_final_sum_kernel adds the entries in double.  No atomics: the same bits every time.
 // Instantiated with PACKED = POSE = false only (launch_preprocess_bwd), and an instantiation of its own, so that the kernels
 // without it stay the same code.
-template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false, bool REG = false>
+// ABS: the absolute screen-space gradients (gsr_backward_args.dL_dmean2D_abs).  The backward blend's ABS instantiations left
+// sum_p |w (2 A' dx + B' dy)| and sum_p |w (B' dx + 2 C' dy)| in slot words [10], [11], with the conic as the blend prescales it
+// (blend.h: A' = -log2(e) A / 2, B' = -log2(e) B): they ride through the run sums as a[10], a[11], and the positive constants --
+// the opacity, ln 2, W/2 and H/2 -- are applied here, behind the reduction.  With stat_accum set the statistic is the norm of
+// this pair.  Instantiations of their own (PACKED = false: not through the multi-GPU exchange), so that the kernels without it
+// stay the same code.
+template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false, bool REG = false, bool ABS = false>
 __global__ void __launch_bounds__(PRB_THREADS)
 preprocess_bwd_kernel(const PreprocessBwdParams p)
 {
@@ -335,7 +341,7 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 	// ------------------------------------------------------------------ gradients of the blend stage (partials.h)
 	// the per-instance slots of this Gaussian's tiles are summed here, in registers: colour 0..2, mean2D moments 3..4,
 	// conic moments 5..7, opacity 8 never round-trip through HBM
-	float a[DEPTH ? 10 : 9];
+	float a[ABS ? 12 : (DEPTH ? 10 : 9)];
 	{
 		const uint32_t cnt = (vis && p.partials) ? p.tiles_touched[idx] : 0u;
 		const uint32_t first = cnt ? __float_as_uint(p.rec[3 * (size_t)idx + 2].w) : 0u;
@@ -360,6 +366,7 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 	float4 ga0 = make_float4(0.f, 0.f, 0.f, 0.f), ga1 = make_float4(0.f, 0.f, 0.f, 0.f);
 	float g_opacity = 0.f;
 	float aa_o = 0.f;   // AA: the record's (compensated) opacity
+	float abs_x = 0.f, abs_y = 0.f;   // ABS: sum_p |g_p.x|, sum_p |g_p.y| of dL_dmean2D's per-pixel terms g_p
 
 	if (vis) {
 		mx = p.means3D[3 * (size_t)idx];
@@ -373,6 +380,12 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		ga0 = make_float4(a[0], a[1], a[2], -o * p.half_w * (a[3] * A + a[4] * B));
 		ga1 = make_float4(-o * p.half_h * (a[4] * C + a[3] * B), -0.5f * o * a[5], -0.5f * o * a[6], -0.5f * o * a[7]);
 		g_opacity = a[8];
+		if constexpr (ABS) {
+			// |g_p.x| = o W/2 |w (A dx + B dy)| = o W/2 ln 2 |w (2 A' dx + B' dy)|: the positive constants behind the sum
+			constexpr float LN2 = 0.6931471805599453f;
+			abs_x = fabsf(o) * p.half_w * (LN2 * a[10]);
+			abs_y = fabsf(o) * p.half_h * (LN2 * a[11]);
+		}
 		if constexpr (AA) {
 			aa_o = o;   // (the chain rule of the opacity waits for h: below, behind the 2-D covariance)
 		} else {
@@ -390,6 +403,10 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 			p.dL_dmean2D[3 * (size_t)idx + 0] = ga0.w;
 			p.dL_dmean2D[3 * (size_t)idx + 1] = ga1.x;
 			p.dL_dmean2D[3 * (size_t)idx + 2] = 0.f;
+		}
+		if constexpr (ABS) {
+			p.dL_dmean2D_abs[2 * (size_t)idx + 0] = abs_x;
+			p.dL_dmean2D_abs[2 * (size_t)idx + 1] = abs_y;
 		}
 		p.dL_dcolor[3 * (size_t)idx + 0] = ga0.x;
 		p.dL_dcolor[3 * (size_t)idx + 1] = ga0.y;
@@ -425,7 +442,8 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 	}
 	if (p.stat_accum && vis) {
 		// densify_stats_kernel (train_ops.hip; gaussian_mapper.cpp:714-719, gaussian_model.cpp:817-831) on the values at hand
-		p.stat_accum[idx] += sqrtf(ga0.w * ga0.w + ga1.x * ga1.x);
+		if constexpr (ABS) p.stat_accum[idx] += sqrtf(abs_x * abs_x + abs_y * abs_y);   // (densify_stats_abs_kernel, densify.hip)
+		else p.stat_accum[idx] += sqrtf(ga0.w * ga0.w + ga1.x * ga1.x);
 		p.stat_denom[idx] += 1.0f;
 		p.stat_max_radii[idx] = fmaxf(p.stat_max_radii[idx], (float)p.radii[idx]);
 	}
@@ -914,7 +932,7 @@ int launch_sh_adam_lazy(int P, const int* radii, const LazyAdam& a, hipStream_t 
 // The runs of more than LONG_RUN instance slots (partials.h): one wave per run, a fixed grid that strides over the list the
 // forward pass left (its length lives on the device).
 constexpr int LRS_BLOCKS = 1024;   // (one listed run per wave at C3: 512 -> 1 024 workgroups: 18.6 -> 14.1 us; more: equal)
-template <bool DEPTH>
+template <bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(256)
 long_run_sums_kernel(const PreprocessBwdParams p)
 {
@@ -926,7 +944,7 @@ long_run_sums_kernel(const PreprocessBwdParams p)
 		const uint32_t g = p.long_runs[(size_t)list * p.long_capacity + e];
 		const uint32_t cnt = p.tiles_touched[g];
 		const uint32_t first = __float_as_uint(p.rec[3 * (size_t)g + 2].w);
-		wave_sum_long_run<DEPTH>(first, cnt, p.partials, p.touched);
+		wave_sum_long_run<DEPTH, ABS>(first, cnt, p.partials, p.touched);
 	}
 }
 
@@ -1010,7 +1028,11 @@ int launch_reg_zero(float* loss, hipStream_t stream)
 
 int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 {
-	if (p.partials && p.depth) GSR_LAUNCH(long_run_sums_kernel<true>, LRS_BLOCKS, 256, stream, p);
+	const bool abs_sums = p.dL_dmean2D_abs != nullptr;   // the absolute screen-space gradients: slot words [10], [11]
+	if (abs_sums && (p.dL_dcolor_view || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // not through the multi-GPU exchange
+	if (p.partials && abs_sums && p.depth) GSR_LAUNCH((long_run_sums_kernel<true, true>), LRS_BLOCKS, 256, stream, p);
+	else if (p.partials && abs_sums) GSR_LAUNCH((long_run_sums_kernel<false, true>), LRS_BLOCKS, 256, stream, p);
+	else if (p.partials && p.depth) GSR_LAUNCH(long_run_sums_kernel<true>, LRS_BLOCKS, 256, stream, p);
 	else if (p.partials) GSR_LAUNCH(long_run_sums_kernel<false>, LRS_BLOCKS, 256, stream, p);
 	const bool factored = p.dL_dcolor_view != nullptr;
 	const bool adam = p.adam_exp_avg != nullptr;
@@ -1029,6 +1051,14 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 	if (reg && !p.scales && (p.reg_w_scale != 0.f || p.reg_w_iso != 0.f)) return GSR_ERR_INVALID_ARG;
 #define GSR_PRB(RO, AAV)                                                                                                          \
 	do {                                                                                                                          \
+		if (abs_sums) {                                                                                                           \
+			if (reg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV, true, true>), grid, PRB_THREADS, stream, p);  \
+			else if (reg) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV, true, true>), grid, PRB_THREADS, stream, p);   \
+			else if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, true, AAV, false, true>), grid, PRB_THREADS, stream, p); \
+			else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, true, AAV, false, true>), grid, PRB_THREADS, stream, p);  \
+			else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV, false, true>), grid, PRB_THREADS, stream, p); \
+			else GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV, false, true>), grid, PRB_THREADS, stream, p);       \
+		} else                                                                                                                    \
 		if (reg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV, true>), grid, PRB_THREADS, stream, p);  \
 		else if (reg) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV, true>), grid, PRB_THREADS, stream, p);      \
 		else if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, true, AAV>), grid, PRB_THREADS, stream, p);       \

@@ -80,6 +80,40 @@ static inline void wave_reduce10_swap_f32(const float (&v)[10], float& packed, f
 	ninth_row = r8;
 	tenth_row = r9;
 }
+// wave_reduce9_swap_f32 plus the row sums of K more values (the absolute mean2D sums of the backward blend, with the tenth in front
+// of them where the depth map has a gradient).  The ninth and the K extras travel in ONE exchange, 128 bits per lane: the same
+// number of rendezvous as the nine-value form, for the reason given above.  hipemu's exchange carries 64 bits per lane; the upper
+// 64 ride in the side array below, which every lane fills BEFORE the exchange's rendezvous and reads behind it (fibers switch at
+// rendezvous only, and one workgroup of at most 1 024 threads runs at a time: hip_emu.h).
+inline uint64_t emu_exchange_hi[16][64];
+template <int K>
+static inline void wave_reduce9_rows_swap_f32(const float (&v)[9], const float (&e)[K], float& packed, float& ninth_row, float (&e_row)[K])
+{
+	static_assert(K >= 1 && K <= 3, "the ninth and up to three more values fill the exchange");
+	float t[9];
+	for (int c = 0; c < 9; c++) t[c] = v[c];
+	uint32_t b[4] = {0u, 0u, 0u, 0u};
+	memcpy(&b[0], &v[8], 4);
+	for (int k = 0; k < K; k++) memcpy(&b[1 + k], &e[k], 4);
+	uint64_t* const hi = emu_exchange_hi[(threadIdx.x >> 6) & 15u];
+	hi[::hipemu::lane()] = (uint64_t)b[2] | ((uint64_t)b[3] << 32);
+	const uint64_t* s = ::hipemu::wave_exchange((uint64_t)b[0] | ((uint64_t)b[1] << 32));
+	float r[4] = {0.f, 0.f, 0.f, 0.f};
+	for (int i = 0; i < 16; i++) {
+		const int src = (::hipemu::lane() & ~15) + i;
+		const uint32_t bits[4] = {(uint32_t)s[src], (uint32_t)(s[src] >> 32), (uint32_t)hi[src], (uint32_t)(hi[src] >> 32)};
+		for (int k = 0; k < 4; k++) {
+			float f;
+			memcpy(&f, &bits[k], 4);
+			r[k] += f;
+		}
+	}
+	::hipemu::wave_sync();
+	wave_reduce9_f32(t);
+	packed = t[wave_swap9_component(::hipemu::lane())];
+	ninth_row = r[0];
+	for (int k = 0; k < K; k++) e_row[k] = r[1 + k];
+}
 static inline float4 load_stream_f4(const float4* p) { return *p; }
 static inline void store_stream_f4(float4* p, const float4 v) { *p = v; }
 #define GSR_SCHED_BARRIER() ((void)0)
@@ -305,6 +339,16 @@ __device__ __forceinline__ void wave_reduce10_swap_f32(const float (&v)[10], flo
 {
 	wave_reduce9_swap_f32(*reinterpret_cast<const float(*)[9]>(&v[0]), packed, ninth_row);
 	tenth_row = wave_row_sum16_f32(v[9]);
+}
+// ... and K more values reduced like the ninth (the absolute mean2D sums of the backward blend, blend_bwd.hip: ABS; with the depth
+// map's tenth in front of them): 4 DPP adds each
+template <int K>
+__device__ __forceinline__ void wave_reduce9_rows_swap_f32(const float (&v)[9], const float (&e)[K], float& packed, float& ninth_row,
+                                                            float (&e_row)[K])
+{
+	wave_reduce9_swap_f32(v, packed, ninth_row);
+#pragma unroll
+	for (int k = 0; k < K; k++) e_row[k] = wave_row_sum16_f32(e[k]);
 }
 // the value whose total `packed` holds in this lane
 __device__ __forceinline__ int wave_swap9_component(int lane)

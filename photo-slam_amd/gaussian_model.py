@@ -467,17 +467,26 @@ class GaussianModel:
         return lr
 
     # ---- densification statistics, src/gaussian_model.cpp:817-831
-    def addDensificationStats(self, viewspace_point_tensor, update_filter):
-        g = viewspace_point_tensor.grad
+    def addDensificationStats(self, viewspace_point_tensor, update_filter, absgrad=None):
+        """absgrad (extension): the [P,2] absolute screen-space gradients of the view (the viewspace tensor's `.absgrad`,
+        GaussianRasterizationSettings.absgrad_) -- their norm is accumulated instead of the signed gradient's (AbsGS)"""
+        g = viewspace_point_tensor.grad if absgrad is None else absgrad
         self.xyz_gradient_accum_[update_filter] += torch.norm(g[update_filter][:, :2], dim=-1, keepdim=True)
         self.denom_[update_filter] += 1
 
-    def addViewStats(self, viewspace_point_tensor, radii):
+    def addViewStats(self, viewspace_point_tensor, radii, absgrad=None):
         """max_radii2D / xyz_gradient_accum / denom update of one view (gaussian_mapper.cpp:714-719) in one
-        HIP pass (gsr_densify_stats) instead of boolean-mask gathers and scatters."""
+        HIP pass (gsr_densify_stats) instead of boolean-mask gathers and scatters.  absgrad: the view's [P,2] absolute
+        screen-space gradients, accumulated instead (gsr_densify_stats_abs)."""
         lib = rp._lib()
-        g = viewspace_point_tensor.grad.contiguous()
         r = radii.contiguous()
+        if absgrad is not None:
+            g = absgrad.contiguous()
+            capi.check(lib, lib.gsr_densify_stats_abs(self.xyz_.shape[0], g.data_ptr(), r.data_ptr(), self.xyz_gradient_accum_.data_ptr(),
+                                                      self.denom_.data_ptr(), self.max_radii2D_.data_ptr(), rp._stream_ptr(g)),
+                       "gsr_densify_stats_abs")
+            return
+        g = viewspace_point_tensor.grad.contiguous()
         capi.check(lib, lib.gsr_densify_stats(self.xyz_.shape[0], g.data_ptr(), r.data_ptr(), self.xyz_gradient_accum_.data_ptr(),
                                               self.denom_.data_ptr(), self.max_radii2D_.data_ptr(), rp._stream_ptr(g)),
                    "gsr_densify_stats")

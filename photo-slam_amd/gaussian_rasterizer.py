@@ -65,10 +65,19 @@ class GaussianRasterizationSettings:
     # the per-Gaussian weights are lambda_opacity / V and lambda_scale / (3 V), lambda_isotropic / (3 V), V = max(visible count of
     # the forward pass, 1).  loss: a float32 [3] tensor that receives the three loss values, or None (they are not formed).
     geom_reg_: dict = None
+    # extension (gsr_backward_args.dL_dmean2D_abs, include/gsr.h; AbsGS, gsplat's `absgrad`): backward also forms the absolute
+    # screen-space gradients -- per Gaussian the sums over its pixels of |d/dmean2D.x| and |d/dmean2D.y| of each pixel's own term --
+    # and leaves them, as upstream does, in a `.absgrad` attribute ([P,2]) of the means2D / viewspace tensor the forward was given.
+    # With view_stats_ the fused statistics accumulate the norm of that pair.  Not together with sh_grad_view_.
+    absgrad_: bool = False
 
 
-def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth=None, alpha=None):
-    """the forward of both autograd Functions (depth / alpha: [H,W] tensors the maps are rendered into, or None)"""
+def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth=None, alpha=None, means2D=None):
+    """the forward of both autograd Functions (depth / alpha: [H,W] tensors the maps are rendered into, or None; means2D: the
+    viewspace tensor, which receives `.absgrad` in backward with settings.absgrad_)"""
+    if s.absgrad_ and s.sh_grad_view_ is not None:
+        raise RuntimeError("absgrad_ is not available through the view-factored exchange (sh_grad_view_)")
+    ctx.viewspace = means2D if s.absgrad_ else None
     num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = rp.RasterizeGaussiansCUDA(
         s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
         s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
@@ -103,6 +112,7 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None, pose=False)
         geom_reg = dict(w_opacity=float(s.geom_reg_.get("lambda_opacity", 0.0)) / V,
                         w_scale=float(s.geom_reg_.get("lambda_scale", 0.0)) / (3.0 * V),
                         w_isotropic=float(s.geom_reg_.get("lambda_isotropic", 0.0)) / (3.0 * V), loss=s.geom_reg_.get("loss"))
+    absgrad = torch.empty((means3D.size(0), 2), dtype=torch.float32, device=means3D.device) if s.absgrad_ else None
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
      dL_drotations, *dL_dcamera) = rp.RasterizeGaussiansBackwardCUDA(
         s.bg_, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier_, cov3Ds_precomp, s.viewmatrix_,
@@ -114,7 +124,9 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None, pose=False)
         s.sh_adam_ if (s.sh_grad_view_ is None or (s.sh_adam_ or {}).get("row_step") is not None) else None, s.view_stats_,
         s.geom_adam_, s.training_outputs_only_, dL_ddepth=cont(grad_depth), dL_dalpha=cont(grad_alpha),
         pose_grad=pose, workspace=s.workspace_ if (pose or geom_reg is not None) else None, antialiasing=s.antialiasing_,
-        geom_reg=geom_reg)
+        geom_reg=geom_reg, absgrad=absgrad)
+    if absgrad is not None and ctx.viewspace is not None:
+        ctx.viewspace.absgrad = absgrad   # (as upstream: next to .grad on the viewspace tensor)
     # order of src/gaussian_rasterizer.cpp:159-179
     def g(t, like):   # (None where an extension took the gradient's place)
         return t if like.numel() and t is not None else None
@@ -131,7 +143,8 @@ class GaussianRasterizerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        return _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+        return _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                        means2D=means2D)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
@@ -148,7 +161,7 @@ class GaussianRasterizerDepthFunction(torch.autograd.Function):
         s = raster_settings
         depth = torch.zeros((int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
         alpha = torch.zeros_like(depth)
-        color, radii = _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth, alpha)
+        color, radii = _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth, alpha, means2D=means2D)
         return color, radii, depth, alpha
 
     @staticmethod
@@ -169,10 +182,10 @@ class GaussianRasterizerPoseFunction(torch.autograd.Function):
         if s.sh_grad_view_ is not None:
             raise RuntimeError("camera gradients are not available through the view-factored exchange (sh_grad_view_)")
         if not s.render_depth_:
-            return _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s)
+            return _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, means2D=means2D)
         depth = torch.zeros((int(s.image_height_), int(s.image_width_)), dtype=torch.float32, device=means3D.device)
         alpha = torch.zeros_like(depth)
-        color, radii = _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth, alpha)
+        color, radii = _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth, alpha, means2D=means2D)
         return color, radii, depth, alpha
 
     @staticmethod

@@ -135,6 +135,9 @@ public:
 	void optimizerStepGroup(int group);
 	void zeroGrad();
 	void addDensificationStats(torch::Tensor& viewspace_point_tensor, torch::Tensor& update_filter);  // :817-831
+	// ... from the view's [P,2] absolute screen-space gradients instead of the viewspace tensor's gradient (AbsGS:
+	// GaussianRasterizationExtensions::absgrad_)
+	void addDensificationStats(torch::Tensor& viewspace_point_tensor, torch::Tensor& update_filter, const torch::Tensor& absgrad);
 	std::vector<torch::Tensor> params()
 	{
 		syncFeatures();
@@ -300,6 +303,17 @@ public:
 	bool read_reg_losses_ = true;
 	torch::Tensor lastRegLosses() const { return last_reg_losses_; }
 	torch::Tensor last_reg_losses_;
+	// Densification by absolute screen-space gradients (AbsGS; gsplat's absgrad): the backward pass sums |d/dmean2D| per pixel
+	// before the reduction over a Gaussian's pixels (gsr_backward_args.dL_dmean2D_abs), the fused statistics accumulate the norm of
+	// those sums, and densifyAndPrune compares their mean with densify_abs_grad_threshold_ instead of densify_grad_threshold_.
+	// 0.0008 is gsplat's recommended value with absgrad: a default for the caller to override, not a tuned number.  Off = the
+	// signed statistic and threshold of the reference.  lastAbsgrad(): the [P,2] array of the last step, undefined when that
+	// step formed none or rebuilt the model (its rows would be those of the model before the rebuild).  Not
+	// with a process group: throws.
+	bool absgrad_ = false;
+	float densify_abs_grad_threshold_ = 0.0008f;
+	torch::Tensor lastAbsgrad() const { return last_absgrad_; }
+	torch::Tensor last_absgrad_;
 	// Fixed-budget maps (3DGS-MCMC): with mcmc_ on and densify_ set, the iterations that rebuild today run relocateDead + addNew
 	// instead of densifyAndPrune -- the count grows by 5 % per event to exactly mcmc_cap_max_ and then stays, no tensor is rebuilt
 	// on a relocation, that iteration's update is skipped as a rebuild's is, and the opacity is never reset -- and every step adds

@@ -123,6 +123,11 @@ struct GaussianRasterizationExtensions {
 	double opacity_reg_ = 0.0, scale_reg_ = 0.0, isotropic_reg_ = 0.0;
 	torch::Tensor reg_loss_;
 	bool hasGeomReg() const { return opacity_reg_ != 0.0 || scale_reg_ != 0.0 || isotropic_reg_ != 0.0 || reg_loss_.defined(); }
+	// the absolute screen-space gradients (gsr_backward_args.dL_dmean2D_abs; AbsGS, gsplat's absgrad): a float32 [P,2] tensor of
+	// the caller's that backward() fills -- what upstream leaves in `.absgrad` of the viewspace tensor (a C++ tensor carries no
+	// attributes; the Python host does attach it there).  With view_stats_ the fused statistics accumulate the norm of this pair.
+	// Undefined = off.  Not together with sh_grad_view_.
+	torch::Tensor absgrad_;
 };
 
 class GaussianRasterizerFunctionEx : public torch::autograd::Function<GaussianRasterizerFunctionEx> {

@@ -121,6 +121,11 @@ struct RasterBackwardExtensions {
 	// the regularisers on the visible Gaussians: nullptr = off.  Not together with dL_dcolor_view or pose_grad.  workspace: when
 	// given, it owns the scratch of the loss sums (otherwise allocated per call)
 	const GeomRegStep* geom_reg = nullptr;
+	// a contiguous float32 [P,2] tensor that receives the absolute screen-space gradients (gsr_backward_args.dL_dmean2D_abs; AbsGS,
+	// gsplat's absgrad): per Gaussian the sums over its pixels of |d/dmean2D.x| and |d/dmean2D.y| of each pixel's own term; every
+	// row is written.  With view_stats the statistics accumulate the norm of this pair.  Undefined = off.  Not together with
+	// dL_dcolor_view.
+	torch::Tensor absgrad;
 };
 
 // (num_rendered, out_color[3,H,W], radii[P] i32, geomBuffer u8, binningBuffer u8, imgBuffer u8)

@@ -118,6 +118,7 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 	b.color_view_ready_stream = e.color_view_ready_stream_;
 	b.packed_view = e.packed_view_;
 	b.packed_capacity = e.packed_capacity_;
+	b.absgrad = e.absgrad_;
 	PoseGradients camera;
 	if (pose) {
 		b.pose_grad = &camera;

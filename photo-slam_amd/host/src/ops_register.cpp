@@ -94,6 +94,26 @@ std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_contribution(
 	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
 	                 colors_precomp, scales, rotations, cov3Ds_precomp);
 }
+// rasterize_gaussians_modes (ex) with the absolute screen-space gradients: backward() of the returned image fills `absgrad`
+// ([P,2], GaussianRasterizationExtensions::absgrad_).  (image, radii)
+std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_absgrad(
+    torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh, torch::Tensor colors_precomp, torch::Tensor opacities,
+    torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3Ds_precomp, torch::Tensor bg, double scale_modifier,
+    torch::Tensor viewmatrix, torch::Tensor projmatrix, double tanfovx, double tanfovy, int64_t image_height, int64_t image_width,
+    int64_t sh_degree, torch::Tensor campos, int64_t raw_params, torch::Tensor absgrad)
+{
+	GaussianRasterizationSettings s((int)image_height, (int)image_width, (float)tanfovx, (float)tanfovy, bg,
+	                                (float)scale_modifier, viewmatrix, projmatrix, (int)sh_degree, campos, false);
+	auto has = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
+	GaussianRasterizationExtensions e;
+	e.raw_params_ = (int)raw_params & 7;
+	e.cull_empty_tiles_ = (raw_params & 8) != 0;
+	e.antialiasing_ = (raw_params & 256) != 0;
+	e.absgrad_ = absgrad;
+	GaussianRasterizerEx r(s, e);
+	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
+	                 colors_precomp, scales, rotations, cov3Ds_precomp);
+}
 double covisibility_op(torch::Tensor a, torch::Tensor b) { return covisibility(a, b); }
 
 torch::Tensor mark_visible(torch::Tensor means3D, torch::Tensor viewmatrix, torch::Tensor projmatrix)
@@ -202,6 +222,12 @@ torch::Tensor trainer_render_and_backward_depth(int64_t h, torch::Tensor view, t
                                                 torch::Tensor gt_depth)
 {
 	return get(h)->renderAndBackward(make_kf(view, proj, campos, fovx, fovy, H, W), gt, mask, gt_depth).detach();
+}
+// TrainStep::lastAbsgrad: the [P,2] absolute screen-space gradients of the last step that formed them, or an empty tensor
+torch::Tensor trainer_last_absgrad(int64_t h)
+{
+	auto t = get(h);
+	return t->lastAbsgrad().defined() ? t->lastAbsgrad() : torch::empty({0, 2}, t->gaussians_->xyz_.options().requires_grad(false));
 }
 // TrainStep::lastRegLosses: the three regulariser terms of the last step ([3]), or an empty tensor when they were not formed
 torch::Tensor trainer_last_reg_losses(int64_t h)
@@ -386,6 +412,8 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "scale_reg") t->scale_reg_ = v;
 		else if (k == "isotropic_reg") t->isotropic_reg_ = v;
 		else if (k == "read_reg_losses") t->read_reg_losses_ = v != 0.0;
+		else if (k == "absgrad") t->absgrad_ = v != 0.0;
+		else if (k == "densify_abs_grad_threshold") t->densify_abs_grad_threshold_ = (float)v;
 		else if (k == "mcmc") t->mcmc_ = v != 0.0;
 		else if (k == "mcmc_cap_max") t->mcmc_cap_max_ = (int64_t)v;
 		else if (k == "mcmc_noise_lr") t->mcmc_noise_lr_ = v;
@@ -634,6 +662,8 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("rasterize_gaussians", &rasterize_gaussians);
 	m.def("rasterize_gaussians_modes", &rasterize_gaussians_modes);
 	m.def("rasterize_gaussians_contribution", &rasterize_gaussians_contribution);
+	m.def("rasterize_gaussians_absgrad", &rasterize_gaussians_absgrad);
+	m.def("trainer_last_absgrad", &trainer_last_absgrad);
 	m.def("covisibility", &covisibility_op);
 	m.def("trainer_score_contribution", &trainer_score_contribution);
 	m.def("trainer_prune_uncontributing", &trainer_prune_uncontributing);

@@ -391,6 +391,14 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 			fill_sh_adam(sh_adam, const_cast<float*>(a.shs), adam, lazy);
 			a.sh_adam = &adam;
 		}
+		if (ext.absgrad.defined()) {
+			const auto& t = ext.absgrad;
+			if (factored) throw std::runtime_error("absgrad is not available through the view-factored exchange (dL_dcolor_view)");
+			if (t.dim() != 2 || t.size(0) != P || t.size(1) != 2 || t.scalar_type() != torch::kFloat32 || !t.is_contiguous() ||
+			    t.device() != means3D.device())
+				throw std::runtime_error("absgrad must be a contiguous float32 (num_points, 2) tensor on the device of means3D");
+			a.dL_dmean2D_abs = t.data_ptr<float>();
+		}
 		a.dL_dcolor_view = factored ? dL_dcolor_view.data_ptr<float>() : nullptr;
 		a.color_view_ready_stream = factored ? ext.color_view_ready_stream : nullptr;
 		if (factored && ext.packed_view.defined()) {

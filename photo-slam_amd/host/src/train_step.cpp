@@ -189,6 +189,14 @@ void GaussianModel::addDensificationStats(torch::Tensor& viewspace_point_tensor,
 	denom_.index_put_({update_filter}, denom_.index({update_filter}) + 1);
 }
 
+void GaussianModel::addDensificationStats(torch::Tensor& viewspace_point_tensor, torch::Tensor& update_filter, const torch::Tensor& absgrad)
+{
+	if (!absgrad.defined()) return addDensificationStats(viewspace_point_tensor, update_filter);
+	auto n = torch::norm(absgrad.index({update_filter}).slice(1, 0, 2), 2, {-1}, true);
+	xyz_gradient_accum_.index_put_({update_filter}, xyz_gradient_accum_.index({update_filter}) + n);
+	denom_.index_put_({update_filter}, denom_.index({update_filter}) + 1);
+}
+
 // a viewer's render: the raw leaves in the rasterizer, forward-only, into the second workspace
 GaussianRasterizationExtensions TrainStep::viewExtensions()
 {
@@ -394,7 +402,10 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		throw std::runtime_error("TrainStep: the opacity / scale / isotropy regularisers are not supported with a process group");
 	if (mcmc_ && (process_group_ || factored_exchange_))
 		throw std::runtime_error("TrainStep: mcmc_ is not supported with a process group");
+	if (absgrad_ && (process_group_ || factored_exchange_))
+		throw std::runtime_error("TrainStep: absgrad_ is not supported with a process group");
 	last_reg_losses_ = torch::Tensor();
+	last_absgrad_ = torch::Tensor();
 	auto& g = gaussians_;
 	if (optimize_exposure_ && !kf->exposure_.defined())   // the identity at first use
 		kf->exposure_ = torch::eye(3, 4, g->xyz_.options().requires_grad(false));
@@ -542,6 +553,9 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	// the densification statistics of this view (:714-719) are added by the backward kernel that holds dL_dmean2D in
 	// registers
 	if (iteration_ < o.densify_until_iter_) ext.view_stats_ = {g->xyz_gradient_accum_, g->denom_, g->max_radii2D_};
+	// AbsGS: the statistics accumulate the norm of the absolute pair (only they read it)
+	if (absgrad_ && !ext.view_stats_.empty())
+		ext.absgrad_ = last_absgrad_ = torch::empty({g->xyz_.size(0), 2}, g->xyz_.options().requires_grad(false));
 	g->in_lazy_step_ = lazy;
 	// (with the depth loss: the same render with the depth and alpha maps appended, GaussianRenderer::renderWithDepth)
 	auto pkg = use_depth ? GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, g, pipe, background_,
@@ -768,12 +782,14 @@ void TrainStep::finishBegin()
 		if (densifyDue()) {
 			const int size_threshold = iteration_ > prune_big_point_after_iter_ ? 20 : 0;   // src/gaussian_mapper.cpp:723
 			g->zeroGrad();   // shapes change; this step's update is skipped
+			last_absgrad_ = torch::Tensor();   // (its rows are those of the model before the rebuild)
 			if (mcmc_) {
 				last_mcmc_counts_ = g->relocateDead(mcmc_min_opacity_, generator_);
 				g->addNew(mcmc_cap_max_, generator_, mcmc_min_opacity_);
 			} else {
-				last_densify_ = g->densifyAndPrune(o.densify_grad_threshold_, densify_min_opacity_, cameras_extent_, size_threshold,
-				                                   generator_);
+				// (AbsGS: the accumulator holds the absolute statistic, which has its own threshold)
+				const float max_grad = absgrad_ ? densify_abs_grad_threshold_ : o.densify_grad_threshold_;
+				last_densify_ = g->densifyAndPrune(max_grad, densify_min_opacity_, cameras_extent_, size_threshold, generator_);
 			}
 		}
 		if (!mcmc_ && o.opacity_reset_interval_ && iteration_ % o.opacity_reset_interval_ == 0) g->resetOpacity();

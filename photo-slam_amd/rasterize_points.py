@@ -228,7 +228,7 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                                    geomBuffer, R, binningBuffer, imageBuffer, raw_params=0, dL_dcolor_view=None, sh_adam=None,
                                    view_stats=None, geom_adam=None, training_outputs_only=False, packed_view=None,
                                    dL_ddepth=None, dL_dalpha=None, pose_grad=False, workspace=None, antialiasing=False,
-                                   geom_reg=None):
+                                   geom_reg=None, absgrad=None):
     """dL_dcolor_view (extension, default None = reference contract): a [P,3] float tensor that receives the clamp-masked
     colour gradient; dL_dsh is then NOT computed and None is returned in its place (view-factored gradient exchange,
     shGradFromViews below).
@@ -258,7 +258,11 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
     the pass, before they are returned or consumed by geom_adam.  The weights are per Gaussian (the caller normalises them, e.g. by
     lastVisibleCount()); loss: a contiguous float32 [3] tensor on the device of means3D that receives the three loss values (its
     scratch comes from `workspace`, or is allocated per call), None = they are not formed.  Not together with dL_dcolor_view or
-    pose_grad.  The return tuple is the same."""
+    pose_grad.  The return tuple is the same.
+    absgrad (extension, default None): a contiguous float32 [P, 2] tensor on the device of means3D that receives the absolute
+    screen-space gradients (gsr_backward_args.dL_dmean2D_abs: per Gaussian the sums over its pixels of |d/dmean2D.x| and
+    |d/dmean2D.y| of each pixel's own term, AbsGS / gsplat's absgrad); every row is written.  With view_stats the statistics then
+    accumulate the norm of this pair instead of |dL_dmeans2D.xy|.  Not together with dL_dcolor_view.  The return tuple is the same."""
     lib = _lib()
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
@@ -292,6 +296,10 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                      not dL_dcolor_view.is_contiguous() or dL_dcolor_view.device != dev):
         raise RuntimeError("dL_dcolor_view must be a contiguous float32 (num_points, 3) tensor on the device of means3D")
     dL_dsh = None if factored or sh_adam is not None else torch.empty((P, M, 3), **opts)
+    if absgrad is not None:
+        # (together with dL_dcolor_view the library refuses the call: GSR_ERR_UNSUPPORTED, a capi.GsrError)
+        if absgrad.shape != (P, 2) or absgrad.dtype != torch.float32 or not absgrad.is_contiguous() or absgrad.device != dev:
+            raise RuntimeError("absgrad must be a contiguous float32 (num_points, 2) tensor on the device of means3D")
     if pose_grad:
         if factored:
             raise RuntimeError("pose_grad is not available through the view-factored exchange (dL_dcolor_view)")
@@ -336,6 +344,7 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
         a.dL_dcolor_view = dL_dcolor_view.data_ptr() if factored else None
         a.dL_ddepth = _image_arg(dL_ddepth, H, W, dev, "dL_ddepth")
         a.dL_dalpha = _image_arg(dL_dalpha, H, W, dev, "dL_dalpha")
+        a.dL_dmean2D_abs = absgrad.data_ptr() if absgrad is not None else None
         if packed_view is not None:
             # (message, capacity_rows): a message packViewPlan() prepared -- backward writes its rows and header (gsr_backward_args.packed_view)
             msg, cap = packed_view

@@ -266,6 +266,13 @@ class TrainStep:
         self.scale_reg_ = 0.0
         self.isotropic_reg_ = 0.0
         self.last_reg_losses = None
+        # Densification by absolute screen-space gradients (AbsGS; gsplat's absgrad): the backward pass sums |d/dmean2D| per pixel
+        # before the reduction over a Gaussian's pixels (gsr_backward_args.dL_dmean2D_abs), the fused statistics accumulate the norm
+        # of those sums, and densifyAndPrune compares their mean with densify_abs_grad_threshold_ instead of the model's
+        # densify_grad_threshold_.  0.0008 is gsplat's recommended value with absgrad: a default for the caller to override, not
+        # a tuned number.  Off = the signed statistic and threshold of the reference.
+        self.absgrad_ = False
+        self.densify_abs_grad_threshold_ = 0.0008
         # Fixed-budget maps (3DGS-MCMC, the other half of opacity_reg_ / scale_reg_): with mcmc_ on and densify set, the iterations
         # that rebuild today run relocateDead + addNew instead of densifyAndPrune -- the count grows by 5 % per event to exactly
         # mcmc_cap_max_ and then stays, no tensor is rebuilt on a relocation and the opacity is never reset -- and every step adds
@@ -485,6 +492,8 @@ class TrainStep:
                             lambda_isotropic=float(self.isotropic_reg_),
                             loss=torch.zeros(3, dtype=torch.float32, device=g.xyz_.device) if sync_loss else None)
         self.last_reg_losses = None
+        if self.absgrad_ and self.world_size_ > 1:
+            raise RuntimeError("TrainStep: absgrad_ is not supported with a process group")
         self.iteration_ += 1
         it = self.iteration_
         g.updateLearningRate(it if position_lr_step is None else min(int(position_lr_step), opt.position_lr_max_steps_))   # :661-674
@@ -532,7 +541,8 @@ class TrainStep:
                 sh_grad_view=sh_view, sh_adam=fwd_adam, view_stats=view_stats, geom_adam=geom_adam,
                 training_outputs_only=True,   # the statistics are fused (or over): nobody reads the viewspace gradient
                 cull_empty_tiles=self.cull_empty_tiles_, workspace=self.workspace_ if self.persistent_workspace_ else None,
-                render_depth=use_depth, antialiasing=self.antialiasing_, geom_reg=geom_reg)
+                render_depth=use_depth, antialiasing=self.antialiasing_, geom_reg=geom_reg,
+                absgrad=bool(self.absgrad_) and view_stats is not None)   # (only the statistics read it)
             rendered_image, viewspace_point_tensor, visibility_filter, radii = out[:4]
         finally:
             g._in_lazy_step = False
@@ -584,7 +594,8 @@ class TrainStep:
                             self.last_mcmc_counts_ = g.relocateDead(self.mcmc_min_opacity_, generator=self.generator_)
                             g.addNew(self.mcmc_cap_max_, generator=self.generator_, min_opacity=self.mcmc_min_opacity_)
                         else:
-                            self.last_densify_ = g.densifyAndPrune(opt.densify_grad_threshold_, self.densify_min_opacity_,
+                            max_grad = self.densify_abs_grad_threshold_ if self.absgrad_ else opt.densify_grad_threshold_
+                            self.last_densify_ = g.densifyAndPrune(max_grad, self.densify_min_opacity_,
                                                                    self.cameras_extent_, size_threshold,
                                                                    generator=self.generator_)
                     if not self.mcmc_ and opt.opacity_reset_interval_ and it % opt.opacity_reset_interval_ == 0:      # :732-735
