@@ -719,6 +719,83 @@ int gsr_mcmc_relocate(const gsr_mcmc_relocate_args* args, char* scratch, int* co
 int gsr_mcmc_add_noise(int P, float* xyz, const float* opacity, const float* scaling, const float* rotation, const float* z,
                        float noise_scale, void* stream);
 
+/* ---- seeding Gaussians from an RGB-D frame where the map does not explain it (SplaTAM's add_new_gaussians, MonoGS's
+ * unexplored-region insertion) ----
+ * gsr_seed_select compares the alpha and depth maps of a forward-only render of the current map (gsr_forward_args.out_alpha /
+ * out_depth) with the sensor depth, ranks the unexplained pixels and leaves the plan in scratch; the caller reads counts[0] ONCE,
+ * makes room, and gsr_seed_emit back-projects the planned pixels and writes them as rows [P, P + n_emit) of the five raw parameter
+ * tensors, IN PLACE.  No host synchronisation inside, no atomics on global memory, no floating-point sum: the same inputs give
+ * the same bits on every run, and every decision is an fp32 comparison that numpy restates exactly.
+ *
+ * Selection (pixel p = v * width + u, all values fp32; a = alpha[p], d = depth[p], both 0 when the maps are NULL; g = gt_depth[p]):
+ *   valid     = min_depth < g && g < max_depth                      (the rule of gsr_depth_l1_loss: NaN, inf and 0 fail it)
+ *   candidate = u % stride == offset_x && v % stride == offset_y
+ *   unseen    = a < alpha_threshold
+ *   e         = |g - d|
+ *   T         = max(depth_error_abs, depth_error_median_factor * median)   (one fp32 product, one fp32 max); the factor 0 leaves
+ *               T = depth_error_abs and no median is formed; both 0 switch the depth rule off
+ *   in front  = d > g && e > T                                      (the map puts a surface in front of the measured one)
+ *   selected  = candidate && valid && (unseen || in front)
+ * Median: the exact LOWER median of e over ALL valid pixels (candidates or not), the element of ascending rank (n_valid - 1) / 2.
+ *   Non-negative floats order like their bit patterns: a radix select, four passes of eight bits over per-workgroup histograms
+ *   (integer counts, summed per bin in workgroup order) -- no sort, no host read.
+ * Order: the selected pixels are ranked in row-major pixel order (block scan of the per-thread counts, an exclusive scan of the
+ *   block totals); r below is that rank.
+ * Thinning (n_emit < n_selected): the selected pixel of rank r is written iff floor((r+1) n_emit / n_selected) > floor(r n_emit /
+ *   n_selected) (uint64), to row P + floor(r n_emit / n_selected) -- an even thinning over the image, not a truncation of its top.
+ *   Row P + j therefore holds the pixel of rank ceil((j+1) n_selected / n_emit) - 1.
+ * A written row, z = gt_depth[p]:
+ *   p_c      = ((u - cx) * z / fx, (v - cy) * z / fy, z)            (the operation order of gsr_reproject_depth_pinhole)
+ *   xyz      = R^T (p_c - t), R[r][c] = viewmatrix[4c+r], t[r] = viewmatrix[12+r]   (world -> camera, rigid)
+ *   scaling  = logf(scale_factor * stride * z / (0.5f * (fx + fy))) three times: the pixel's footprint at its depth (SplaTAM's
+ *              isotropic rule; no kNN -- the spacing of a pixel grid is known)
+ *   rotation = (1, 0, 0, 0);   opacity = logit(init_opacity), formed on the host in double and rounded once
+ *   SH row   = ((c - 0.5f) / 0.28209479177387814f for the three channels c of image at p, then zeros); image NULL: all zeros
+ *   the ten moment rows 0, exist_since_iter = iteration, the three statistics 0, out_pixel = p.
+ *   Nothing outside rows [P, P + n_emit) is touched. */
+typedef struct gsr_seed_select_args {
+	int width, height;
+	const float* alpha;      /* [H,W] out_alpha of a render of the current map; NULL = no map yet: 0 everywhere */
+	const float* depth;      /* [H,W] out_depth (sum z alpha T, NOT normalised); NULL together with alpha */
+	const float* gt_depth;   /* [H,W] sensor depth */
+	float min_depth, max_depth;
+	float alpha_threshold;           /* SplaTAM 0.5 */
+	float depth_error_abs;
+	float depth_error_median_factor; /* SplaTAM 50 */
+	int stride, offset_x, offset_y;  /* stride >= 1, offsets in [0, stride) */
+} gsr_seed_select_args;
+size_t gsr_seed_scratch_bytes(int width, int height);
+/* counts: DEVICE int[8], written on the stream: [0] selected, [1] of them by the unseen rule, [2] by the depth rule alone, [3] valid
+ * pixels, [4] the bits of the median (0 if unused or no valid pixel), the rest 0.  scratch: gsr_seed_scratch_bytes(width, height)
+ * device bytes; it holds the plan and must reach gsr_seed_emit unchanged.  The three maps are read with 16-byte loads when all
+ * their bases are 16-byte aligned, with 4-byte loads otherwise.  width * height == 0 writes zeros to counts and nothing else;
+ * stride < 1, an offset outside [0, stride), alpha and depth not both NULL or both set: GSR_ERR_INVALID_ARG. */
+int gsr_seed_select(const gsr_seed_select_args* args, char* scratch, int* counts, void* stream);
+
+typedef struct gsr_seed_emit_args {
+	int width, height, stride;   /* as passed to gsr_seed_select */
+	int n_selected, n_emit;      /* counts[0] read back; 0 <= n_emit <= n_selected rows are written */
+	int P;                       /* rows [P, P + n_emit) of every array below are the destinations (the caller guarantees the room) */
+	int features_row_floats;     /* 3 * M of the [.,M,3] SH tensor */
+	const float* gt_depth;
+	const float* image;          /* [3,H,W] or NULL (DC = 0) */
+	const float* viewmatrix;     /* DEVICE [16], element (r,c) at [4c+r], world -> camera, rigid: the one gsr_forward takes */
+	float fx, fy, cx, cy;
+	float scale_factor, init_opacity;   /* init_opacity in (0, 1) */
+	/* index 0..4 = xyz [.,3], features [.,M,3], opacity [.,1], scaling [.,3], rotation [.,4] (the raw parameters); the moments may
+	 * be NULL, all ten together, when no optimizer state exists */
+	float* param[5];
+	float* exp_avg[5];
+	float* exp_avg_sq[5];
+	int* exist_since_iter;       /* optional [.] int32 */
+	int iteration;
+	float* stats[3];             /* optional xyz_gradient_accum, denom, max_radii2D ([.] each); NULL = skip */
+	int* out_pixel;              /* optional [n_emit]: v * width + u of every written row */
+} gsr_seed_emit_args;
+/* width * height == 0 or n_emit == 0 writes nothing and returns GSR_OK.  stride < 1, init_opacity outside (0, 1), n_emit > n_selected:
+ * GSR_ERR_INVALID_ARG. */
+int gsr_seed_emit(const gsr_seed_emit_args* args, const char* scratch, void* stream);
+
 /* ---- Photo-SLAM's point-cloud kernels ----
  * transformPoints (src/operate_points.cu:73-93): out = M[:3,:4] * (p, 1), M = transformmatrix[16] with
  * element (r,c) at [4c+r] (transformPoint4x3). */

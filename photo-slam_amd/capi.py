@@ -146,6 +146,23 @@ class McmcRelocateArgs(C.Structure):
                 ("draws", C.c_void_p), ("exist_since_iter", C.c_void_p), ("stats", C.c_void_p * 3), ("out_weights", C.c_void_p)]
 
 
+class SeedSelectArgs(C.Structure):
+    """gsr_seed_select_args"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("alpha", C.c_void_p), ("depth", C.c_void_p), ("gt_depth", C.c_void_p),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("alpha_threshold", C.c_float), ("depth_error_abs", C.c_float),
+                ("depth_error_median_factor", C.c_float), ("stride", C.c_int), ("offset_x", C.c_int), ("offset_y", C.c_int)]
+
+
+class SeedEmitArgs(C.Structure):
+    """gsr_seed_emit_args"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("stride", C.c_int), ("n_selected", C.c_int), ("n_emit", C.c_int),
+                ("P", C.c_int), ("features_row_floats", C.c_int), ("gt_depth", C.c_void_p), ("image", C.c_void_p),
+                ("viewmatrix", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("scale_factor", C.c_float), ("init_opacity", C.c_float), ("param", C.c_void_p * 5), ("exp_avg", C.c_void_p * 5),
+                ("exp_avg_sq", C.c_void_p * 5), ("exist_since_iter", C.c_void_p), ("iteration", C.c_int), ("stats", C.c_void_p * 3),
+                ("out_pixel", C.c_void_p)]
+
+
 RAW_OPACITY, RAW_SCALING, RAW_ROTATION = 1, 2, 4   # GSR_RAW_* of include/gsr.h
 CULL_EMPTY_TILES, FORWARD_ONLY = 8, 128             # GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY
 ANTIALIAS = 256                                     # GSR_ANTIALIAS: forward AND backward (the same value in both calls)
@@ -167,6 +184,7 @@ EXPORTED_SYMBOLS = [
     "gsr_loss_exposure_scratch_bytes", "gsr_l1_ssim_loss_exposure", "gsr_apply_exposure",
     "gsr_geom_reg_scratch_bytes",
     "gsr_mcmc_scratch_bytes", "gsr_mcmc_relocate", "gsr_mcmc_add_noise",
+    "gsr_seed_scratch_bytes", "gsr_seed_select", "gsr_seed_emit",
 ]
 
 _libs = {}
@@ -259,6 +277,12 @@ def load(path=None):
     L.gsr_mcmc_relocate.argtypes = [C.POINTER(McmcRelocateArgs), vp, vp, vp]
     L.gsr_mcmc_add_noise.restype = i32
     L.gsr_mcmc_add_noise.argtypes = [i32, vp, vp, vp, vp, vp, f32, vp]
+    L.gsr_seed_scratch_bytes.restype = sz
+    L.gsr_seed_scratch_bytes.argtypes = [i32, i32]
+    L.gsr_seed_select.restype = i32
+    L.gsr_seed_select.argtypes = [C.POINTER(SeedSelectArgs), vp, vp, vp]
+    L.gsr_seed_emit.restype = i32
+    L.gsr_seed_emit.argtypes = [C.POINTER(SeedEmitArgs), vp, vp]
     L.gsr_transform_points.restype = i32
     L.gsr_transform_points.argtypes = [i32, vp, vp, vp, vp]
     L.gsr_scale_transform_points.restype = i32

@@ -316,8 +316,13 @@ class GaussianModel:
 
     def _append_rows(self, new_rows, iteration):
         """densificationPostfix (:644-712) as an append into the arena of the rebuilds."""
+        self._grow_rows(new_rows["xyz_"].shape[0], iteration, new_rows)
+
+    def _grow_rows(self, n, iteration, new_rows=None):
+        """The append itself: n rows behind the live ones in the arena -- parameters, zero moments, exist_since_iter = iteration, all
+        three statistics reset.  new_rows None: the parameter rows are left for a kernel to write (seedFromDepth)."""
         _ = self.features_           # lazy SH Adam: every row up to date before the tensor is re-seated
-        P, n = self.xyz_.shape[0], new_rows["xyz_"].shape[0]
+        P = self.xyz_.shape[0]
         dev = self.xyz_.device
         arena = getattr(self, "_arena", None)
         live = arena is not None and arena["capacity"] >= P + n and all(
@@ -339,7 +344,8 @@ class GaussianModel:
                 if have:
                     bufs[1][:P].copy_(m)
                     bufs[2][:P].copy_(v)
-            bufs[0][P:].copy_(new_rows[name])
+            if new_rows is not None:
+                bufs[0][P:].copy_(new_rows[name])
             bufs[1][P:].zero_()
             bufs[2][P:].zero_()
             if not have:
@@ -747,6 +753,78 @@ class GaussianModel:
             capi.check(lib, lib.gsr_mcmc_add_noise(P, self.xyz_.data_ptr(), self.opacity_.data_ptr(), self.scaling_.data_ptr(),
                                                    self.rotation_.data_ptr(), z.data_ptr(), float(noise_scale),
                                                    rp._stream_ptr(self.xyz_)), "gsr_mcmc_add_noise")
+
+    # ------------------------------------------------------------------ seeding from an RGB-D frame (include/gsr.h: gsr_seed_*)
+    def seedFromDepth(self, gt_depth, gt_image, alpha, depth, viewmatrix, fx, fy, cx, cy, iteration, max_new, min_depth=0.0,
+                      max_depth=float("inf"), alpha_threshold=0.5, depth_error_abs=0.0, depth_median_factor=50.0, stride=1,
+                      offset_x=0, offset_y=0, scale_factor=1.0, init_opacity=0.5, want_pixels=False):
+        """SplaTAM's add_new_gaussians / MonoGS's unexplored-region insertion: the pixels of the sensor depth map gt_depth [H,W] that
+        the map does not explain -- alpha < alpha_threshold in the map's own render, or the render puts a surface in front of the
+        measured one by more than max(depth_error_abs, depth_median_factor * the median depth error) -- are back-projected through
+        the camera (viewmatrix: world_view_transform_; fx, fy, cx, cy in pixels) and appended as Gaussians of one pixel's footprint,
+        coloured from gt_image [3,H,W] (None: DC 0).  alpha / depth: out_alpha / out_depth of a forward-only render of the current
+        map, or None for a map that does not exist yet.  gsr_seed_select, ONE read of the counts, room through the arena path of
+        increasePcd / addNew, gsr_seed_emit; at most max_new rows, thinned evenly over the image.  sparse_points_* are not touched.
+        Returns the number of rows appended; last_seed_counts_ holds the counts read ([selected, by the unseen rule, by the depth
+        rule alone, valid pixels, the median's bits]) and, with want_pixels, last_seed_pixels_ the pixel v * W + u of every new row."""
+        lib = rp._lib()
+        dev = gt_depth.device
+        H, W = int(gt_depth.shape[-2]), int(gt_depth.shape[-1])
+        with torch.no_grad():
+            if getattr(self, "xyz_", None) is None:   # an empty model: the first frame of a session initialises the map
+                M = (self.max_sh_degree_ + 1) ** 2
+                leaf = lambda *shape: torch.zeros(shape, device=dev).requires_grad_(True)
+                self.xyz_, self.features_, self.opacity_ = leaf(0, 3), leaf(0, M, 3), leaf(0, 1)
+                self.scaling_, self.rotation_ = leaf(0, 3), leaf(0, 4)
+                self.max_radii2D_ = torch.zeros(0, device=dev)
+                self.xyz_gradient_accum_, self.denom_ = torch.zeros((0, 1), device=dev), torch.zeros((0, 1), device=dev)
+                self.exist_since_iter_ = torch.zeros(0, dtype=torch.int32, device=dev)
+            f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
+            gt_depth, gt_image, alpha, depth, viewmatrix = f32(gt_depth), f32(gt_image), f32(alpha), f32(depth), f32(viewmatrix)
+            stream = rp._stream_ptr(gt_depth)
+            a = capi.SeedSelectArgs()
+            a.width, a.height = W, H
+            a.alpha, a.depth = (alpha.data_ptr(), depth.data_ptr()) if alpha is not None else (None, None)
+            a.gt_depth = gt_depth.data_ptr()
+            a.min_depth, a.max_depth, a.alpha_threshold = float(min_depth), float(max_depth), float(alpha_threshold)
+            a.depth_error_abs, a.depth_error_median_factor = float(depth_error_abs), float(depth_median_factor)
+            a.stride, a.offset_x, a.offset_y = int(stride), int(offset_x), int(offset_y)
+            nbytes = lib.gsr_seed_scratch_bytes(W, H)
+            scratch = getattr(self, "_seed_scratch", None)
+            if scratch is None or scratch.numel() < nbytes or scratch.device != dev:
+                scratch = self._seed_scratch = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+            counts = torch.empty(8, dtype=torch.int32, device=dev)
+            capi.check(lib, lib.gsr_seed_select(C.byref(a), scratch.data_ptr(), counts.data_ptr(), stream), "gsr_seed_select")
+            self.last_seed_counts_ = counts.tolist()[:5]   # the one host read
+            self.last_seed_pixels_ = None
+            n_selected = self.last_seed_counts_[0]
+            n = min(n_selected, max(int(max_new), 0))
+            if n <= 0:
+                return 0
+            P = self.xyz_.shape[0]
+            self._grow_rows(n, int(iteration))
+            e = capi.SeedEmitArgs()
+            e.width, e.height, e.stride, e.n_selected, e.n_emit, e.P = W, H, int(stride), n_selected, n, P
+            e.features_row_floats = int(self._features.shape[1] * self._features.shape[2])
+            e.gt_depth, e.image = gt_depth.data_ptr(), (gt_image.data_ptr() if gt_image is not None else None)
+            e.viewmatrix = viewmatrix.data_ptr()
+            e.fx, e.fy, e.cx, e.cy = float(fx), float(fy), float(cx), float(cy)
+            e.scale_factor, e.init_opacity = float(scale_factor), float(init_opacity)
+            opt = self.optimizer_
+            for i, p in enumerate(self.params_raw()):
+                assert p.is_contiguous()
+                e.param[i] = p.data_ptr()
+                if opt is not None and id(p) in opt.state:
+                    st = opt.state[id(p)]
+                    e.exp_avg[i], e.exp_avg_sq[i] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+            e.exist_since_iter, e.iteration = self.exist_since_iter_.data_ptr(), int(iteration)
+            for k, t in enumerate((self.xyz_gradient_accum_, self.denom_, self.max_radii2D_)):
+                e.stats[k] = t.data_ptr()
+            if want_pixels:
+                self.last_seed_pixels_ = torch.empty(n, dtype=torch.int32, device=dev)
+                e.out_pixel = self.last_seed_pixels_.data_ptr()
+            capi.check(lib, lib.gsr_seed_emit(C.byref(e), scratch.data_ptr(), stream), "gsr_seed_emit")
+        return n
 
     def resetOpacity(self, clamp_to=None):
         """src/gaussian_model.cpp:556-565 exactly as shipped: opacities_new = inverse_sigmoid(min(sigmoid(o), ones_like(sigmoid(o)

@@ -112,6 +112,28 @@ public:
 	// addPositionNoise: xyz += Sigma (z sigmoid(100 ((1 - o) - 0.995)) noise_scale), z ~ N(0, 1) from the generator, in place
 	void addPositionNoise(float noise_scale, c10::optional<at::Generator> generator = c10::nullopt);
 
+	// Seeding from an RGB-D frame (include/gsr.h: gsr_seed_select / gsr_seed_emit; SplaTAM's add_new_gaussians, MonoGS's
+	// unexplored-region insertion): the pixels of the sensor depth map gt_depth [H,W] that the map does not explain -- alpha <
+	// alpha_threshold_ in the map's own render, or the render puts a surface in front of the measured one by more than
+	// max(depth_error_abs_, depth_median_factor_ * the median depth error) -- are back-projected through the camera (viewmatrix:
+	// world_view_transform_; fx, fy, cx, cy in pixels) and appended as Gaussians of one pixel's footprint, coloured from gt_image
+	// [3,H,W] (undefined: DC 0).  alpha / depth: out_alpha / out_depth of a forward-only render of the current map, or undefined
+	// for a map that does not exist yet.  gsr_seed_select, ONE read of the counts, room through the arena path of increasePcd /
+	// addNew, gsr_seed_emit; at most max_new rows, thinned evenly over the image.  sparse_points_* are not touched.  Returns the
+	// number of rows appended; last_seed_counts_ holds the counts read (selected, by the unseen rule, by the depth rule alone,
+	// valid pixels, the median's bits) and, with want_pixels_, last_seed_pixels_ the pixel v * W + u of every new row.
+	struct SeedOptions {
+		float min_depth_ = 0.0f, max_depth_ = std::numeric_limits<float>::infinity();
+		float alpha_threshold_ = 0.5f, depth_error_abs_ = 0.0f, depth_median_factor_ = 50.0f;
+		int stride_ = 1, offset_x_ = 0, offset_y_ = 0;
+		float scale_factor_ = 1.0f, init_opacity_ = 0.5f;
+		bool want_pixels_ = false;
+	};
+	int64_t seedFromDepth(torch::Tensor gt_depth, torch::Tensor gt_image, torch::Tensor alpha, torch::Tensor depth, torch::Tensor viewmatrix,
+	                      float fx, float fy, float cx, float cy, int iteration, int64_t max_new, const SeedOptions& options);
+	std::vector<int64_t> last_seed_counts_;
+	torch::Tensor last_seed_pixels_;
+
 	// activations, src/gaussian_model.cpp:48-71
 	torch::Tensor getXYZ() { return xyz_; }
 	torch::Tensor getScalingActivation() { return torch::exp(scaling_); }
@@ -207,7 +229,14 @@ private:
 		std::array<torch::Tensor, 3> stats[2];
 		torch::Tensor exist[2];   // exist_since_iter_ ([capacity] int32)
 	} arena_;
-	void appendRows(const std::array<torch::Tensor, 5>& rows, int iteration);   // densificationPostfix as an append into the arena
+public:
+	// densificationPostfix as an append into the arena: what increasePcd and addNew end in (public for the host tests, which hand a
+	// model the rows another one was seeded with)
+	void appendRows(const std::array<torch::Tensor, 5>& rows, int iteration);
+private:
+	// the append itself: n rows behind the live ones -- zero moments, exist_since_iter = iteration, the statistics reset; rows
+	// null: the parameter rows are left for a kernel to write (seedFromDepth)
+	void growRows(int64_t n, int iteration, const std::array<torch::Tensor, 5>* rows);
 public:
 	// The arena keeps two sets of 1.25-1.5x (parameters + moments) resident (~2 kB per Gaussian) so that rebuilds allocate
 	// nothing.  LIFETIME CONTRACT: after a rebuild xyz_, features_, ..., the Adam moments and the statistics are narrow() views
@@ -220,6 +249,7 @@ public:
 private:
 	torch::Tensor densify_scratch_;
 	torch::Tensor mcmc_scratch_;
+	torch::Tensor seed_scratch_;
 	torch::Tensor mcmcCall(int64_t P, int64_t n_add, const torch::Tensor& draws, float min_opacity);
 };
 
@@ -324,6 +354,19 @@ public:
 	double mcmc_noise_lr_ = 5e5;   // (upstream's noise_lr)
 	float mcmc_min_opacity_ = 0.005f;
 	torch::Tensor last_mcmc_counts_;   // the device counts of the last relocateDead
+	// Seeding from an RGB-D frame: the mapper's "where does the map fail to explain this frame, and what do I put there" step.
+	// seedFromDepth makes one forward-only render of the map with its depth and alpha maps (renderViewWithDepth; none while the
+	// model is empty -- the first frame of a session initialises the map this way) and calls GaussianModel::seedFromDepth with the
+	// seed_* options below (SplaTAM's values), the valid range depth_min_ < gt < depth_max_ of the depth loss and the rasterizer's
+	// own pixel-centre convention fx = W / (2 tanfovx), cx = (W - 1) / 2 (likewise y), so that a seed projects onto the centre of
+	// its pixel.  At most mcmc_cap_max_ - P rows with mcmc_ on, seed_max_new_ otherwise.  Returns the number of rows appended.
+	// Not with a process group: throws.  Nothing calls it by itself.
+	int64_t seedFromDepth(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image, torch::Tensor gt_depth, int iteration,
+	                      bool want_pixels = false);
+	float seed_alpha_threshold_ = 0.5f, seed_depth_median_factor_ = 50.0f, seed_depth_error_abs_ = 0.0f;
+	int seed_stride_ = 1;
+	float seed_scale_factor_ = 1.0f, seed_init_opacity_ = 0.5f;
+	int64_t seed_max_new_ = int64_t(1) << 30;
 	bool optimize_exposure_ = false;
 	float exposure_lr_init_ = 0.01f, exposure_lr_final_ = 0.001f;
 	int exposure_lr_max_steps_ = -1;

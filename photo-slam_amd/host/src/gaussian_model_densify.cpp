@@ -103,8 +103,13 @@ void GaussianModel::increasePcd(torch::Tensor& new_point_cloud, torch::Tensor& n
 // views, only the new rows are written.
 void GaussianModel::appendRows(const std::array<torch::Tensor, 5>& rows, int iteration)
 {
+	growRows(rows[0].size(0), iteration, &rows);
+}
+
+void GaussianModel::growRows(int64_t n, int iteration, const std::array<torch::Tensor, 5>* rows)
+{
 	torch::NoGradGuard ng;
-	const int64_t P = xyz_.size(0), n = rows[0].size(0);
+	const int64_t P = xyz_.size(0);
 	const bool have_state = groups_.size() == 5;
 	bool live = arena_.capacity >= P + n && arena_.params[0][0][0].defined() && arena_.params[0][0][0].device() == xyz_.device();
 	for (int i = 0; live && i < 5; i++) live = paramByIndex(i).data_ptr() == arena_.params[arena_.cur][i][0].data_ptr();
@@ -136,7 +141,7 @@ void GaussianModel::appendRows(const std::array<torch::Tensor, 5>& rows, int ite
 				b[2].narrow(0, 0, P).copy_(old_mom[i][1]);
 			}
 		}
-		b[0].narrow(0, P, n).copy_(rows[i].reshape(b[0].narrow(0, P, n).sizes()));
+		if (rows) b[0].narrow(0, P, n).copy_((*rows)[i].reshape(b[0].narrow(0, P, n).sizes()));
 		b[1].narrow(0, P, n).zero_();
 		b[2].narrow(0, P, n).zero_();
 		if (have_state) replaceParam(i, b[0], b[1], b[2], /*rows_kept=*/keep_lazy);
@@ -538,4 +543,103 @@ void GaussianModel::addPositionNoise(float noise_scale, c10::optional<at::Genera
 	check_gsr(gsr_mcmc_add_noise(static_cast<int>(P), xyz_.data_ptr<float>(), opacity_.data_ptr<float>(), scaling_.data_ptr<float>(),
 	                             rotation_.data_ptr<float>(), z.data_ptr<float>(), noise_scale, hostStream(xyz_)),
 	          "gsr_mcmc_add_noise");
+}
+
+// ---- seeding from an RGB-D frame (csrc/points.hip, include/gsr.h: gsr_seed_select / gsr_seed_emit) -----------------------------
+
+int64_t GaussianModel::seedFromDepth(torch::Tensor gt_depth, torch::Tensor gt_image, torch::Tensor alpha, torch::Tensor depth,
+                                     torch::Tensor viewmatrix, float fx, float fy, float cx, float cy, int iteration, int64_t max_new,
+                                     const SeedOptions& options)
+{
+	torch::NoGradGuard ng;
+	TORCH_CHECK(gt_depth.defined() && gt_depth.dim() >= 2, "seedFromDepth: gt_depth must be an [H,W] map");
+	TORCH_CHECK(alpha.defined() == depth.defined(), "seedFromDepth: the alpha and depth maps come together or not at all");
+	const auto o = gt_depth.options().dtype(torch::kFloat32).requires_grad(false);
+	if (!xyz_.defined()) {   // an empty model: the first frame of a session initialises the map
+		const int64_t M = (max_sh_degree_ + 1) * (max_sh_degree_ + 1);
+		auto leaf = [&](std::vector<int64_t> shape) { return torch::zeros(shape, o).set_requires_grad(true); };
+		xyz_ = leaf({0, 3});
+		features_ = leaf({0, M, 3});
+		opacity_ = leaf({0, 1});
+		scaling_ = leaf({0, 3});
+		rotation_ = leaf({0, 4});
+		max_radii2D_ = torch::zeros({0}, o);
+		xyz_gradient_accum_ = torch::zeros({0, 1}, o);
+		denom_ = torch::zeros({0, 1}, o);
+		exist_since_iter_ = torch::zeros({0}, o.dtype(torch::kInt32));
+	}
+	const int H = static_cast<int>(gt_depth.size(-2)), W = static_cast<int>(gt_depth.size(-1));
+	auto f32 = [&](const torch::Tensor& t) { return t.defined() ? t.detach().to(o).contiguous() : t; };
+	gt_depth = f32(gt_depth);
+	gt_image = f32(gt_image);
+	alpha = f32(alpha);
+	depth = f32(depth);
+	viewmatrix = f32(viewmatrix);
+	void* stream = hostStream(gt_depth);
+	gsr_seed_select_args a{};
+	a.width = W;
+	a.height = H;
+	a.alpha = alpha.defined() ? alpha.data_ptr<float>() : nullptr;
+	a.depth = depth.defined() ? depth.data_ptr<float>() : nullptr;
+	a.gt_depth = gt_depth.data_ptr<float>();
+	a.min_depth = options.min_depth_;
+	a.max_depth = options.max_depth_;
+	a.alpha_threshold = options.alpha_threshold_;
+	a.depth_error_abs = options.depth_error_abs_;
+	a.depth_error_median_factor = options.depth_median_factor_;
+	a.stride = options.stride_;
+	a.offset_x = options.offset_x_;
+	a.offset_y = options.offset_y_;
+	const auto bytes = static_cast<int64_t>(gsr_seed_scratch_bytes(W, H));
+	if (!seed_scratch_.defined() || seed_scratch_.numel() < bytes || seed_scratch_.device() != gt_depth.device())
+		seed_scratch_ = torch::empty({bytes + 256}, o.dtype(torch::kUInt8));
+	char* scratch = reinterpret_cast<char*>(seed_scratch_.data_ptr<uint8_t>());
+	auto counts = torch::empty({8}, o.dtype(torch::kInt32));
+	check_gsr(gsr_seed_select(&a, scratch, counts.data_ptr<int>(), stream), "gsr_seed_select");
+	auto host = counts.cpu();   // the one host read
+	last_seed_counts_.assign(host.data_ptr<int>(), host.data_ptr<int>() + 5);
+	last_seed_pixels_ = torch::Tensor();
+	const int64_t n_selected = last_seed_counts_[0];
+	const int64_t n = std::min<int64_t>(n_selected, std::max<int64_t>(max_new, 0));
+	if (n <= 0) return 0;
+	const int64_t P = xyz_.size(0);
+	growRows(n, iteration, nullptr);
+	gsr_seed_emit_args e{};
+	e.width = W;
+	e.height = H;
+	e.stride = options.stride_;
+	e.n_selected = static_cast<int>(n_selected);
+	e.n_emit = static_cast<int>(n);
+	e.P = static_cast<int>(P);
+	e.features_row_floats = static_cast<int>(features_.size(1) * features_.size(2));
+	e.gt_depth = gt_depth.data_ptr<float>();
+	e.image = gt_image.defined() ? gt_image.data_ptr<float>() : nullptr;
+	e.viewmatrix = viewmatrix.data_ptr<float>();
+	e.fx = fx;
+	e.fy = fy;
+	e.cx = cx;
+	e.cy = cy;
+	e.scale_factor = options.scale_factor_;
+	e.init_opacity = options.init_opacity_;
+	const bool have_state = groups_.size() == 5;
+	for (int i = 0; i < 5; i++) {
+		auto& p = paramByIndex(i);
+		TORCH_CHECK(p.is_contiguous(), "seedFromDepth: the parameter tensors must be contiguous");
+		e.param[i] = p.data_ptr<float>();
+		if (have_state) {
+			e.exp_avg[i] = groups_[i].exp_avg.data_ptr<float>();
+			e.exp_avg_sq[i] = groups_[i].exp_avg_sq.data_ptr<float>();
+		}
+	}
+	e.exist_since_iter = exist_since_iter_.data_ptr<int>();
+	e.iteration = iteration;
+	e.stats[0] = xyz_gradient_accum_.data_ptr<float>();
+	e.stats[1] = denom_.data_ptr<float>();
+	e.stats[2] = max_radii2D_.data_ptr<float>();
+	if (options.want_pixels_) {
+		last_seed_pixels_ = torch::empty({n}, o.dtype(torch::kInt32));
+		e.out_pixel = last_seed_pixels_.data_ptr<int>();
+	}
+	check_gsr(gsr_seed_emit(&e, scratch, stream), "gsr_seed_emit");
+	return n;
 }

@@ -418,6 +418,13 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "mcmc_cap_max") t->mcmc_cap_max_ = (int64_t)v;
 		else if (k == "mcmc_noise_lr") t->mcmc_noise_lr_ = v;
 		else if (k == "mcmc_min_opacity") t->mcmc_min_opacity_ = (float)v;
+		else if (k == "seed_alpha_threshold") t->seed_alpha_threshold_ = (float)v;
+		else if (k == "seed_depth_median_factor") t->seed_depth_median_factor_ = (float)v;
+		else if (k == "seed_depth_error_abs") t->seed_depth_error_abs_ = (float)v;
+		else if (k == "seed_stride") t->seed_stride_ = (int)v;
+		else if (k == "seed_scale_factor") t->seed_scale_factor_ = (float)v;
+		else if (k == "seed_init_opacity") t->seed_init_opacity_ = (float)v;
+		else if (k == "seed_max_new") t->seed_max_new_ = (int64_t)v;
 		else if (k == "depth_loss_weight") t->depth_loss_weight_ = static_cast<float>(v);
 		else if (k == "depth_min") t->depth_min_ = static_cast<float>(v);
 		else if (k == "depth_max") t->depth_max_ = static_cast<float>(v);
@@ -476,6 +483,33 @@ torch::Tensor trainer_last_mcmc_counts(int64_t h)
 {
 	auto t = get(h);
 	return t->last_mcmc_counts_.defined() ? t->last_mcmc_counts_ : torch::empty({0}, t->gaussians_->xyz_.options().dtype(torch::kInt32).requires_grad(false));
+}
+// TrainStep::seedFromDepth (the pixels of the new rows are kept: trainer_last_seed_pixels); GaussianModel::last_seed_counts_ / _pixels_
+int64_t trainer_seed_from_depth(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx, double fovy,
+                                int64_t H, int64_t W, torch::Tensor gt_image, torch::Tensor gt_depth, int64_t iteration)
+{
+	return get(h)->seedFromDepth(make_kf(view, proj, campos, fovx, fovy, H, W), gt_image, gt_depth, (int)iteration, true);
+}
+// GaussianModel::appendRows: the five row tensors join the model as increasePcd's rows do
+void trainer_append_rows(int64_t h, std::vector<torch::Tensor> rows, int64_t iteration)
+{
+	TORCH_CHECK(rows.size() == 5, "trainer_append_rows: xyz, features, opacity, scaling, rotation");
+	get(h)->gaussians_->appendRows({rows[0], rows[1], rows[2], rows[3], rows[4]}, (int)iteration);
+}
+// a trainer around a model that has no tensors yet (no optimizer either): seedFromDepth makes the first Gaussians
+int64_t trainer_create_empty(int64_t sh_degree, torch::Tensor background)
+{
+	auto model = std::make_shared<GaussianModel>((int)sh_degree);
+	model->device_ = background.device();
+	std::lock_guard<std::mutex> lk(g_mu);
+	g_trainers[g_next] = std::make_shared<TrainStep>(model, background);
+	return g_next++;
+}
+std::vector<int64_t> trainer_last_seed_counts(int64_t h) { return get(h)->gaussians_->last_seed_counts_; }
+torch::Tensor trainer_last_seed_pixels(int64_t h)
+{
+	auto g = get(h)->gaussians_;
+	return g->last_seed_pixels_.defined() ? g->last_seed_pixels_ : torch::empty({0}, g->xyz_.options().dtype(torch::kInt32).requires_grad(false));
 }
 torch::Tensor trainer_reorder_along_z_curve(int64_t h) { return get(h)->gaussians_->reorderAlongZCurve(); }
 std::vector<int64_t> trainer_last_densify(int64_t h)
@@ -719,6 +753,11 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("trainer_add_new", &trainer_add_new);
 	m.def("trainer_add_position_noise", &trainer_add_position_noise);
 	m.def("trainer_last_mcmc_counts", &trainer_last_mcmc_counts);
+	m.def("trainer_seed_from_depth", &trainer_seed_from_depth);
+	m.def("trainer_last_seed_counts", &trainer_last_seed_counts);
+	m.def("trainer_append_rows", &trainer_append_rows);
+	m.def("trainer_create_empty", &trainer_create_empty);
+	m.def("trainer_last_seed_pixels", &trainer_last_seed_pixels);
 	m.def("trainer_last_densify", &trainer_last_densify);
 	m.def("trainer_save_ply", &trainer_save_ply);
 	m.def("trainer_create_from_ply", &trainer_create_from_ply);

@@ -298,6 +298,37 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::renderViewWit
 	return std::make_tuple(std::get<0>(pkg), std::get<4>(pkg), std::get<5>(pkg));
 }
 
+int64_t TrainStep::seedFromDepth(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image, torch::Tensor gt_depth,
+                                 int iteration, bool want_pixels)
+{
+	if (process_group_ || factored_exchange_) throw std::runtime_error("TrainStep: seedFromDepth is not supported with a process group");
+	auto& g = gaussians_;
+	const int64_t P = g->xyz_.defined() ? g->xyz_.size(0) : 0;
+	torch::Tensor alpha, depth;
+	if (P > 0) {
+		auto maps = renderViewWithDepth(viewpoint_cam);
+		depth = std::get<1>(maps);
+		alpha = std::get<2>(maps);
+	}
+	const int H = viewpoint_cam->image_height_, W = viewpoint_cam->image_width_;
+	// the rasterizer's own tan(FoV / 2) (GaussianRenderer::render) and its pixel-centre convention
+	const float tanfovx = std::tan(viewpoint_cam->FoVx_ * 0.5f), tanfovy = std::tan(viewpoint_cam->FoVy_ * 0.5f);
+	GaussianModel::SeedOptions o;
+	o.min_depth_ = depth_min_;
+	o.max_depth_ = depth_max_;
+	o.alpha_threshold_ = seed_alpha_threshold_;
+	o.depth_error_abs_ = seed_depth_error_abs_;
+	o.depth_median_factor_ = seed_depth_median_factor_;
+	o.stride_ = seed_stride_;
+	o.scale_factor_ = seed_scale_factor_;
+	o.init_opacity_ = seed_init_opacity_;
+	o.want_pixels_ = want_pixels;
+	const int64_t max_new = mcmc_ ? mcmc_cap_max_ - P : seed_max_new_;
+	return g->seedFromDepth(gt_depth, gt_image, alpha, depth, viewpoint_cam->world_view_transform_,
+	                        static_cast<float>(W / (2.0 * static_cast<double>(tanfovx))), static_cast<float>(H / (2.0 * static_cast<double>(tanfovy))),
+	                        static_cast<float>((W - 1) / 2.0), static_cast<float>((H - 1) / 2.0), iteration, max_new, o);
+}
+
 namespace {
 // the frozen map of refinePose: exactly the members GaussianRenderer::render touches, detached tensors
 struct FrozenModel {

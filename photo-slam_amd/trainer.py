@@ -228,7 +228,8 @@ class TrainStep:
         self.densify_, self.densify_min_opacity_ = densify, densify_min_opacity
         self.prune_big_point_after_iter_ = prune_big_point_after_iter
         # every rank draws the same split samples: identical replicas without a broadcast
-        self.generator_ = torch.Generator(device=gaussians.xyz_.device).manual_seed(seed)
+        # (a model without a single Gaussian yet -- seedFromDepth makes the first ones -- names its device itself)
+        self.generator_ = torch.Generator(device=gaussians.xyz_.device if getattr(gaussians, "xyz_", None) is not None else gaussians.device_).manual_seed(seed)
         self.last_densify_ = None
         self.iteration_ = 0
         self.world_size_ = world_size
@@ -282,6 +283,16 @@ class TrainStep:
         self.mcmc_noise_lr_ = 5e5       # (upstream's noise_lr)
         self.mcmc_min_opacity_ = 0.005
         self.last_mcmc_counts_ = None   # the device counts of the last relocateDead
+        # Seeding from an RGB-D frame (seedFromDepth; GaussianModel.seedFromDepth, include/gsr.h: gsr_seed_*): SplaTAM's values.
+        # seed_max_new_ bounds one call's rows when mcmc_ is off (with mcmc_ on the bound is mcmc_cap_max_ - P).  Nothing calls
+        # seedFromDepth by itself.
+        self.seed_alpha_threshold_ = 0.5
+        self.seed_depth_median_factor_ = 50.0
+        self.seed_depth_error_abs_ = 0.0
+        self.seed_stride_ = 1
+        self.seed_scale_factor_ = 1.0
+        self.seed_init_opacity_ = 0.5
+        self.seed_max_new_ = 1 << 30
         self.optimize_exposure_ = False
         self.exposure_lr_init_ = 0.01
         self.exposure_lr_final_ = 0.001
@@ -377,6 +388,29 @@ class TrainStep:
             with torch.no_grad():
                 self.gaussians_.prunePoints(mask)
         return n
+
+    def seedFromDepth(self, viewpoint_cam, gt_image, gt_depth, iteration, want_pixels=False):
+        """The mapper's "where does the map fail to explain this frame, and what do I put there" step (SplaTAM's add_new_gaussians,
+        MonoGS's unexplored-region insertion): one forward-only render of the map with its depth and alpha maps (render_view; none
+        while the model is empty -- the first frame of a session initialises the map this way), then GaussianModel.seedFromDepth
+        with the seed_* options, the valid range depth_min_ < gt < depth_max_ of the depth loss, and the rasterizer's own
+        pixel-centre convention fx = W / (2 tanfovx), cx = (W - 1) / 2 (likewise y), so that a seed projects onto the centre of
+        its pixel.  At most mcmc_cap_max_ - P rows with mcmc_ on, seed_max_new_ otherwise.  Returns the number of rows appended."""
+        if self.world_size_ > 1:
+            raise RuntimeError("TrainStep: seedFromDepth is not supported with a process group")
+        g = self.gaussians_
+        P = 0 if getattr(g, "xyz_", None) is None else int(g.xyz_.shape[0])
+        alpha = depth = None
+        if P > 0:
+            _, depth, alpha = self.render_view(viewpoint_cam, with_depth=True)
+        H, W = int(viewpoint_cam.image_height_), int(viewpoint_cam.image_width_)
+        max_new = (int(self.mcmc_cap_max_) - P) if self.mcmc_ else int(self.seed_max_new_)
+        return g.seedFromDepth(gt_depth, gt_image, alpha, depth, viewpoint_cam.world_view_transform_,
+                               W / (2.0 * viewpoint_cam.tanfovx_), H / (2.0 * viewpoint_cam.tanfovy_), (W - 1) / 2.0, (H - 1) / 2.0,
+                               iteration, max_new, min_depth=self.depth_min_, max_depth=self.depth_max_,
+                               alpha_threshold=self.seed_alpha_threshold_, depth_error_abs=self.seed_depth_error_abs_,
+                               depth_median_factor=self.seed_depth_median_factor_, stride=self.seed_stride_,
+                               scale_factor=self.seed_scale_factor_, init_opacity=self.seed_init_opacity_, want_pixels=want_pixels)
 
     @staticmethod
     def covisibility(n_touched_a, n_touched_b):
