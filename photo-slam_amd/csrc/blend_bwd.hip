@@ -62,6 +62,7 @@
 //
 #include "blend.h"
 #include "kernels.h"
+#include "variant.h"
 
 namespace gsr {
 
@@ -80,6 +81,8 @@ struct BwdPixel {
 	uint32_t last;
 };
 
+// the instantiations that exist (variant.h): half tiles or quads, 2 x 2 x 2 = 8
+constexpr bool blend_bwd_variant(int WAVES, bool DEPTH, bool ABS) { return WAVES == 2 || WAVES == 4; }
 template <int WAVES, bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(64 * WAVES)
 blend_bwd_kernel(const BlendBwdParams p)
@@ -425,23 +428,15 @@ int launch_blend_bwd(const BlendBwdParams& p, hipStream_t stream)
 {
 	const bool depth = p.dL_ddepth || p.dL_dalpha;
 	if (depth && !p.depth) return GSR_ERR_INVALID_ARG;
-	if (p.abs_sums) {
-		if (p.half_tiles && depth)
-			GSR_LAUNCH((blend_bwd_kernel<2, true, true>), tile_grid(p.deal), 128, stream, p);
-		else if (p.half_tiles)
-			GSR_LAUNCH((blend_bwd_kernel<2, false, true>), tile_grid(p.deal), 128, stream, p);
-		else if (depth)
-			GSR_LAUNCH((blend_bwd_kernel<4, true, true>), tile_grid(p.deal), 256, stream, p);
-		else
-			GSR_LAUNCH((blend_bwd_kernel<4, false, true>), tile_grid(p.deal), 256, stream, p);
-	} else if (p.half_tiles && depth)
-		GSR_LAUNCH((blend_bwd_kernel<2, true>), tile_grid(p.deal), 128, stream, p);
-	else if (p.half_tiles)
-		GSR_LAUNCH((blend_bwd_kernel<2, false>), tile_grid(p.deal), 128, stream, p);
-	else if (depth)
-		GSR_LAUNCH((blend_bwd_kernel<4, true>), tile_grid(p.deal), 256, stream, p);
-	else
-		GSR_LAUNCH((blend_bwd_kernel<4, false>), tile_grid(p.deal), 256, stream, p);
+	const int st = with_int<2, 4>([&](auto waves) {
+		return with_flags([&](auto dp, auto ab) -> int {
+			constexpr int WAVES = decltype(waves)::value;
+			constexpr bool DEPTH = decltype(dp)::value, ABS = decltype(ab)::value, EXISTS = blend_bwd_variant(WAVES, DEPTH, ABS);
+			if constexpr (EXISTS) GSR_LAUNCH((blend_bwd_kernel<WAVES, DEPTH, ABS>), tile_grid(p.deal), 64 * WAVES, stream, p);
+			return EXISTS ? GSR_OK : GSR_ERR_UNSUPPORTED;
+		}, depth, p.abs_sums != 0);
+	}, p.half_tiles ? 2 : 4, GSR_ERR_UNSUPPORTED);
+	if (st != GSR_OK) return st;
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

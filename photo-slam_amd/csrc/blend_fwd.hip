@@ -25,9 +25,12 @@
 // writes were zeroed by the caller; contribution_reduce_kernel sums every Gaussian's run.  1 = all weights one, 2 = weight map.
 #include "blend.h"
 #include "kernels.h"
+#include "variant.h"
 
 namespace gsr {
 
+// the instantiations that exist (variant.h): 2 x 2 x 3 = 12
+constexpr bool blend_fwd_variant(bool FWD_ONLY, bool DEPTH, int CONTRIB) { return CONTRIB >= 0 && CONTRIB <= 2; }
 template <bool FWD_ONLY, bool DEPTH, int CONTRIB = 0>
 __global__ void __launch_bounds__(64)
 blend_fwd_kernel(const BlendFwdParams p)
@@ -304,34 +307,19 @@ int launch_contribution_reduce(const ContributionParams& p, hipStream_t stream)
 	return GSR_OK;
 }
 
-template <int CONTRIB>
-static int launch_blend_fwd_contrib(const BlendFwdParams& p, bool depth, hipStream_t stream)
-{
-	if (p.forward_only && depth)
-		GSR_LAUNCH((blend_fwd_kernel<true, true, CONTRIB>), quad_grid(p.deal), 64, stream, p);
-	else if (p.forward_only)
-		GSR_LAUNCH((blend_fwd_kernel<true, false, CONTRIB>), quad_grid(p.deal), 64, stream, p);
-	else if (depth)
-		GSR_LAUNCH((blend_fwd_kernel<false, true, CONTRIB>), quad_grid(p.deal), 64, stream, p);
-	else
-		GSR_LAUNCH((blend_fwd_kernel<false, false, CONTRIB>), quad_grid(p.deal), 64, stream, p);
-	GSR_CHECK_LAUNCH();
-	return GSR_OK;
-}
-
 int launch_blend_fwd(const BlendFwdParams& p, hipStream_t stream)
 {
 	const bool depth = p.out_depth || p.out_alpha;
 	if (depth && !p.depth) return GSR_ERR_INVALID_ARG;
-	if (p.stats) return p.pixel_weight ? launch_blend_fwd_contrib<2>(p, depth, stream) : launch_blend_fwd_contrib<1>(p, depth, stream);
-	if (p.forward_only && depth)
-		GSR_LAUNCH((blend_fwd_kernel<true, true>), quad_grid(p.deal), 64, stream, p);
-	else if (p.forward_only)
-		GSR_LAUNCH((blend_fwd_kernel<true, false>), quad_grid(p.deal), 64, stream, p);
-	else if (depth)
-		GSR_LAUNCH((blend_fwd_kernel<false, true>), quad_grid(p.deal), 64, stream, p);
-	else
-		GSR_LAUNCH((blend_fwd_kernel<false, false>), quad_grid(p.deal), 64, stream, p);
+	const int st = with_int<0, 2>([&](auto contrib) {
+		return with_flags([&](auto fo, auto dp) -> int {
+			constexpr int CONTRIB = decltype(contrib)::value;
+			constexpr bool FWD_ONLY = decltype(fo)::value, DEPTH = decltype(dp)::value, EXISTS = blend_fwd_variant(FWD_ONLY, DEPTH, CONTRIB);
+			if constexpr (EXISTS) GSR_LAUNCH((blend_fwd_kernel<FWD_ONLY, DEPTH, CONTRIB>), quad_grid(p.deal), 64, stream, p);
+			return EXISTS ? GSR_OK : GSR_ERR_UNSUPPORTED;
+		}, p.forward_only != 0, depth);
+	}, p.stats ? (p.pixel_weight ? 2 : 1) : 0, GSR_ERR_UNSUPPORTED);
+	if (st != GSR_OK) return st;
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

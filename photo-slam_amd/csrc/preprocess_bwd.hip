@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "shrows.h"
 #include "partials.h"
+#include "variant.h"
 
 namespace gsr {
 
@@ -105,6 +106,8 @@ __device__ __forceinline__ void geom_adam_finish4(const GeomAdamTensor& t, size_
 // and gsr_sh_grad_from_views rebuilds dL_dsh for the whole keyframe batch after the exchange.
 // POSE (gsr_backward_args.dL_dcampos): the direction term is d/d(mean - campos), so its negative, summed over the wave (= the
 // workgroup), is this workgroup's entry of the camera-centre sums in the pose slab (kernels.h) -- an instantiation of its own.
+// The instantiations that exist (variant.h): 3 modes x 4 degrees, and POSE at the degrees that have a direction term, not factored: 12 + 6
+constexpr bool sh_bwd_rows_variant(int DEG, int MODE, bool POSE) { return DEG >= 0 && DEG <= 3 && MODE >= 0 && MODE <= 2 && (!POSE || (DEG > 0 && MODE != 1)); }
 template <int DEG, int MODE, bool POSE = false>   // MODE: 0 = gradient rows out, 1 = factored (colour gradient out), 2 = fused Adam step
 #ifndef GSR_SHB_SMALL_TRIP
 #define GSR_SHB_SMALL_TRIP 4
@@ -304,14 +307,20 @@ __device__ __forceinline__ void pack_view_row(const PreprocessBwdParams& p, int 
 // store or the fused geom_adam step: one code path for both, no traffic.  With p.reg_slab set (kernel-uniform) the three loss terms
 // of the lane are summed over the wave, the waves meet in LDS in a fixed order and ONE slab entry per workgroup and sum leaves with
 // plain stores (kernels.h: reg_slab_floats); reg_final_sum_kernel adds the entries in double.  No atomics: the same bits every time.
-// Instantiated with PACKED = POSE = false only (launch_preprocess_bwd), and an instantiation of its own, so that the kernels
+// Not together with PACKED or POSE (preprocess_bwd_variant below), and an instantiation of its own, so that the kernels
 // without it stay the same code.
 // ABS: the absolute screen-space gradients (gsr_backward_args.dL_dmean2D_abs).  The backward blend's ABS instantiations left
 // sum_p |w (2 A' dx + B' dy)| and sum_p |w (B' dx + 2 C' dy)| in slot words [10], [11], with the conic as the blend prescales it
 // (blend.h: A' = -log2(e) A / 2, B' = -log2(e) B): they ride through the run sums as a[10], a[11], and the positive constants --
 // the opacity, ln 2, W/2 and H/2 -- are applied here, behind the reduction.  With stat_accum set the statistic is the norm of
-// this pair.  Instantiations of their own (PACKED = false: not through the multi-GPU exchange), so that the kernels without it
-// stay the same code.
+// this pair.  Instantiations of their own (not together with PACKED, preprocess_bwd_variant below: not through the multi-GPU
+// exchange), so that the kernels without it stay the same code.
+// The instantiations that exist (variant.h): of PACKED, POSE, REG at most one, and ABS not with PACKED -- 7, times ROWS_OK, DEPTH
+// and AA: 56.  launch_preprocess_bwd refuses the other combinations in front of its first launch, as gsr_backward does.
+constexpr bool preprocess_bwd_variant(bool ROWS_OK, bool PACKED, bool DEPTH, bool POSE, bool AA, bool REG, bool ABS)
+{
+	return PACKED + POSE + REG <= 1 && !(ABS && PACKED);
+}
 template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false, bool REG = false, bool ABS = false>
 __global__ void __launch_bounds__(PRB_THREADS)
 preprocess_bwd_kernel(const PreprocessBwdParams p)
@@ -932,6 +941,7 @@ int launch_sh_adam_lazy(int P, const int* radii, const LazyAdam& a, hipStream_t 
 // The runs of more than LONG_RUN instance slots (partials.h): one wave per run, a fixed grid that strides over the list the
 // forward pass left (its length lives on the device).
 constexpr int LRS_BLOCKS = 1024;   // (one listed run per wave at C3: 512 -> 1 024 workgroups: 18.6 -> 14.1 us; more: equal)
+constexpr bool long_run_sums_variant(bool DEPTH, bool ABS) { return true; }   // the instantiations that exist (variant.h): all 4
 template <bool DEPTH, bool ABS = false>
 __global__ void __launch_bounds__(256)
 long_run_sums_kernel(const PreprocessBwdParams p)
@@ -1028,90 +1038,62 @@ int launch_reg_zero(float* loss, hipStream_t stream)
 
 int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 {
+	// ---- every refusal, in front of the first launch (gsr_backward: a refused call has enqueued nothing)
 	const bool abs_sums = p.dL_dmean2D_abs != nullptr;   // the absolute screen-space gradients: slot words [10], [11]
 	if (abs_sums && (p.dL_dcolor_view || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // not through the multi-GPU exchange
-	if (p.partials && abs_sums && p.depth) GSR_LAUNCH((long_run_sums_kernel<true, true>), LRS_BLOCKS, 256, stream, p);
-	else if (p.partials && abs_sums) GSR_LAUNCH((long_run_sums_kernel<false, true>), LRS_BLOCKS, 256, stream, p);
-	else if (p.partials && p.depth) GSR_LAUNCH(long_run_sums_kernel<true>, LRS_BLOCKS, 256, stream, p);
-	else if (p.partials) GSR_LAUNCH(long_run_sums_kernel<false>, LRS_BLOCKS, 256, stream, p);
 	const bool factored = p.dL_dcolor_view != nullptr;
 	const bool adam = p.adam_exp_avg != nullptr;
 	const bool rows_ok = sh_rows_path(p.shs, p.M, p.D, factored, adam, p.dL_dsh);   // (includes 0 <= D <= 3)
 	if (adam && (!rows_ok || factored || ((reinterpret_cast<uintptr_t>(p.adam_exp_avg) | reinterpret_cast<uintptr_t>(p.adam_exp_avg_sq)) & 15)))
 		return GSR_ERR_UNSUPPORTED;   // the fused step exists for aligned [P,16,3] rows only
-	if (p.geom.on && !(rows_ok && p.D >= 0 && p.D <= 3 && p.scales && p.rotations && p.dL_dmean3D))
+	if (p.geom.on && !(rows_ok && p.scales && p.rotations && p.dL_dmean3D))
 		return GSR_ERR_UNSUPPORTED;   // the fused geometry step lives in the two-kernel path of the reference's SH layout
-	const int grid = div_up(p.P, PRB_THREADS);
 	const bool pose = p.pose_scratch != nullptr;
-	unsigned pose_b_rows = 0u;   // entries of the camera centre's sums in the pose slab (kernels.h)
 	if (pose && (factored || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // no pose gradients through the multi-GPU exchange
-	const bool aa = (p.raw_params & GSR_ANTIALIAS) != 0;
 	const bool reg = p.reg_on != 0;
 	if (reg && (pose || factored || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // (keeps the number of instantiations down)
 	if (reg && !p.scales && (p.reg_w_scale != 0.f || p.reg_w_iso != 0.f)) return GSR_ERR_INVALID_ARG;
-#define GSR_PRB(RO, AAV)                                                                                                          \
-	do {                                                                                                                          \
-		if (abs_sums) {                                                                                                           \
-			if (reg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV, true, true>), grid, PRB_THREADS, stream, p);  \
-			else if (reg) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV, true, true>), grid, PRB_THREADS, stream, p);   \
-			else if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, true, AAV, false, true>), grid, PRB_THREADS, stream, p); \
-			else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, true, AAV, false, true>), grid, PRB_THREADS, stream, p);  \
-			else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV, false, true>), grid, PRB_THREADS, stream, p); \
-			else GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV, false, true>), grid, PRB_THREADS, stream, p);       \
-		} else                                                                                                                    \
-		if (reg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV, true>), grid, PRB_THREADS, stream, p);  \
-		else if (reg) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV, true>), grid, PRB_THREADS, stream, p);      \
-		else if (pose && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, true, AAV>), grid, PRB_THREADS, stream, p);       \
-		else if (pose) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, true, AAV>), grid, PRB_THREADS, stream, p);            \
-		else if (p.packed_msg && p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, true, true, false, AAV>), grid, PRB_THREADS, stream, p); \
-		else if (p.packed_msg) GSR_LAUNCH((preprocess_bwd_kernel<RO, true, false, false, AAV>), grid, PRB_THREADS, stream, p);    \
-		else if (p.depth) GSR_LAUNCH((preprocess_bwd_kernel<RO, false, true, false, AAV>), grid, PRB_THREADS, stream, p);         \
-		else GSR_LAUNCH((preprocess_bwd_kernel<RO, false, false, false, AAV>), grid, PRB_THREADS, stream, p);                     \
-	} while (0)
-	if (rows_ok && p.D >= 0 && p.D <= 3) {
-		if (aa) GSR_PRB(true, true);
-		else GSR_PRB(true, false);
-		GSR_CHECK_LAUNCH();
-		if (p.notify_stream && p.notify_event) {   // dL_dcolor_view is complete: whoever gathers it need not wait for the SH kernel
-			GSR_HIP(hipEventRecord((hipEvent_t)p.notify_event, stream));
-			GSR_HIP(hipStreamWaitEvent((hipStream_t)p.notify_stream, (hipEvent_t)p.notify_event, 0));
-		}
-		const int g = div_up(p.P, SHB_THREADS);
-	// (POSE: the direction term vanishes at degree 0 -- the colour-only kernel runs and the camera centre's sums have no entries)
-#define GSR_SHB(DEG)                                                                  \
-	do {                                                                              \
-		if (pose && DEG > 0 && adam)                                                  \
-			GSR_LAUNCH((sh_bwd_rows_kernel<(DEG > 0 ? DEG : 1), 2, true>), g, SHB_THREADS, stream, p); \
-		else if (pose && DEG > 0)                                                     \
-			GSR_LAUNCH((sh_bwd_rows_kernel<(DEG > 0 ? DEG : 1), 0, true>), g, SHB_THREADS, stream, p); \
-		else if (factored)                                                                 \
-			GSR_LAUNCH((sh_bwd_rows_kernel<DEG, 1>), g, SHB_THREADS, stream, p);      \
-		else if (adam)                                                                \
-			GSR_LAUNCH((sh_bwd_rows_kernel<DEG, 2>), g, SHB_THREADS, stream, p);      \
-		else                                                                          \
-			GSR_LAUNCH((sh_bwd_rows_kernel<DEG, 0>), g, SHB_THREADS, stream, p);      \
-	} while (0)
-		if (p.D == 3)
-			GSR_SHB(3);
-		else if (p.D == 2)
-			GSR_SHB(2);
-		else if (p.D == 1)
-			GSR_SHB(1);
-		else
-			GSR_SHB(0);
-#undef GSR_SHB
-		pose_b_rows = p.D > 0 ? (unsigned)g : 0u;
-	} else {
-		if (aa) GSR_PRB(false, true);
-		else GSR_PRB(false, false);
-		if (p.notify_stream && p.notify_event) {
-			GSR_HIP(hipEventRecord((hipEvent_t)p.notify_event, stream));
-			GSR_HIP(hipStreamWaitEvent((hipStream_t)p.notify_stream, (hipEvent_t)p.notify_event, 0));
-		}
-		// (the SH direction term, if any, was formed by preprocess_bwd_kernel: one camera-centre entry per workgroup of it)
-		pose_b_rows = (p.shs && p.D > 0) ? (unsigned)grid : 0u;
+	// ---- the launches
+	const bool depth = p.depth != 0;
+	int st = !p.partials ? (int)GSR_OK : with_flags([&](auto dp, auto ab) -> int {
+		constexpr bool DEPTH = decltype(dp)::value, ABS = decltype(ab)::value, EXISTS = long_run_sums_variant(DEPTH, ABS);
+		if constexpr (EXISTS) GSR_LAUNCH((long_run_sums_kernel<DEPTH, ABS>), LRS_BLOCKS, 256, stream, p);
+		return EXISTS ? GSR_OK : GSR_ERR_UNSUPPORTED;
+	}, depth, abs_sums);
+	if (st != GSR_OK) return st;
+	const int grid = div_up(p.P, PRB_THREADS);
+	st = with_flags([&](auto ro, auto pk, auto dp, auto ps, auto aa, auto rg, auto ab) -> int {
+		constexpr bool ROWS_OK = decltype(ro)::value, PACKED = decltype(pk)::value, DEPTH = decltype(dp)::value, POSE = decltype(ps)::value,
+		               AA = decltype(aa)::value, REG = decltype(rg)::value, ABS = decltype(ab)::value,
+		               EXISTS = preprocess_bwd_variant(ROWS_OK, PACKED, DEPTH, POSE, AA, REG, ABS);
+		if constexpr (EXISTS) GSR_LAUNCH((preprocess_bwd_kernel<ROWS_OK, PACKED, DEPTH, POSE, AA, REG, ABS>), grid, PRB_THREADS, stream, p);
+		return EXISTS ? GSR_OK : GSR_ERR_UNSUPPORTED;
+	}, rows_ok, p.packed_msg != nullptr, depth, pose, (p.raw_params & GSR_ANTIALIAS) != 0, reg, abs_sums);
+	if (st != GSR_OK) return st;
+	if (rows_ok) GSR_CHECK_LAUNCH();
+	if (p.notify_stream && p.notify_event) {   // dL_dcolor_view is complete: whoever gathers it need not wait for the SH kernel
+		GSR_HIP(hipEventRecord((hipEvent_t)p.notify_event, stream));
+		GSR_HIP(hipStreamWaitEvent((hipStream_t)p.notify_stream, (hipEvent_t)p.notify_event, 0));
 	}
-#undef GSR_PRB
+	// entries of the camera centre's sums in the pose slab (kernels.h).  Without the row kernel the SH direction term, if any, was
+	// formed by preprocess_bwd_kernel: one entry per workgroup of it
+	unsigned pose_b_rows = (p.shs && p.D > 0) ? (unsigned)grid : 0u;
+	if (rows_ok) {
+		const int g = div_up(p.P, SHB_THREADS);
+		// (POSE: the direction term vanishes at degree 0 -- the colour-only kernel runs and the camera centre's sums have no entries)
+		st = with_int<0, 3>([&](auto deg) {
+			return with_int<0, 2>([&](auto mode) {
+				return with_flags([&](auto ps) -> int {
+					constexpr int DEG = decltype(deg)::value, MODE = decltype(mode)::value;
+					constexpr bool POSE = decltype(ps)::value, EXISTS = sh_bwd_rows_variant(DEG, MODE, POSE);
+					if constexpr (EXISTS) GSR_LAUNCH((sh_bwd_rows_kernel<DEG, MODE, POSE>), g, SHB_THREADS, stream, p);
+					return EXISTS ? GSR_OK : GSR_ERR_UNSUPPORTED;
+				}, pose && p.D > 0);
+			}, factored ? 1 : (adam ? 2 : 0), GSR_ERR_UNSUPPORTED);
+		}, p.D, GSR_ERR_UNSUPPORTED);
+		if (st != GSR_OK) return st;
+		pose_b_rows = p.D > 0 ? (unsigned)g : 0u;
+	}
 	GSR_CHECK_LAUNCH();
 	if (pose) return launch_pose_final_sum(p.pose_scratch, (unsigned)grid, pose_b_rows, p.dL_dview, p.dL_dproj, p.dL_dcampos, stream);
 	if (reg && p.reg_slab) {
@@ -1138,6 +1120,8 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 // PACKED: the views arrive as the messages of gsr_pack_color_view (include/gsr.h) -- a bit per Gaussian says whether the view sees
 // it, its row sits at (seen rows in front of the 64-row group) + (seen rows in front of it inside the group); the camera centre
 // rides in the header.  Same rows, same order of the views: the same bits as the dense form.
+// The instantiations that exist (variant.h): 4 degrees x (rows out, the step, the lazy step) x PACKED = 24
+constexpr bool sh_grad_from_views_variant(int DEG, bool ADAM, bool LAZY, bool PACKED) { return DEG >= 0 && DEG <= 3 && (ADAM || !LAZY); }
 template <int DEG, bool ADAM, bool LAZY, bool PACKED>
 __global__ void __launch_bounds__(SHB_THREADS) GSR_WAVES_PER_EU(4, 8)
 sh_grad_from_views_kernel(int P, int n_views, const float* __restrict__ means3D, const float* __restrict__ campos,
@@ -1301,31 +1285,18 @@ int launch_sh_grad_from_views(int P, int D, int M, int n_views, const float* mea
 		const int g = div_up(P, SHB_THREADS);
 		const RowAdam ra = adam ? *adam : RowAdam{};
 		const LazyAdam lz = lazy ? *lazy : LazyAdam{};
-#define GSR_SHV_LAUNCH(DEG, A, L, K)                                                                                          \
-	GSR_LAUNCH((sh_grad_from_views_kernel<DEG, A, L, K>), g, SHB_THREADS, stream, P, n_views, means3D, campos, campos_stride,   \
-	           views, view_stride, scale, dL_dsh, ra, lz, packed, pkp, pkm)
-#define GSR_SHV(DEG)                                                                                                          \
-	do {                                                                                                                      \
-		if (packed.msgs) {                                                                                                    \
-			if (adam && lazy) GSR_SHV_LAUNCH(DEG, true, true, true);                                                          \
-			else if (adam) GSR_SHV_LAUNCH(DEG, true, false, true);                                                            \
-			else GSR_SHV_LAUNCH(DEG, false, false, true);                                                                     \
-		} else {                                                                                                              \
-			if (adam && lazy) GSR_SHV_LAUNCH(DEG, true, true, false);                                                         \
-			else if (adam) GSR_SHV_LAUNCH(DEG, true, false, false);                                                           \
-			else GSR_SHV_LAUNCH(DEG, false, false, false);                                                                    \
-		}                                                                                                                     \
-	} while (0)
-		if (D == 3)
-			GSR_SHV(3);
-		else if (D == 2)
-			GSR_SHV(2);
-		else if (D == 1)
-			GSR_SHV(1);
-		else
-			GSR_SHV(0);
-#undef GSR_SHV
-#undef GSR_SHV_LAUNCH
+		const int st = with_int<0, 3>([&](auto deg) {
+			return with_flags([&](auto with_adam, auto with_lazy, auto pk) -> int {
+				constexpr int DEG = decltype(deg)::value;
+				constexpr bool ADAM = decltype(with_adam)::value, LAZY = decltype(with_lazy)::value, PACKED = decltype(pk)::value;
+				constexpr bool EXISTS = sh_grad_from_views_variant(DEG, ADAM, LAZY, PACKED);
+				if constexpr (EXISTS)
+					GSR_LAUNCH((sh_grad_from_views_kernel<DEG, ADAM, LAZY, PACKED>), g, SHB_THREADS, stream, P, n_views, means3D, campos,
+					           campos_stride, views, view_stride, scale, dL_dsh, ra, lz, packed, pkp, pkm);
+				return EXISTS ? GSR_OK : GSR_ERR_INVALID_ARG;   // (lazy without adam: refused with this status above)
+			}, adam != nullptr, lazy != nullptr, packed.msgs != nullptr);
+		}, D, GSR_ERR_INVALID_ARG);   // (D outside 0..3: gsr_sh_grad_from_views and its siblings have refused it with this status)
+		if (st != GSR_OK) return st;
 	} else {
 		GSR_LAUNCH(sh_grad_from_views_generic_kernel, div_up(P, 128), 128, stream, P, D, M, n_views, means3D, campos,
 		           campos_stride, views, view_stride, scale, dL_dsh);
