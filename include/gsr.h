@@ -182,6 +182,9 @@ typedef struct gsr_forward_args {
 	int* out_n_touched;          /* [P] or NULL */
 	int contribution_accumulate; /* 0: every element of the outputs is written.  1: sum += new (one float add), max = max(max, new),
 	                                n_touched += new: a scoring pass over K keyframes is K renders with nothing in between */
+	/* Extension (read only with GSR_FILTER_3D in raw_params, see there; without the bit the pointer is not read): the 3-D smoothing
+	 * filter of every Gaussian, e.g. from gsr_filter3d_compute.  An input without a gradient. */
+	const float* filter_3D;      /* [P] */
 } gsr_forward_args;
 
 #define GSR_RAW_OPACITY 1   /* opacities are logits */
@@ -269,6 +272,37 @@ typedef struct gsr_forward_args {
  * the buffers of a training-form call gives the gradients it gives after a plain forward.  The binning buffer grows by 48 bytes
  * per instance: gsr_binning_bytes_for(R, raw_params) is the size requested.  P == 0 leaves the outputs untouched. */
 #define GSR_CONTRIBUTION 512
+/* ... and one that changes what is rendered (read by gsr_forward AND gsr_backward: the same value in both calls, exactly as
+ * GSR_ANTIALIAS, and refused by gsr_backward in the same way when it differs from the forward call's).  The 3-D SMOOTHING FILTER of
+ * Mip-Splatting, the other half of GSR_ANTIALIAS: every Gaussian is bounded from below by the sampling interval of the keyframes
+ * that observe it, so that no view closer than any keyframe erodes it.  filter_3D[i] = f is a per-Gaussian INPUT (gsr_forward_args /
+ * gsr_backward_args.filter_3D; gsr_filter3d_compute derives it from the keyframes) and has no gradient.  With s_k the activated scale
+ * (the input, or its exp under GSR_RAW_SCALING; WITHOUT scale_modifier) and o the activated opacity (the input, or its sigmoid under
+ * GSR_RAW_OPACITY), in float32, every operation rounded on its own, in this order:
+ *   F   = f * f
+ *   a_k = s_k * s_k + F          s'_k = sqrtf(a_k)          r_k = s_k / s'_k        (k = 0, 1, 2)
+ *   c   = (r_0 * r_1) * r_2      o'   = o * c
+ * Everything downstream sees (s', o') in place of (s, o): the covariance, scale_modifier, the radius, the h of GSR_ANTIALIAS (the
+ * record holds (o c) h), the blend record's opacity, the bound of GSR_CULL_EMPTY_TILES, the depth and alpha maps, the contribution
+ * statistics.  c = sqrt(det Sigma / det(Sigma + F I)) of Mip-Splatting, written as a product of ratios so that nothing underflows
+ * for tiny scales; f = 0 gives s' = s and c = 1 exactly (scales whose squares do not underflow).  Division and square root are the
+ * correctly rounded ones (the HIP compiler's default for float): gsr_forward and gsr_backward evaluate the same bits.
+ * gsr_backward, with g_s' the gradient of the filtered scale and g_o' that of the filtered opacity (what the pass forms without
+ * the bit):
+ *   dL/ds_k = g_s'_k * r_k + g_o' * o * (r_{k+1} * r_{k+2}) * F / (a_k * s'_k)       dL/do = g_o' * c
+ * then the raw chain rules as ever (* s_k under GSR_RAW_SCALING, * o (1 - o) under GSR_RAW_OPACITY).  o is recovered from the
+ * record as o' / c, as under GSR_ANTIALIAS (the backward pass is given no opacities); a Gaussian with c == 0 (a scale that is
+ * exactly 0 under a non-zero filter) renders nothing and gets no opacity term.  The gsr_geom_reg terms join AFTER this chain rule
+ * and stay defined on the unfiltered s and o; stat_*, dL_dmean2D_abs and the pose gradients are unaffected except through the
+ * changed render; dL_dcov3D is the gradient of the filtered covariance.
+ * GSR_ERR_INVALID_ARG: the bit with filter_3D == NULL; the bit together with cov3D_precomp (no scales to filter).  A negative or
+ * non-finite entry is the caller's error and is not checked on the device.  GSR_ERR_UNSUPPORTED: together with dL_dcolor_view /
+ * packed_view (the multi-GPU exchange).
+ * Works with geom_adam (the fused step consumes the filtered chain rule's gradients), sh_adam (eager and lazy), dL_ddepth /
+ * dL_dalpha, GSR_ANTIALIAS, GSR_FORWARD_ONLY, GSR_CONTRIBUTION, GSR_CULL_EMPTY_TILES, both GSR_BINNING_* arrangements, geom_reg,
+ * dL_dmean2D_abs and the pose outputs.  0 = the render and the gradients without it, bit for bit, by the same kernels as before
+ * (the bit selects instantiations of its own). */
+#define GSR_FILTER_3D 1024
 
 /* Rasterizer::forward, cuda_rasterizer/rasterizer_impl.cu:198-336.
  * Fills out_color and radii, returns the number of (tile, Gaussian) instances in
@@ -411,6 +445,8 @@ typedef struct gsr_backward_args {
 	 * before.  Works with geom_adam, sh_adam, geom_reg, the pose gradients, GSR_ANTIALIAS and both GSR_BINNING_* arrangements; not
 	 * together with dL_dcolor_view / packed_view (the multi-GPU exchange): GSR_ERR_UNSUPPORTED. */
 	float* dL_dmean2D_abs;
+	/* Extension (read only with GSR_FILTER_3D in raw_params, see there): the filter the forward call was given. */
+	const float* filter_3D;      /* [P] */
 } gsr_backward_args;
 
 /* Rasterizer::backward, cuda_rasterizer/rasterizer_impl.cu:340-433.
@@ -819,6 +855,33 @@ int gsr_reproject_depth_pinhole(int P, int width, float fx, float fy, float cx, 
 int gsr_neighborhood_depth_pinhole(int N, int width, float fx, float fy, float cx, float cy, float max_pixel_dist,
                                    const float* pixels, const uint8_t* has3D, const float* point3D, const float* colors,
                                    float* out_points, float* out_colors, void* stream);
+
+/* ---- the 3-D smoothing filter of GSR_FILTER_3D from the keyframes (Mip-Splatting's compute_3D_filter) ----
+ * cameras: K structs ON THE DEVICE; viewmatrix as gsr_forward_args.viewmatrix, focal lengths and size in pixels of the finest level
+ * the keyframe is trained at.  Per Gaussian and camera, in float32, every operation rounded on its own, in this order:
+ *   1. (x, y, z) = the view-space point, x = V[0] X + V[4] Y + V[8] Z + V[12] (summed left to right), y and z likewise; z is
+ *      exactly the expression gsr_forward culls by, so z > 0.2f is the rasterizer's own near test
+ *   2. u = (x / z) * focal_x + 0.5f * width,  v = (y / z) * focal_y + 0.5f * height
+ *   3. the camera OBSERVES the Gaussian iff z > 0.2f and -0.15f width <= u <= 1.15f width and -0.15f height <= v <= 1.15f height
+ *      (Mip-Splatting's 15 % margin)
+ *   4. T_i = min over the observing cameras of z / fmaxf(focal_x, focal_y)
+ *   5. filter_3D[i] = sqrtf(variance) * T_i                                    (variance: 0.2f upstream)
+ *   6. a Gaussian no camera observes gets sqrtf(variance) * max over the observed Gaussians of T_i (upstream's rule); when nothing
+ *      is observed, or K == 0, every entry is 0
+ *   7. P == 0 writes nothing
+ * This differs from upstream in two ways: upstream takes the smallest z and the globally largest focal length separately, and
+ * projects both axes with focal_x.  For cameras of one focal length and square pixels the two definitions coincide; with pyramid
+ * levels of different focal lengths this one is the exact per-camera sampling interval z / f.
+ * The maximum of step 6 is formed without float atomics (per-workgroup maxima in `scratch`, a second small launch): the same inputs
+ * give the same bits on every run.  scratch: gsr_filter3d_scratch_bytes(P) device bytes, 4-byte aligned, contents don't care.
+ * GSR_ERR_INVALID_ARG: P or K negative, a negative or non-finite variance, a NULL pointer (cameras may be NULL when K == 0). */
+typedef struct gsr_filter3d_camera {
+	float viewmatrix[16];
+	float focal_x, focal_y, width, height;
+} gsr_filter3d_camera;   /* 80 bytes */
+size_t gsr_filter3d_scratch_bytes(int P);
+int gsr_filter3d_compute(int P, const float* means3D, int K, const gsr_filter3d_camera* cameras, float variance, float* filter_3D,
+                         char* scratch, void* stream);
 
 /* Scratch sizes (bytes) gsr_forward will request, for callers that pre-allocate. */
 size_t gsr_geometry_bytes(int P);

@@ -34,7 +34,8 @@ class ForwardArgs(C.Structure):
                 ("out_color", C.c_void_p), ("radii", C.c_void_p), ("raw_params", C.c_int), ("sh_adam", C.c_void_p),
                 ("out_depth", C.c_void_p), ("out_alpha", C.c_void_p),
                 ("pixel_weight", C.c_void_p), ("out_weight_sum", C.c_void_p), ("out_weight_max", C.c_void_p),
-                ("out_n_touched", C.c_void_p), ("contribution_accumulate", C.c_int)]
+                ("out_n_touched", C.c_void_p), ("contribution_accumulate", C.c_int),
+                ("filter_3D", C.c_void_p)]
 
 
 SH_LAZY_WINDOW = 32   # GSR_SH_LAZY_WINDOW
@@ -122,7 +123,14 @@ class BackwardArgs(C.Structure):
                 ("dL_ddepth", C.c_void_p), ("dL_dalpha", C.c_void_p),
                 ("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p),
                 ("pose_scratch", C.c_void_p), ("geom_reg", C.POINTER(GeomReg)),
-                ("dL_dmean2D_abs", C.c_void_p)]
+                ("dL_dmean2D_abs", C.c_void_p), ("filter_3D", C.c_void_p)]
+
+
+class Filter3DCamera(C.Structure):
+    """gsr_filter3d_camera (80 bytes): viewmatrix as gsr_forward_args.viewmatrix, focal lengths and size in pixels"""
+    _fields_ = [("viewmatrix", C.c_float * 16), ("focal_x", C.c_float), ("focal_y", C.c_float), ("width", C.c_float),
+                ("height", C.c_float)]
+
 
 class DensifySelectArgs(C.Structure):
     _fields_ = [("P", C.c_int), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p), ("scaling", C.c_void_p),
@@ -167,6 +175,7 @@ RAW_OPACITY, RAW_SCALING, RAW_ROTATION = 1, 2, 4   # GSR_RAW_* of include/gsr.h
 CULL_EMPTY_TILES, FORWARD_ONLY = 8, 128             # GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY
 ANTIALIAS = 256                                     # GSR_ANTIALIAS: forward AND backward (the same value in both calls)
 CONTRIBUTION = 512                                  # GSR_CONTRIBUTION: per-Gaussian contribution statistics of a forward pass
+FILTER_3D = 1024                                    # GSR_FILTER_3D: forward AND backward (the same value in both calls)
 
 
 # every symbol include/gsr.h declares
@@ -185,6 +194,7 @@ EXPORTED_SYMBOLS = [
     "gsr_geom_reg_scratch_bytes",
     "gsr_mcmc_scratch_bytes", "gsr_mcmc_relocate", "gsr_mcmc_add_noise",
     "gsr_seed_scratch_bytes", "gsr_seed_select", "gsr_seed_emit",
+    "gsr_filter3d_scratch_bytes", "gsr_filter3d_compute",
 ]
 
 _libs = {}
@@ -283,6 +293,10 @@ def load(path=None):
     L.gsr_seed_select.argtypes = [C.POINTER(SeedSelectArgs), vp, vp, vp]
     L.gsr_seed_emit.restype = i32
     L.gsr_seed_emit.argtypes = [C.POINTER(SeedEmitArgs), vp, vp]
+    L.gsr_filter3d_scratch_bytes.restype = sz
+    L.gsr_filter3d_scratch_bytes.argtypes = [i32]
+    L.gsr_filter3d_compute.restype = i32
+    L.gsr_filter3d_compute.argtypes = [i32, vp, i32, vp, f32, vp, vp, vp]
     L.gsr_transform_points.restype = i32
     L.gsr_transform_points.argtypes = [i32, vp, vp, vp, vp]
     L.gsr_scale_transform_points.restype = i32

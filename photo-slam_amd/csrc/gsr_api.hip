@@ -114,8 +114,8 @@ static thread_local int t_last_forward_only = -1;   // gsr_last_forward_only()
 // the geometry buffer of this thread's last forward-only gsr_forward (GSR_FORWARD_ONLY): gsr_backward refuses it -- a cheap guard,
 // not a full check (a backward pass on another thread is not caught); a training forward on the same buffer clears it
 static thread_local const char* t_forward_only_geom = nullptr;
-// GSR_ANTIALIAS must be the same in gsr_forward and gsr_backward (the record holds the compensated opacity): the geometry buffer
-// and the bit of this thread's last training forward are remembered, and gsr_backward refuses that buffer with the other value.
+// GSR_ANTIALIAS and GSR_FILTER_3D must be the same in gsr_forward and gsr_backward (the record holds the compensated / filtered
+// opacity): the geometry buffer and the two bits of this thread's last training forward are remembered, and gsr_backward refuses that buffer with the other value.
 // The same kind of cheap guard: a backward pass on another thread is not caught.
 static thread_local const char* t_antialias_geom = nullptr;
 static thread_local int t_antialias_bit = 0;
@@ -398,6 +398,9 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	if (st != GSR_OK) return st;
 	if (!a->background || !a->means3D || !a->opacities || !a->viewmatrix || !a->projmatrix || !a->cam_pos || !a->out_color)
 		return GSR_ERR_INVALID_ARG;
+	// GSR_FILTER_3D: the bit needs the filter and scales to apply it to; without the bit the pointer is not read (include/gsr.h)
+	const bool filter3d = (a->raw_params & GSR_FILTER_3D) != 0;
+	if (filter3d && (!a->filter_3D || a->cov3D_precomp)) return GSR_ERR_INVALID_ARG;
 	hipStream_t stream = (hipStream_t)stream_;
 	const int P = a->P, W = a->width, H = a->height;
 	const int grid_x = div_up(W, TILE), grid_y = div_up(H, TILE), tiles = grid_x * grid_y;
@@ -409,7 +412,7 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	else if (t_forward_only_geom == geom_chunk) t_forward_only_geom = nullptr;
 	if (!fwd_only) {
 		t_antialias_geom = geom_chunk;
-		t_antialias_bit = a->raw_params & GSR_ANTIALIAS;
+		t_antialias_bit = a->raw_params & (GSR_ANTIALIAS | GSR_FILTER_3D);
 	}
 	char* img_chunk = imageBuffer(image_ctx, image_bytes(W, H, fwd_only));
 	if (!img_chunk) return GSR_ERR_ALLOC;
@@ -436,6 +439,7 @@ int gsr_forward(const gsr_forward_args* a, gsr_alloc_fn geometryBuffer, void* ge
 	pp.ranges = im.ranges; pp.tiles = tiles;   // zeroed there: rasterizer_impl.cu:310
 	pp.lazy = LazyAdam{};
 	pp.forward_only = fwd_only ? 1 : 0;
+	pp.filter_3D = filter3d ? a->filter_3D : nullptr;
 	if (a->sh_adam && a->sh_adam->lazy) {   // lazy SH Adam: visible rows that lag behind take their missed steps first
 		if (!a->shs) return GSR_ERR_INVALID_ARG;
 		if ((st = make_lazy_adam(*a->sh_adam, a->shs, a->M, pp.lazy)) != GSR_OK) return st;
@@ -621,6 +625,10 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 		return GSR_ERR_INVALID_ARG;
 	if (pose && (a->dL_dcolor_view || a->packed_view)) return GSR_ERR_UNSUPPORTED;   // not through the multi-GPU exchange
 	if (a->dL_dmean2D_abs && (a->dL_dcolor_view || a->packed_view)) return GSR_ERR_UNSUPPORTED;   // likewise
+	// GSR_FILTER_3D (gsr.h): the bit needs the filter and scales; not through the multi-GPU exchange
+	const bool filter3d = (a->raw_params & GSR_FILTER_3D) != 0;
+	if (filter3d && (!a->filter_3D || a->cov3D_precomp)) return GSR_ERR_INVALID_ARG;
+	if (filter3d && (a->dL_dcolor_view || a->packed_view)) return GSR_ERR_UNSUPPORTED;
 	if (!a->dL_dopacity && !a->geom_adam) return GSR_ERR_INVALID_ARG;   // (dL_dmean2D / dL_dcov3D: nullable, see gsr.h)
 	if (a->shs && !a->dL_dsh && !a->dL_dcolor_view && !a->sh_adam) return GSR_ERR_INVALID_ARG;
 	if ((a->stat_grad_accum != nullptr) != (a->stat_denom != nullptr) || (a->stat_denom != nullptr) != (a->stat_max_radii != nullptr))
@@ -635,8 +643,10 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	if (a->R > 0 && !a->binning_buffer) return GSR_ERR_INVALID_ARG;
 	// the buffers of a forward-only pass hold nothing a backward pass needs (GSR_FORWARD_ONLY; this thread's last such pass only)
 	if (t_forward_only_geom != nullptr && a->geom_buffer == t_forward_only_geom) return GSR_ERR_INVALID_ARG;
-	// GSR_ANTIALIAS differs from the forward pass that filled this geometry buffer (this thread's last training forward only)
-	if (t_antialias_geom != nullptr && a->geom_buffer == t_antialias_geom && (a->raw_params & GSR_ANTIALIAS) != t_antialias_bit)
+	// GSR_ANTIALIAS or GSR_FILTER_3D differs from the forward pass that filled this geometry buffer (this thread's last training
+	// forward only)
+	if (t_antialias_geom != nullptr && a->geom_buffer == t_antialias_geom &&
+	    (a->raw_params & (GSR_ANTIALIAS | GSR_FILTER_3D)) != t_antialias_bit)
 		return GSR_ERR_INVALID_ARG;
 	// (a stream cannot be made to wait for an event of its own future: refused HERE, before anything is enqueued and before the
 	// lazy rows' catch-up has advanced a step counter)
@@ -818,6 +828,7 @@ int gsr_backward(const gsr_backward_args* a, void* stream_)
 	pb.reg_slab = (reg && a->geom_reg->loss) ? reinterpret_cast<float*>(a->geom_reg->scratch) : nullptr;
 	pb.reg_loss = reg ? a->geom_reg->loss : nullptr;
 	pb.dL_dmean2D_abs = a->dL_dmean2D_abs;
+	pb.filter_3D = filter3d ? a->filter_3D : nullptr;
 	pb.notify_stream = nullptr; pb.notify_event = nullptr;
 	if (a->color_view_ready_stream && a->dL_dcolor_view) {
 		if ((st = t_sync.init_notify()) != GSR_OK) return fail(st);

@@ -66,6 +66,7 @@ struct PreprocessParams {
 	int tiles;
 	LazyAdam lazy;   // row_step != null: visible rows that lag behind (step - 1) are brought up to date before their SH evaluation
 	int forward_only;   // GSR_FORWARD_ONLY: no clamp mask; lazy rows are caught up in LDS only (nothing of the Adam state is written)
+	const float* filter_3D;   // [P] GSR_FILTER_3D: the 3-D smoothing filter of every Gaussian (filter3d_terms below); null = off
 };
 int launch_preprocess_fwd(const PreprocessParams& p, const GeometryState& g, hipStream_t stream);
 int launch_check_frustum(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t stream);
@@ -235,6 +236,9 @@ struct PreprocessBwdParams {
 	// slot words [10], [11]; the ABS instantiations carry them through the run sums, apply the positive per-Gaussian constants and
 	// write [P,2]; with stat_accum set the statistic is the norm of this pair.  null = off
 	float* dL_dmean2D_abs;
+	// GSR_FILTER_3D: the filter the forward pass was given ([P]; null = off).  The covariance is recomputed from the filtered scales,
+	// the record holds the filtered opacity, and the scale and opacity gradients take the filter's chain rule (preprocess_bwd.hip)
+	const float* filter_3D;
 };
 // The regularisers' loss slab: 3 sums (opacity, scale, isotropy), component-major, one entry per workgroup of preprocess_bwd_kernel
 static inline size_t reg_slab_floats(int P) { return 3 * (((size_t)(P > 0 ? P : 0) + 127) / 128) + 4; }   // PRB_THREADS
@@ -302,20 +306,51 @@ __device__ __forceinline__ float antialias_h2(float a0, float b, float c0, float
 	return fmaxf(AA_H2_MIN, det0 / det1);
 }
 
+// GSR_FILTER_3D (include/gsr.h): Mip-Splatting's 3-D smoothing filter f on the activated scales s (without scale_modifier):
+//   F = f f;  a_k = s_k s_k + F;  s'_k = sqrtf(a_k);  r_k = s_k / s'_k          (the opacity factor is c = (r_0 r_1) r_2)
+// ONE function for the forward preprocess (through compute_cov3D) and the backward preprocess (compute_cov3D again, and the chain
+// rule of the scale gradient): both translation units are compiled with -ffp-contract=off and the device's division and square
+// root are correctly rounded (the HIP default), so the evaluations are the same bits; the operation order is part of the contract.
+__device__ __forceinline__ void filter3d_terms(float f, float sx, float sy, float sz, float sp[3], float r[3], float a[3], float& F)
+{
+	F = f * f;
+	a[0] = sx * sx + F;
+	a[1] = sy * sy + F;
+	a[2] = sz * sz + F;
+	sp[0] = sqrtf(a[0]);
+	sp[1] = sqrtf(a[1]);
+	sp[2] = sqrtf(a[2]);
+	r[0] = sx / sp[0];
+	r[1] = sy / sp[1];
+	r[2] = sz / sp[2];
+}
+
 // computeCov3D, forward.cu:118-152 (M = S*R with S diagonal: M[c][r] = s_r * R[c][r]; Sigma = transpose(M) * M), with the
 // activations of raw_params applied first (getScalingActivation / getRotationActivation, gaussian_model.cpp:48-56).
+// filter_3D (null = off; the preprocess kernels pass a compile-time null from their instantiations without GSR_FILTER_3D): the
+// activated scales are replaced by the filtered ones (filter3d_terms) in front of scale_modifier, and *filter_c receives the
+// opacity factor c.
 // ONE function for the forward preprocess, which needs Sigma for the projection, and for the backward preprocess, which
 // needs it again for computeCov2DCUDA (backward.cu:144-274): the reference stores 24 bytes per Gaussian in between
 // (geomState.cov3D), here the backward pass recomputes them from the scale and rotation it loads anyway -- both translation
 // units are compiled with -ffp-contract=off, so the two evaluations are the same bits.
 __device__ __forceinline__ void compute_cov3D(const float* __restrict__ scales, const float* __restrict__ rotations, size_t idx,
-                                              float scale_modifier, int raw_params, float c3[6])
+                                              float scale_modifier, int raw_params, float c3[6],
+                                              const float* __restrict__ filter_3D = nullptr, float* filter_c = nullptr)
 {
 	float sx = scales[3 * idx], sy = scales[3 * idx + 1], sz = scales[3 * idx + 2];
 	if (raw_params & GSR_RAW_SCALING) {   // getScalingActivation, gaussian_model.cpp:48-51
 		sx = expf(sx);
 		sy = expf(sy);
 		sz = expf(sz);
+	}
+	if (filter_3D != nullptr) {
+		float sp[3], r[3], a[3], F;
+		filter3d_terms(filter_3D[idx], sx, sy, sz, sp, r, a, F);
+		sx = sp[0];
+		sy = sp[1];
+		sz = sp[2];
+		if (filter_c) *filter_c = (r[0] * r[1]) * r[2];
 	}
 	const float s0 = scale_modifier * sx, s1 = scale_modifier * sy, s2 = scale_modifier * sz;
 	float4 q = reinterpret_cast<const float4*>(rotations)[idx];

@@ -515,11 +515,119 @@ static inline SeedScratch seed_carve(char* scratch, long long n)
 	return s;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Mip-Splatting's 3-D smoothing filter from the keyframes that observe a Gaussian (include/gsr.h: gsr_filter3d_compute).
+//
+//   filter3d_kernel      : one Gaussian per lane, its mean in registers, a loop over the K cameras.  The camera index is
+//                          wave-uniform and the array is const __restrict__: the 80 bytes of a camera arrive through scalar loads
+//                          (s_load_dwordx16 + x4 in the ISA), once per wave and camera, not per lane.  The means are read once for all
+//                          K cameras: 12 B in and 4 B out per Gaussian.  An observed Gaussian leaves sqrt(variance) T, T = its
+//                          smallest sampling interval z / max(fx, fy); an unobserved one leaves F3D_UNOBSERVED (a negative number:
+//                          every observed value is positive).  The grid is capped at F3D_MAX_BLOCKS workgroups that stride over
+//                          the rows, and every workgroup leaves the largest T it saw in `block_max` with a plain store.
+//   filter3d_fill_kernel : every workgroup takes the maximum of the (at most F3D_MAX_BLOCKS) entries and gives the unobserved rows
+//                          of its stride sqrt(variance) times that -- upstream's rule; 0 when nothing is observed.
+// T >= 0, so the maxima are taken on the bit patterns (the integer order of non-negative floats is their order): no float atomics,
+// no order dependence -- the same inputs give the same bits.
+constexpr int F3D_THREADS = 256;
+constexpr int F3D_MAX_BLOCKS = 1024;
+constexpr float F3D_UNOBSERVED = -1.0f;
+
+__global__ void __launch_bounds__(F3D_THREADS)
+filter3d_kernel(int P, const float* __restrict__ means3D, int K, const gsr_filter3d_camera* __restrict__ cams, float sqrt_variance,
+                float* __restrict__ filter_3D, uint32_t* __restrict__ block_max)
+{
+	__shared__ uint32_t s_max[F3D_THREADS / 64];
+	uint32_t t_max = 0u;   // bits of the largest T of an observed Gaussian of this thread
+	// (every thread of the workgroup runs the same number of rounds: the wave maximum below needs whole waves)
+	for (long long base = (long long)blockIdx.x * F3D_THREADS; base < (long long)P; base += (long long)gridDim.x * F3D_THREADS) {
+		const long long i = base + threadIdx.x;
+		if (i >= (long long)P) continue;
+		const float px = means3D[3 * (size_t)i], py = means3D[3 * (size_t)i + 1], pz = means3D[3 * (size_t)i + 2];
+		float T = 0.f;
+		bool observed = false;
+		for (int k = 0; k < K; k++) {
+			const float* V = cams[k].viewmatrix;
+			const float fx = cams[k].focal_x, fy = cams[k].focal_y, w = cams[k].width, h = cams[k].height;
+			const float x = V[0] * px + V[4] * py + V[8] * pz + V[12];
+			const float y = V[1] * px + V[5] * py + V[9] * pz + V[13];
+			const float z = V[2] * px + V[6] * py + V[10] * pz + V[14];   // vz of preprocess_fwd_kernel: z > 0.2f is its near test
+			const float u = (x / z) * fx + 0.5f * w;
+			const float v = (y / z) * fy + 0.5f * h;
+			const bool sees = z > 0.2f && u >= -0.15f * w && u <= 1.15f * w && v >= -0.15f * h && v <= 1.15f * h;
+			const float t = z / fmaxf(fx, fy);
+			if (sees) {
+				T = observed ? fminf(T, t) : t;
+				observed = true;
+			}
+		}
+		filter_3D[i] = observed ? sqrt_variance * T : F3D_UNOBSERVED;
+		if (observed && T > 0.f) {   // (a NaN or a negative T -- a caller's camera without a focal length -- never becomes the maximum)
+			const uint32_t b = __float_as_uint(T);
+			t_max = b > t_max ? b : t_max;
+		}
+	}
+	const uint32_t w_max = wave_max_u32(t_max);
+	if (lane_id() == 0) s_max[wave_id()] = w_max;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint32_t m = s_max[0];
+#pragma unroll
+		for (int k = 1; k < F3D_THREADS / 64; k++) m = s_max[k] > m ? s_max[k] : m;
+		block_max[blockIdx.x] = m;
+	}
+}
+
+__global__ void __launch_bounds__(F3D_THREADS)
+filter3d_fill_kernel(int P, int n_blocks, const uint32_t* __restrict__ block_max, float sqrt_variance, float* __restrict__ filter_3D)
+{
+	__shared__ uint32_t s_max[F3D_THREADS / 64];
+	uint32_t m = 0u;
+	for (int b = (int)threadIdx.x; b < n_blocks; b += F3D_THREADS) m = block_max[b] > m ? block_max[b] : m;
+	m = wave_max_u32(m);
+	if (lane_id() == 0) s_max[wave_id()] = m;
+	__syncthreads();
+	m = s_max[0];
+#pragma unroll
+	for (int k = 1; k < F3D_THREADS / 64; k++) m = s_max[k] > m ? s_max[k] : m;
+	const float fill = sqrt_variance * __uint_as_float(m);
+	for (long long i = (long long)blockIdx.x * F3D_THREADS + threadIdx.x; i < (long long)P; i += (long long)gridDim.x * F3D_THREADS)
+		if (filter_3D[i] < 0.f) filter_3D[i] = fill;
+}
+
+static inline int filter3d_blocks(int P)
+{
+	const int b = div_up(P, F3D_THREADS);
+	return b < F3D_MAX_BLOCKS ? b : F3D_MAX_BLOCKS;
+}
+
 }  // namespace gsr
 
 using namespace gsr;
 
 extern "C" {
+
+size_t gsr_filter3d_scratch_bytes(int P)
+{
+	(void)P;   // one word per workgroup of filter3d_kernel, whose grid is capped
+	return (size_t)F3D_MAX_BLOCKS * sizeof(uint32_t);
+}
+
+int gsr_filter3d_compute(int P, const float* means3D, int K, const gsr_filter3d_camera* cameras, float variance, float* filter_3D,
+                         char* scratch, void* stream_)
+{
+	if (P < 0 || K < 0 || !(variance >= 0.f) || !(variance <= FLT_MAX)) return GSR_ERR_INVALID_ARG;
+	if (P == 0) return GSR_OK;
+	if (!means3D || !filter_3D || !scratch || (K > 0 && !cameras) || (reinterpret_cast<uintptr_t>(scratch) & 3)) return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	const int blocks = filter3d_blocks(P);
+	const float sqrt_variance = sqrtf(variance);
+	uint32_t* block_max = reinterpret_cast<uint32_t*>(scratch);
+	GSR_LAUNCH(filter3d_kernel, blocks, F3D_THREADS, stream, P, means3D, K, cameras, sqrt_variance, filter_3D, block_max);
+	GSR_LAUNCH(filter3d_fill_kernel, blocks, F3D_THREADS, stream, P, blocks, (const uint32_t*)block_max, sqrt_variance, filter_3D);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
 
 size_t gsr_seed_scratch_bytes(int width, int height)
 {

@@ -14,6 +14,7 @@
 #include "wave64.h"
 #include "kernels.h"
 #include "shrows.h"
+#include "variant.h"
 
 namespace gsr {
 
@@ -42,7 +43,10 @@ constexpr int FWD_TRIP_GROUPS = GSR_FWD_TRIP_GROUPS;   // row groups the loader 
 
 // AA: GSR_ANTIALIAS (include/gsr.h) -- the opacity of the blend record is multiplied by h = sqrt(det Sigma / det(Sigma + 0.3 I))
 // (kernels.h: antialias_h2).  An instantiation of its own, so that the default kernel is the same code as without the feature.
-template <bool AA>
+// F3: GSR_FILTER_3D (include/gsr.h), p.filter_3D != null -- the filtered scales go into the covariance and the record holds the
+// filtered opacity: one 4-byte load per visible Gaussian.  An instantiation of its own, as in preprocess_bwd_kernel, so that the
+// kernels without the filter stay the same code.
+template <bool AA, bool F3>
 __global__ void __launch_bounds__(PRE_THREADS)
 preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 {
@@ -67,6 +71,7 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 	float pix = 0.f, piy = 0.f, conx = 0.f, cony = 0.f, conz = 0.f;
 	uint32_t rect_lo = 0, rect_hi = 0;
 	float aa_h = 1.0f;   // AA: the opacity compensation of the low-pass
+	float f3_c = 1.0f;   // GSR_FILTER_3D: the opacity factor of the 3-D smoothing filter (kernels.h: filter3d_terms)
 
 	// ---------------- phase 1: geometry (per lane)
 	if (in_range) {
@@ -92,7 +97,8 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 #pragma unroll
 				for (int i = 0; i < 6; i++) c3[i] = p.cov3D_precomp[6 * (size_t)idx + i];
 			} else {
-				compute_cov3D(p.scales, p.rotations, (size_t)idx, p.scale_modifier, p.raw_params, c3);   // (kernels.h: shared with the backward pass)
+				// (kernels.h: shared with the backward pass; with p.filter_3D the filtered scales go into the covariance)
+				compute_cov3D(p.scales, p.rotations, (size_t)idx, p.scale_modifier, p.raw_params, c3, F3 ? p.filter_3D : nullptr, &f3_c);
 			}
 
 			// computeCov2D, forward.cu:74-113
@@ -240,6 +246,7 @@ preprocess_fwd_kernel(const PreprocessParams p, GeometryState g)
 			g.rec[3 * (size_t)idx + 0] = make_float4(pix, piy, conx, cony);
 			float opac = p.opacities[idx];
 			if (p.raw_params & GSR_RAW_OPACITY) opac = 1.0f / (1.0f + expf(-opac));   // getOpacityActivation, :68-71
+			if constexpr (F3) opac = opac * f3_c;   // the filtered opacity, in front of the low-pass's h
 			if constexpr (AA) opac = opac * aa_h;   // every later stage reads the compensated opacity from the record
 			g.rec[3 * (size_t)idx + 1] = make_float4(conz, opac, cr, cg);
 			g.rec[3 * (size_t)idx + 2] = make_float4(cb, __uint_as_float(rect_lo), __uint_as_float(rect_hi), 0.f);
@@ -277,8 +284,11 @@ check_frustum_kernel(int P, const float* __restrict__ means3D, const float* __re
 
 int launch_preprocess_fwd(const PreprocessParams& p, const GeometryState& g, hipStream_t stream)
 {
-	if (p.raw_params & GSR_ANTIALIAS) GSR_LAUNCH(preprocess_fwd_kernel<true>, div_up(p.P, PRE_THREADS), PRE_THREADS, stream, p, g);
-	else GSR_LAUNCH(preprocess_fwd_kernel<false>, div_up(p.P, PRE_THREADS), PRE_THREADS, stream, p, g);
+	const int st = with_flags([&](auto aa, auto f3) -> int {
+		GSR_LAUNCH((preprocess_fwd_kernel<decltype(aa)::value, decltype(f3)::value>), div_up(p.P, PRE_THREADS), PRE_THREADS, stream, p, g);
+		return GSR_OK;
+	}, (p.raw_params & GSR_ANTIALIAS) != 0, p.filter_3D != nullptr);
+	if (st != GSR_OK) return st;
 	GSR_CHECK_LAUNCH();
 	return GSR_OK;
 }

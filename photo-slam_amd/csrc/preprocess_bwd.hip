@@ -315,13 +315,21 @@ __device__ __forceinline__ void pack_view_row(const PreprocessBwdParams& p, int 
 // the opacity, ln 2, W/2 and H/2 -- are applied here, behind the reduction.  With stat_accum set the statistic is the norm of
 // this pair.  Instantiations of their own (not together with PACKED, preprocess_bwd_variant below: not through the multi-GPU
 // exchange), so that the kernels without it stay the same code.
+// F3: GSR_FILTER_3D (include/gsr.h), p.filter_3D != null.  The covariance is recomputed from the filtered scales (compute_cov3D),
+// the record holds o c (times h under AA), and the chain rule of both gradients is applied where the scale gradient is formed -- in
+// front of the REG terms and of the fused geom_adam steps, which stay on the unfiltered values.  An instantiation of its own, so
+// that the kernels without it stay the same code, as in the forward kernel: the eight POSE kernels without the row path sit at 79
+// VGPRs, one below the step from 6 to 5 waves per SIMD, and a kernel-uniform run-time branch (what the GSR_RAW_* activations are)
+// holds registers across the projection in every kernel, the filter on or off (DESIGN.md section 4.5 has the table).  Not together
+// with PACKED (not through the multi-GPU exchange).
 // The instantiations that exist (variant.h): of PACKED, POSE, REG at most one, and ABS not with PACKED -- 7, times ROWS_OK, DEPTH
-// and AA: 56.  launch_preprocess_bwd refuses the other combinations in front of its first launch, as gsr_backward does.
-constexpr bool preprocess_bwd_variant(bool ROWS_OK, bool PACKED, bool DEPTH, bool POSE, bool AA, bool REG, bool ABS)
+// and AA: 56; F3 with the 6 of those 7 that are not PACKED: 48 more, 104.  launch_preprocess_bwd refuses the other combinations in front of its first launch, as gsr_backward does.
+constexpr bool preprocess_bwd_variant(bool ROWS_OK, bool PACKED, bool DEPTH, bool POSE, bool AA, bool REG, bool ABS, bool F3)
 {
-	return PACKED + POSE + REG <= 1 && !(ABS && PACKED);
+	return PACKED + POSE + REG <= 1 && !(ABS && PACKED) && !(F3 && PACKED);
 }
-template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false, bool REG = false, bool ABS = false>
+template <bool ROWS_OK, bool PACKED = false, bool DEPTH = false, bool POSE = false, bool AA = false, bool REG = false, bool ABS = false,
+          bool F3 = false>
 __global__ void __launch_bounds__(PRB_THREADS)
 preprocess_bwd_kernel(const PreprocessBwdParams p)
 {
@@ -375,6 +383,20 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 	float4 ga0 = make_float4(0.f, 0.f, 0.f, 0.f), ga1 = make_float4(0.f, 0.f, 0.f, 0.f);
 	float g_opacity = 0.f;
 	float aa_o = 0.f;   // AA: the record's (compensated) opacity
+	// GSR_FILTER_3D (F3 above the kernel): with it the chain rule of the opacity waits for the scales and g_opacity holds the
+	// gradient of the filtered opacity until then; f3_o: under AA the filtered opacity o c (the record over h)
+	constexpr bool f3 = F3;
+	float f3_o = 0.f;
+	// (with the filter a visible Gaussian's opacity gradient leaves where the scales are at hand, a culled one's -- zero -- where it
+	// always did: two stores under complementary lane masks, 4 bytes per Gaussian, on the filter's path only)
+	auto f3_store_opacity = [&](float g) {
+		if (p.geom.on) {
+			const float go[1] = {g};
+			geom_adam_row<1>(p.geom.opacity, (size_t)idx, go);
+		} else {
+			p.dL_dopacity[idx] = g;
+		}
+	};
 	float abs_x = 0.f, abs_y = 0.f;   // ABS: sum_p |g_p.x|, sum_p |g_p.y| of dL_dmean2D's per-pixel terms g_p
 
 	if (vis) {
@@ -397,6 +419,8 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		}
 		if constexpr (AA) {
 			aa_o = o;   // (the chain rule of the opacity waits for h: below, behind the 2-D covariance)
+		} else if (f3) {
+			// (... and for the filter's c: below, with the scales, where the record's o c is read again -- not held across the projection)
 		} else {
 			// raw logit: d sigmoid = o (1 - o), o = the activated opacity kept in the blend record
 			if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o * (1.0f - o);
@@ -440,7 +464,9 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 			if (PACKED) pack_view_row(p, idx, vis, seen_mask, v0, v1, v2);
 		}
 		if constexpr (!AA) {
-			if (p.geom.on) {
+			if (f3) {
+				if (!vis) f3_store_opacity(0.f);
+			} else if (p.geom.on) {
 				const float go[1] = {g_opacity};
 				geom_adam_row<1>(p.geom.opacity, (size_t)idx, go);
 			} else {
@@ -522,7 +548,7 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 #pragma unroll
 			for (int i = 0; i < 6; i++) c3[i] = p.cov3D[6 * (size_t)idx + i];
 		} else {         // the forward preprocess's own: recomputed, the same bits (kernels.h)
-			compute_cov3D(p.scales, p.rotations, (size_t)idx, p.scale_modifier, p.raw_params, c3);
+			compute_cov3D(p.scales, p.rotations, (size_t)idx, p.scale_modifier, p.raw_params, c3, F3 ? p.filter_3D : nullptr);
 		}
 		float tx = V[0] * mx + V[4] * my + V[8] * mz + V[12];
 		float ty = V[1] * mx + V[5] * my + V[9] * mz + V[13];
@@ -566,10 +592,14 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 			const float o_act = aa_o / h;
 			const float dL_dh = g_opacity * o_act;
 			g_opacity = g_opacity * h;
-			if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o_act * (1.0f - o_act);
-			if constexpr (REG) {   // (the UNcompensated opacity)
-				g_opacity += (p.raw_params & GSR_RAW_OPACITY) ? p.reg_w_opacity * (o_act * (1.0f - o_act)) : p.reg_w_opacity;
-				reg_l[0] = o_act;
+			if (f3) {
+				f3_o = o_act;   // (h compensates the FILTERED opacity: o_act is o c, g_opacity its gradient -- the rest below, with the scales)
+			} else {
+				if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o_act * (1.0f - o_act);
+				if constexpr (REG) {   // (the UNcompensated opacity)
+					g_opacity += (p.raw_params & GSR_RAW_OPACITY) ? p.reg_w_opacity * (o_act * (1.0f - o_act)) : p.reg_w_opacity;
+					reg_l[0] = o_act;
+				}
 			}
 			aa_dh2 = (h2 <= AA_H2_MIN) ? 0.f : dL_dh / (2.0f * h);
 		}
@@ -652,7 +682,9 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 	}
 
 	if constexpr (AA) {
-		if (in_range) {   // (culled: zero, like every other output)
+		if (in_range && f3) {
+			if (!vis) f3_store_opacity(0.f);
+		} else if (in_range) {   // (culled: zero, like every other output)
 			if (p.geom.on) {
 				const float go[1] = {g_opacity};
 				geom_adam_row<1>(p.geom.opacity, (size_t)idx, go);
@@ -695,7 +727,33 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 			sy = expf(sy);
 			sz = expf(sz);
 		}
-		const float s0 = p.scale_modifier * sx, s1 = p.scale_modifier * sy, s2 = p.scale_modifier * sz;
+		// GSR_FILTER_3D: the covariance was formed from the filtered scales s' (kernels.h: filter3d_terms, the forward pass's bits);
+		// sx, sy, sz stay the unfiltered ones (the raw chain rule and the regularisers are theirs).  g_opacity is the gradient of the
+		// filtered opacity o' = o c, c = (r_0 r_1) r_2:
+		//   dL/do   = g_opacity c
+		//   dL/ds_k = ds_k r_k + g_opacity o (r_{k+1} r_{k+2}) F / (a_k s'_k)      (ds'_k/ds_k = r_k, dr_k/ds_k = F / (a_k s'_k))
+		// o is recovered from the record as o' / c (gsr_backward_args carries no opacities); c == 0 -- a scale that is exactly zero
+		// under a non-zero filter -- renders nothing and gets no opacity term.  The opacity is finished HERE and leaves at once, and
+		// only the product g_opacity o crosses the matrix products below; the filter's terms are formed again behind them (the same
+		// bits: three square roots and divisions on this path instead of ten registers held across the products on every path).
+		float fs[3] = {sx, sy, sz};
+		float f3_go = 0.f;
+		if (f3) {
+			float f3_r[3], f3_a[3], f3_F;
+			filter3d_terms(p.filter_3D[idx], sx, sy, sz, fs, f3_r, f3_a, f3_F);
+			const float c = (f3_r[0] * f3_r[1]) * f3_r[2];
+			const float o_rec = AA ? f3_o : p.rec[3 * (size_t)idx + 1].y;
+			const float o_act = c > 0.f ? o_rec / c : 0.f;
+			f3_go = g_opacity * o_act;
+			g_opacity = g_opacity * c;
+			if (p.raw_params & GSR_RAW_OPACITY) g_opacity = g_opacity * o_act * (1.0f - o_act);
+			if constexpr (REG) {   // (the UNfiltered opacity)
+				g_opacity += (p.raw_params & GSR_RAW_OPACITY) ? p.reg_w_opacity * (o_act * (1.0f - o_act)) : p.reg_w_opacity;
+				reg_l[0] = o_act;
+			}
+			f3_store_opacity(g_opacity);
+		}
+		const float s0 = p.scale_modifier * fs[0], s1 = p.scale_modifier * fs[1], s2 = p.scale_modifier * fs[2];
 		// R[c][r]
 		const float R00 = 1.f - 2.f * (y * y + z * z), R01 = 2.f * (x * y - r * z), R02 = 2.f * (x * z + r * y);
 		const float R10 = 2.f * (x * y + r * z), R11 = 1.f - 2.f * (x * x + z * z), R12 = 2.f * (y * z - r * x);
@@ -718,8 +776,20 @@ preprocess_bwd_kernel(const PreprocessBwdParams p)
 		// Rt[c][r] = R[r][c];  dL_dscale.k = dot(Rt[k], dL_dMt[k])
 		// the reference writes dot(Rt[k], dL_dMt[k]) as the scale gradient (backward.cu:318-321); a raw log-scale
 		// adds d exp = the activated scale
-		const float ds0 = R00 * D00 + R10 * D01 + R20 * D02, ds1 = R01 * D10 + R11 * D11 + R21 * D12,
-		            ds2 = R02 * D20 + R12 * D21 + R22 * D22;
+		float ds0 = R00 * D00 + R10 * D01 + R20 * D02, ds1 = R01 * D10 + R11 * D11 + R21 * D12,
+		      ds2 = R02 * D20 + R12 * D21 + R22 * D22;
+		if (f3) {   // (F == 0 adds nothing, and leaves a -0.0f alone)
+			float sp[3], f3_r[3], f3_a[3], f3_F;
+			filter3d_terms(p.filter_3D[idx], sx, sy, sz, sp, f3_r, f3_a, f3_F);
+			ds0 = ds0 * f3_r[0];
+			ds1 = ds1 * f3_r[1];
+			ds2 = ds2 * f3_r[2];
+			if (f3_F > 0.f) {   // ((F / a_k) / s'_k: no product that could underflow)
+				ds0 += f3_go * (f3_r[1] * f3_r[2]) * ((f3_F / f3_a[0]) / sp[0]);
+				ds1 += f3_go * (f3_r[2] * f3_r[0]) * ((f3_F / f3_a[1]) / sp[1]);
+				ds2 += f3_go * (f3_r[0] * f3_r[1]) * ((f3_F / f3_a[2]) / sp[2]);
+			}
+		}
 		const bool raw_s = (p.raw_params & GSR_RAW_SCALING) != 0;
 		g_scale[0] = raw_s ? ds0 * sx : ds0;
 		g_scale[1] = raw_s ? ds1 * sy : ds1;
@@ -1040,6 +1110,8 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 {
 	// ---- every refusal, in front of the first launch (gsr_backward: a refused call has enqueued nothing)
 	const bool abs_sums = p.dL_dmean2D_abs != nullptr;   // the absolute screen-space gradients: slot words [10], [11]
+	const bool filter3d = p.filter_3D != nullptr;         // GSR_FILTER_3D
+	if (filter3d && (p.dL_dcolor_view || p.packed_msg || !p.scales)) return p.scales ? GSR_ERR_UNSUPPORTED : GSR_ERR_INVALID_ARG;
 	if (abs_sums && (p.dL_dcolor_view || p.packed_msg)) return GSR_ERR_UNSUPPORTED;   // not through the multi-GPU exchange
 	const bool factored = p.dL_dcolor_view != nullptr;
 	const bool adam = p.adam_exp_avg != nullptr;
@@ -1062,13 +1134,13 @@ int launch_preprocess_bwd(const PreprocessBwdParams& p, hipStream_t stream)
 	}, depth, abs_sums);
 	if (st != GSR_OK) return st;
 	const int grid = div_up(p.P, PRB_THREADS);
-	st = with_flags([&](auto ro, auto pk, auto dp, auto ps, auto aa, auto rg, auto ab) -> int {
+	st = with_flags([&](auto ro, auto pk, auto dp, auto ps, auto aa, auto rg, auto ab, auto f3) -> int {
 		constexpr bool ROWS_OK = decltype(ro)::value, PACKED = decltype(pk)::value, DEPTH = decltype(dp)::value, POSE = decltype(ps)::value,
-		               AA = decltype(aa)::value, REG = decltype(rg)::value, ABS = decltype(ab)::value,
-		               EXISTS = preprocess_bwd_variant(ROWS_OK, PACKED, DEPTH, POSE, AA, REG, ABS);
-		if constexpr (EXISTS) GSR_LAUNCH((preprocess_bwd_kernel<ROWS_OK, PACKED, DEPTH, POSE, AA, REG, ABS>), grid, PRB_THREADS, stream, p);
+		               AA = decltype(aa)::value, REG = decltype(rg)::value, ABS = decltype(ab)::value, F3 = decltype(f3)::value,
+		               EXISTS = preprocess_bwd_variant(ROWS_OK, PACKED, DEPTH, POSE, AA, REG, ABS, F3);
+		if constexpr (EXISTS) GSR_LAUNCH((preprocess_bwd_kernel<ROWS_OK, PACKED, DEPTH, POSE, AA, REG, ABS, F3>), grid, PRB_THREADS, stream, p);
 		return EXISTS ? GSR_OK : GSR_ERR_UNSUPPORTED;
-	}, rows_ok, p.packed_msg != nullptr, depth, pose, (p.raw_params & GSR_ANTIALIAS) != 0, reg, abs_sums);
+	}, rows_ok, p.packed_msg != nullptr, depth, pose, (p.raw_params & GSR_ANTIALIAS) != 0, reg, abs_sums, filter3d);
 	if (st != GSR_OK) return st;
 	if (rows_ok) GSR_CHECK_LAUNCH();
 	if (p.notify_stream && p.notify_event) {   // dL_dcolor_view is complete: whoever gathers it need not wait for the SH kernel

@@ -215,6 +215,10 @@ class GaussianModel:
         self.exist_since_iter_ = None
         self.sparse_points_xyz_ = None
         self.sparse_points_color_ = None
+        # Mip-Splatting's 3-D smoothing filter (include/gsr.h: GSR_FILTER_3D): a [P] float32 tensor from computeFilter3D, or None.
+        # It belongs to the rows and positions it was computed for: every member that changes the row count, the row order or moves
+        # positions wholesale resets it to None (a stale filter must never be rendered); the renders of TrainStep recompute it.
+        self.filter_3D_ = None
 
     # features_: the [P,16,3] SH leaf.  With lazy Adam steps for the rows of culled Gaussians (FusedAdam.begin_fused_step,
     # gsr_sh_adam_lazy) rows of it may be behind between train steps: every read from outside the fused step brings them up
@@ -259,6 +263,7 @@ class GaussianModel:
     def createFromPcd(self, points, colors, spatial_lr_scale):
         """src/gaussian_model.cpp:114-191: scales from the simple-knn distance (distCUDA2)."""
         self.spatial_lr_scale_ = spatial_lr_scale
+        self.filter_3D_ = None
         pts = points.to(self.device_).float().contiguous()
         n = pts.shape[0]
         # RGB2SH, include/sh_utils.h:138: (rgb - 0.5f) / C0 with the FLOAT constant C0 as a host scalar, exactly the reference's
@@ -322,6 +327,7 @@ class GaussianModel:
         """The append itself: n rows behind the live ones in the arena -- parameters, zero moments, exist_since_iter = iteration, all
         three statistics reset.  new_rows None: the parameter rows are left for a kernel to write (seedFromDepth)."""
         _ = self.features_           # lazy SH Adam: every row up to date before the tensor is re-seated
+        self.filter_3D_ = None       # (the row count changes)
         P = self.xyz_.shape[0]
         dev = self.xyz_.device
         arena = getattr(self, "_arena", None)
@@ -366,10 +372,23 @@ class GaussianModel:
         self.xyz_gradient_accum_, self.denom_, self.max_radii2D_ = stats
 
     # ---- checkpoint interchange, src/gaussian_model.cpp:838-1047
-    def savePly(self, path):
+    def savePly(self, path, fused=False):
+        """The reference's PLY; with filter_3D_ defined a `filter_3D` float property follows the reference's (upstream
+        Mip-Splatting's layout).  fused (needs filter_3D_): the filter is folded into the stored parameters -- log(s') and
+        logit(o') (getScalingWithFilter3D / getOpacityWithFilter3D), no filter_3D property -- so that a viewer without the filter
+        shows the map as it was trained."""
         from . import ply_io
         n = lambda t: t.detach().cpu().numpy()
-        ply_io.save_ply(path, n(self.xyz_), n(self.features_), n(self.opacity_), n(self.scaling_), n(self.rotation_))
+        if fused:
+            if self.filter_3D_ is None:
+                raise RuntimeError("savePly(fused=True) needs filter_3D_ (computeFilter3D)")
+            with torch.no_grad():
+                scaling = torch.log(self.getScalingWithFilter3D())
+                opacity = inverse_sigmoid(self.getOpacityWithFilter3D())
+            ply_io.save_ply(path, n(self.xyz_), n(self.features_), n(opacity), n(scaling), n(self.rotation_))
+            return
+        ply_io.save_ply(path, n(self.xyz_), n(self.features_), n(self.opacity_), n(self.scaling_), n(self.rotation_),
+                        filter_3D=None if self.filter_3D_ is None else n(self.filter_3D_))
 
     @classmethod
     def loadPly(cls, path, device="cuda", sh_degree=3):
@@ -385,7 +404,36 @@ class GaussianModel:
         m.xyz_gradient_accum_ = torch.zeros((P, 1), device=m.device_)
         m.denom_ = torch.zeros((P, 1), device=m.device_)
         m.exist_since_iter_ = torch.zeros(P, dtype=torch.int32, device=m.device_)
+        if d.get("filter_3D") is not None:   # (a map trained with Mip-Splatting's 3-D filter: upstream's extra property)
+            m.filter_3D_ = torch.from_numpy(d["filter_3D"]).to(m.device_).contiguous()
         return m
+
+    # ---- Mip-Splatting's 3-D smoothing filter (include/gsr.h: GSR_FILTER_3D, gsr_filter3d_compute)
+    def computeFilter3D(self, cameras, variance=0.2):
+        """filter_3D_ from the keyframes that observe each Gaussian (gsr_filter3d_compute).  cameras: a [K, 20] float32 tensor of
+        gsr_filter3d_camera rows on the model's device, or a list of (viewmatrix, focal_x, focal_y, width, height) tuples
+        (rasterize_points.filter3DCameras)."""
+        if not torch.is_tensor(cameras):
+            cameras = rp.filter3DCameras(cameras, self.xyz_.device)
+        self.filter_3D_ = rp.filter3D(self.xyz_.detach(), cameras, variance)
+        return self.filter_3D_
+
+    def _filter3d_terms(self):
+        if self.filter_3D_ is None or self.filter_3D_.shape[0] != self.xyz_.shape[0]:
+            raise RuntimeError("filter_3D_ is not defined for this model (computeFilter3D)")
+        s = self.getScalingActivation()
+        sp = torch.sqrt(s * s + (self.filter_3D_ * self.filter_3D_)[:, None])
+        return s, sp
+
+    def getScalingWithFilter3D(self):
+        """s'_k = sqrt(s_k^2 + f^2): the contract of GSR_FILTER_3D in torch, for export and for callers outside the rasterizer"""
+        return self._filter3d_terms()[1]
+
+    def getOpacityWithFilter3D(self):
+        """o' = o (s_0 / s'_0)(s_1 / s'_1)(s_2 / s'_2), [P,1]"""
+        s, sp = self._filter3d_terms()
+        r = s / sp
+        return self.getOpacityActivation() * ((r[:, 0] * r[:, 1]) * r[:, 2])[:, None]
 
     # ---- activations, src/gaussian_model.cpp:48-71
     def getScalingActivation(self):
@@ -546,6 +594,7 @@ class GaussianModel:
         """select: fills a capi.DensifySelectArgs.  Returns the counts [kept, clones, child parents, split, clone-selected,
         rows of the new set]."""
         lib = rp._lib()
+        self.filter_3D_ = None       # (rows leave, join and move: densifyAndPrune, prunePoints, reorderAlongZCurve)
         P = self.xyz_.shape[0]
         dev = self.xyz_.device
         stream = rp._stream_ptr(self.xyz_)
@@ -720,6 +769,7 @@ class GaussianModel:
         their Adam moments are zeroed.  In place: no leaf is replaced and no count is read.  Returns the DEVICE counts tensor
         (int32 [8]: dead rows, destinations written, sources drawn, the largest N)."""
         _ = self.features_           # lazy SH Adam: every row up to date before rows of the tensor and its moments move
+        self.filter_3D_ = None       # (dead rows take the positions of live ones)
         P = self.xyz_.shape[0]
         with torch.no_grad():
             draws = torch.rand(P, generator=generator, device=self.xyz_.device)
@@ -875,6 +925,7 @@ class GaussianModel:
             T_tensor = torch.as_tensor(T, dtype=torch.float32, device=pts.device).transpose(0, 1)
             pts = op.transformPoints(pts, T_tensor)
             scl = self.scaling_.detach() * s
+        self.filter_3D_ = None       # (every position moves)
         self._replace_leaf("xyz_", pts)
         self._replace_leaf("scaling_", scl)
 
@@ -891,6 +942,7 @@ class GaussianModel:
             num_transformed = op.scaleAndTransformThenMarkVisiblePoints(points, rots, point_not_transformed_flags, unstable, diff_pose,
                                                                         kf_world_view_transform, kf_full_proj_transform,
                                                                         num_transformed, scale)
+        self.filter_3D_ = None       # (the keyframe's points move)
         self._replace_leaf("xyz_", points)
         self._replace_leaf("rotation_", rots)
         return num_transformed

@@ -70,6 +70,15 @@ class GaussianRasterizationSettings:
     # and leaves them, as upstream does, in a `.absgrad` attribute ([P,2]) of the means2D / viewspace tensor the forward was given.
     # With view_stats_ the fused statistics accumulate the norm of that pair.  Not together with sh_grad_view_.
     absgrad_: bool = False
+    # extension (GSR_FILTER_3D, include/gsr.h): the [P] float32 3-D smoothing filter of every Gaussian (Mip-Splatting; GaussianModel.
+    # computeFilter3D) -- scales and opacity are filtered inside the rasterizer, forward and backward get the same tensor, the
+    # gradients are those of the unfiltered leaves.  A non-differentiable input; not with cov3D_precomp or sh_grad_view_.  None = off
+    filter_3D_: torch.Tensor = None
+
+
+def _filter_arg(s):
+    """settings.filter_3D_ as the rasterizer takes it: detached (the filter has no gradient), None = off"""
+    return None if s.filter_3D_ is None else s.filter_3D_.detach()
 
 
 def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s, depth=None, alpha=None, means2D=None):
@@ -82,7 +91,7 @@ def _forward(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov
         s.bg_, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier_, cov3Ds_precomp,
         s.viewmatrix_, s.projmatrix_, s.tanfovx_, s.tanfovy_, s.image_height_, s.image_width_, sh, s.sh_degree_,
         s.campos_, s.prefiltered_, s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0), s.sh_adam_,   # sh_adam_: lazy mode brings visible rows up to date first
-        s.workspace_, out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_)
+        s.workspace_, out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_, filter_3D=_filter_arg(s))
     ctx.set_materialize_grads(False)   # (no zero tensor for the unused gradient of `radii`)
     ctx.num_rendered = num_rendered
     # (the forward pass's one host synchronisation has produced the visible count: the regularisers' mean needs it)
@@ -124,7 +133,7 @@ def _backward(ctx, grad_out_color, grad_depth=None, grad_alpha=None, pose=False)
         s.sh_adam_ if (s.sh_grad_view_ is None or (s.sh_adam_ or {}).get("row_step") is not None) else None, s.view_stats_,
         s.geom_adam_, s.training_outputs_only_, dL_ddepth=cont(grad_depth), dL_dalpha=cont(grad_alpha),
         pose_grad=pose, workspace=s.workspace_ if (pose or geom_reg is not None) else None, antialiasing=s.antialiasing_,
-        geom_reg=geom_reg, absgrad=absgrad)
+        geom_reg=geom_reg, absgrad=absgrad, filter_3D=_filter_arg(s))
     if absgrad is not None and ctx.viewspace is not None:
         ctx.viewspace.absgrad = absgrad   # (as upstream: next to .grad on the viewspace tensor)
     # order of src/gaussian_rasterizer.cpp:159-179
@@ -211,7 +220,7 @@ def _rasterize_forward_only(means3D, sh, colors_precomp, opacities, scales, rota
             s.raw_params_ | (capi.CULL_EMPTY_TILES if s.cull_empty_tiles_ else 0) | capi.FORWARD_ONLY, lazy, s.workspace_,
             out_depth=depth, out_alpha=alpha, antialiasing=s.antialiasing_, pixel_weight=c.get("pixel_weight"),
             out_weight_sum=c.get("out_weight_sum"), out_weight_max=c.get("out_weight_max"), out_n_touched=c.get("out_n_touched"),
-            contribution_accumulate=bool(c.get("accumulate", False)))
+            contribution_accumulate=bool(c.get("accumulate", False)), filter_3D=_filter_arg(s))
     if s.render_depth_:
         return color, radii, depth, alpha
     return color, radii

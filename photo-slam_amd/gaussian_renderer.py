@@ -95,7 +95,7 @@ class GaussianRenderer:
     def render(viewpoint_camera, image_height, image_width, pc, pipe, bg_color, override_color=None,
                scaling_modifier=1.0, use_override_color=False, fuse_activations=True, sh_grad_view=None, sh_adam=None, view_stats=None,
                geom_adam=None, training_outputs_only=False, cull_empty_tiles=False, workspace=None, forward_only=False,
-               render_depth=False, antialiasing=False, contribution=None, geom_reg=None, absgrad=False):
+               render_depth=False, antialiasing=False, contribution=None, geom_reg=None, absgrad=False, filter_3D=None):
         """returns (render, viewspace_points, visibility_filter, radii), with render_depth (render, viewspace_points,
         visibility_filter, radii, depth, alpha)
 
@@ -130,7 +130,11 @@ class GaussianRenderer:
         this view sees, added to the gradients inside the rasterizer's backward (TrainStep.opacity_reg_ ...).
 
         absgrad (extension): GaussianRasterizationSettings.absgrad_ -- backward leaves the [P,2] absolute screen-space gradients
-        in viewspace_points.absgrad (as upstream's absgrad does), and fused view_stats accumulate their norm (TrainStep.absgrad_)."""
+        in viewspace_points.absgrad (as upstream's absgrad does), and fused view_stats accumulate their norm (TrainStep.absgrad_).
+
+        filter_3D (extension; None = off): GaussianRasterizationSettings.filter_3D_ -- the [P] 3-D smoothing filter of Mip-Splatting
+        (GSR_FILTER_3D, include/gsr.h; pc.computeFilter3D leaves it in pc.filter_3D_), applied to scales and opacity inside the
+        rasterizer.  A map is rendered with the filter it was trained with.  Not with pipe.compute_cov3D_."""
         env = os.environ.get("GSR_CULL_EMPTY_TILES")
         if env:
             cull_empty_tiles = env == "1"
@@ -165,7 +169,7 @@ class GaussianRenderer:
             geom_adam if raw == 7 else None, bool((geom_adam is not None or training_outputs_only) and raw == 7),
             cull_empty_tiles_=bool(cull_empty_tiles), workspace_=workspace, forward_only_=forward_only,
             render_depth_=bool(render_depth), antialiasing_=bool(antialiasing), contribution_=contribution,
-            geom_reg_=None if forward_only else geom_reg, absgrad_=bool(absgrad) and not forward_only)
+            geom_reg_=None if forward_only else geom_reg, absgrad_=bool(absgrad) and not forward_only, filter_3D_=filter_3D)
         rasterizer = GaussianRasterizer(raster_settings)
         means3D = pc.getXYZ()
         means2D = screenspace_points

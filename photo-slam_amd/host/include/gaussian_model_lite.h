@@ -204,8 +204,26 @@ public:
 	// arena of the rebuilds (gaussian_model_densify.cpp): optional, created on the first rebuild otherwise
 	void reserve(int64_t capacity);
 	// checkpoint interchange with the reference and with Inria viewers (src/ply_io.cpp; src/gaussian_model.cpp:838-1047)
-	void savePly(const std::string& result_path);
+	// With filter_3D_ defined a `filter_3D` float property follows the reference's (upstream Mip-Splatting's layout; loadPly takes it
+	// when present); without it the file is the reference's, byte for byte.  fused (needs filter_3D_): log(s') and logit(o') of
+	// getScalingWithFilter3D / getOpacityWithFilter3D are stored instead and no filter_3D property, so that a viewer without the
+	// filter shows the map as it was trained.
+	void savePly(const std::string& result_path, bool fused = false);
 	void loadPly(const std::string& ply_path);
+
+	// Mip-Splatting's 3-D smoothing filter (include/gsr.h: GSR_FILTER_3D): a [P] float32 tensor, undefined by default.  It belongs to
+	// the rows and positions it was computed for: every member that changes the row count, the row order or moves positions
+	// wholesale (densifyAndPrune, prunePoints, reorderAlongZCurve, increasePcd, seedFromDepth, relocateDead, addNew, the loop-closure
+	// transforms, createFromPcd, loadPly of a file without the property) resets it to undefined -- a stale filter must never be
+	// rendered; TrainStep recomputes it (filter3d_).
+	torch::Tensor filter_3D_;
+	// filter_3D_ from the keyframes that observe each Gaussian (gsr_filter3d_compute): cameras = a float32 [K, 20] tensor of
+	// gsr_filter3d_camera rows on the model's device (rasterize_points.h: filter3DCameraRow)
+	torch::Tensor computeFilter3D(const torch::Tensor& cameras, float variance = 0.2f);
+	// the contract of GSR_FILTER_3D in torch, for export and for callers outside the rasterizer: s'_k = sqrt(s_k^2 + f^2) [P,3] and
+	// o' = o (s_0 / s'_0)(s_1 / s'_1)(s_2 / s'_2) [P,1]; throw while filter_3D_ is undefined
+	torch::Tensor getScalingWithFilter3D();
+	torch::Tensor getOpacityWithFilter3D();
 	torch::Device device_ = torch::kCPU;   // where loadPly() / createFromPcd() put a model that has no tensors yet
 
 	// densifyAndPrune lays the new set out along a Z-order curve of the Gaussians' positions (include/gsr.h:
@@ -427,6 +445,30 @@ public:
 	// covariance.  Unlike the switches above it CHANGES the result; densification and pruning keep their thresholds on the
 	// uncompensated sigmoid(opacity), as upstream does.
 	bool antialiasing_ = false;
+	// Mip-Splatting's 3-D smoothing filter (GSR_FILTER_3D, include/gsr.h), the other half of antialiasing_: every Gaussian is bounded
+	// from below by the sampling interval of the keyframes that observe it.  With filter3d_ on, the model's filter_3D_ is recomputed
+	// from the cameras of setFilterCameras whenever it is undefined (a densification, increasePcd, a loop closure ... reset it) and
+	// every filter3d_interval_ iterations (100: upstream's value, a default to override), before that iteration's render, and EVERY
+	// render of this object carries it through viewExtensions(): renderAndBackward, renderView, renderViewWithDepth, refinePose,
+	// scoreContribution and seedFromDepth's render.  On without cameras: throws.  With a process group: throws.  Densification and
+	// pruning thresholds, the MCMC moves and the regularisers stay on the unfiltered parameters, as upstream.
+	bool filter3d_ = false;
+	int filter3d_interval_ = 100;
+	float filter3d_variance_ = 0.2f;
+	torch::Tensor filter_cameras_;   // [K, 20] float32 rows of gsr_filter3d_camera on the model's device
+	// the keyframes' view matrices with the focal lengths size / (2 tan(FoV / 2)) and the size of each keyframe AS GIVEN: pass it at
+	// the finest level it is trained at.  The model's filter is recomputed before the next render.
+	// K == 0 and a negative filter3d_variance_ are refused by the first render (viewFilter3D, gsr_filter3d_compute), not here.
+	// Works on a model that has no tensors yet (seedFromDepth's start-up): the rows then go to the model's device_.
+	void setFilterCameras(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes);
+	void setFilterCameras(const torch::Tensor& cameras);   // ... or the rows themselves (rasterize_points.h: filter3DCameraRow)
+	// the filter every render of this object carries: undefined with filter3d_ off; else the model's filter_3D_, computed first
+	// when it is undefined (or `recompute`)
+	torch::Tensor viewFilter3D(bool recompute = false);
+	void checkFilter3D() const;   // the two refusals of viewFilter3D alone (a process group; no cameras): throws or does nothing
+	// renders of this object that were handed the filter (every call of viewFilter3D that returned one; RasterizeGaussiansCUDA
+	// refuses a filter whose row count is not the model's): lets a test see that no render went without
+	int64_t filter3d_renders_ = 0;
 	bool cull_empty_tiles_ = false;   // instances of tiles no pixel of which can blend the Gaussian leave the list (a wash on MI355X)
 	// the rasterizer's three scratch buffers, kept across iterations and grown with headroom (rasterize_points.h: RasterWorkspace);
 	// persistent_workspace_ = false: fresh buffers per call, as the reference's resizeFunctional

@@ -110,6 +110,11 @@ struct GaussianRasterizationExtensions {
 	// sqrt(det Sigma / det(Sigma + 0.3 I)) of its projected covariance (upstream's `antialiasing`), in the forward pass, the
 	// forward-only path and the backward pass alike
 	bool antialiasing_ = false;
+	// GSR_FILTER_3D (include/gsr.h): Mip-Splatting's 3-D smoothing filter, a float32 [P] tensor (GaussianModel::computeFilter3D) --
+	// scales and opacity are filtered inside the rasterizer, in the forward pass, the forward-only path and the backward pass alike;
+	// the gradients are those of the unfiltered leaves and the filter gets none (a non-differentiable input: it is not an
+	// argument of the autograd nodes).  Not with cov3D_precomp or sh_grad_view_.  Undefined = off.
+	torch::Tensor filter_3D_;
 	// GSR_CONTRIBUTION (include/gsr.h; rasterize_points.h: RasterForwardExtensions): the per-Gaussian contribution statistics of the
 	// render, left in the caller's [P] tensors (float32 / float32 / int32; any subset), with an optional [H,W] pixel weight map.
 	// Not differentiable: nothing enters the autograd graph.

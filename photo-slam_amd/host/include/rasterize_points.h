@@ -86,6 +86,10 @@ struct RasterForwardExtensions {
 	// with what the tensors hold instead of overwriting it.  Not differentiable: nothing enters the autograd graph.
 	torch::Tensor pixel_weight, out_weight_sum, out_weight_max, out_n_touched;
 	bool contribution_accumulate = false;
+	// GSR_FILTER_3D (include/gsr.h; set by the call when the tensor is defined): the 3-D smoothing filter of every Gaussian, a
+	// contiguous float32 [P] tensor on the device of means3D (filter3D() below computes it).  Scales and opacity are filtered
+	// in-kernel; not with cov3D_precomp.  The backward call must be given the same tensor.  Undefined = off.
+	torch::Tensor filter_3D_;
 };
 
 // ... and to the reference's backward parameter list
@@ -126,7 +130,17 @@ struct RasterBackwardExtensions {
 	// row is written.  With view_stats the statistics accumulate the norm of this pair.  Undefined = off.  Not together with
 	// dL_dcolor_view.
 	torch::Tensor absgrad;
+	// GSR_FILTER_3D: the tensor the forward call was given -- dL_dscales and dL_dopacity are then the gradients of the UNfiltered
+	// scales and opacity; the filter itself gets none.  Undefined = off.  Not together with dL_dcolor_view.
+	torch::Tensor filter_3D_;
 };
+
+// gsr_filter3d_compute (include/gsr.h): the [P] 3-D smoothing filter from the keyframes that observe each Gaussian.  cameras: a
+// contiguous float32 [K, 20] tensor on the device of means3D, rows of gsr_filter3d_camera (viewmatrix[16], focal_x, focal_y, width,
+// height); K may be 0.
+torch::Tensor filter3D(const torch::Tensor& means3D, const torch::Tensor& cameras, float variance = 0.2f);
+// one such row on the host: viewmatrix = the [4,4] world_view_transform_ of the keyframe
+torch::Tensor filter3DCameraRow(const torch::Tensor& viewmatrix, float focal_x, float focal_y, float width, float height);
 
 // (num_rendered, out_color[3,H,W], radii[P] i32, geomBuffer u8, binningBuffer u8, imgBuffer u8)
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> RasterizeGaussiansCUDA(

@@ -30,6 +30,7 @@ void GaussianModel::createFromPcd(torch::Tensor points, torch::Tensor colors, fl
 {
 	torch::NoGradGuard ng;
 	spatial_lr_scale_ = spatial_lr_scale;
+	filter_3D_ = torch::Tensor();   // (rows or positions change: the 3-D smoothing filter is recomputed before it is rendered again)
 	auto pts = points.to(torch::kFloat32).contiguous();
 	const auto n = pts.size(0);
 	const auto o = pts.options();
@@ -109,6 +110,7 @@ void GaussianModel::appendRows(const std::array<torch::Tensor, 5>& rows, int ite
 void GaussianModel::growRows(int64_t n, int iteration, const std::array<torch::Tensor, 5>* rows)
 {
 	torch::NoGradGuard ng;
+	filter_3D_ = torch::Tensor();   // (rows or positions change: the 3-D smoothing filter is recomputed before it is rendered again)
 	const int64_t P = xyz_.size(0);
 	const bool have_state = groups_.size() == 5;
 	bool live = arena_.capacity >= P + n && arena_.params[0][0][0].defined() && arena_.params[0][0][0].device() == xyz_.device();
@@ -256,6 +258,7 @@ void GaussianModel::resetOpacity()
 void GaussianModel::applyScaledTransformation(const float s, torch::Tensor T)
 {
 	torch::NoGradGuard ng;
+	filter_3D_ = torch::Tensor();   // (rows or positions change: the 3-D smoothing filter is recomputed before it is rendered again)
 	// pt <- (s * Ryw * pt + tyw), :385-388: the positions are scaled in place, then transformed with the transposed matrix
 	// (tensor_utils::EigenMatrix2TorchTensor(T.matrix()).transpose(0, 1): transformPoints reads it column-major)
 	auto pts = (xyz_.detach() * s).contiguous();
@@ -275,6 +278,7 @@ void GaussianModel::scaledTransformVisiblePointsOfKeyframe(torch::Tensor& point_
                                                            int& num_transformed, const float scale)
 {
 	torch::NoGradGuard ng;
+	filter_3D_ = torch::Tensor();   // (rows or positions change: the 3-D smoothing filter is recomputed before it is rendered again)
 	auto points = xyz_.detach().clone();                 // (the reference works on the leaf's storage and replaces the leaf anyway)
 	auto rots = getRotationActivation().detach().clone();
 	auto point_unstable_flags = torch::abs(exist_since_iter_ - kf_creation_iter) < stable_num_iter_existence;   // :433-436
@@ -330,6 +334,7 @@ std::array<int64_t, 6> GaussianModel::compact(gsr_densify_select_args& sel, c10:
 {
 	torch::NoGradGuard ng;
 	syncFeatures();   // the gather copies rows of features_ and of its moments: none may be behind (lazy SH Adam)
+	filter_3D_ = torch::Tensor();   // (rows or positions change: the 3-D smoothing filter is recomputed before it is rendered again)
 	const int64_t P = xyz_.size(0);
 	sel.P = static_cast<int>(P);
 	void* stream = hostStream(xyz_);
@@ -513,6 +518,7 @@ torch::Tensor GaussianModel::relocateDead(float min_opacity, c10::optional<at::G
 {
 	torch::NoGradGuard ng;
 	syncFeatures();   // rows of features_ and of its moments move: none may be behind (lazy SH Adam)
+	filter_3D_ = torch::Tensor();   // (rows or positions change: the 3-D smoothing filter is recomputed before it is rendered again)
 	const int64_t P = xyz_.size(0);
 	auto draws = torch::empty({P}, xyz_.options().requires_grad(false)).uniform_(0.0, 1.0, generator);
 	return mcmcCall(P, 0, draws, min_opacity);

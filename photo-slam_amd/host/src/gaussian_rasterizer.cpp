@@ -40,6 +40,7 @@ auto rasterize_forward(const torch::Tensor& means3D, const torch::Tensor& sh, co
 	f.out_depth = depth;
 	f.out_alpha = alpha;
 	f.antialiasing_ = e.antialiasing_;
+	if (e.filter_3D_.defined()) f.filter_3D_ = e.filter_3D_.detach();   // (an input without a gradient)
 	f.pixel_weight = e.pixel_weight_;
 	f.out_weight_sum = e.out_weight_sum_;
 	f.out_weight_max = e.out_weight_max_;
@@ -106,6 +107,7 @@ torch::autograd::tensor_list backward_impl(torch::autograd::AutogradContext* ctx
 	RasterBackwardExtensions b;
 	b.raw_params = e.raw_params_;
 	b.antialiasing_ = e.antialiasing_;
+	if (e.filter_3D_.defined()) b.filter_3D_ = e.filter_3D_.detach();
 	b.dL_dcolor_view = e.sh_grad_view_;
 	// view-factored mode: the SH step follows the exchange (gsr_sh_adam_from_views); sh_adam_ -- its lazy form only -- served
 	// the forward pass (rows this view sees caught up) and lets backward run this step's slice of the rotating catch-up

@@ -249,6 +249,7 @@ std::tuple<torch::Tensor, torch::Tensor> trainer_render(int64_t h, torch::Tensor
 	GaussianRasterizationExtensions ext;
 	ext.raw_params_ = fuse_activations ? 7 : 0;
 	ext.antialiasing_ = t->antialiasing_;
+	ext.filter_3D_ = t->viewFilter3D();
 	auto pkg = GaussianRenderer::render(make_kf(view, proj, campos, fovx, fovy, H, W), (int)H, (int)W, t->gaussians_, pipe,
 	                                    t->background_, override_color, 1.0f, false, ext);
 	return std::make_tuple(std::get<0>(pkg), std::get<3>(pkg));
@@ -366,6 +367,7 @@ torch::Tensor trainer_pose_gradient(int64_t h, torch::Tensor view, torch::Tensor
 	GaussianRasterizationExtensions ext;
 	ext.raw_params_ = 7;
 	ext.antialiasing_ = t->antialiasing_;
+	ext.filter_3D_ = t->viewFilter3D();
 	// (the map frozen for this render: only the camera requires grad)
 	auto frozen = t->gaussians_;
 	std::vector<bool> was;
@@ -404,6 +406,9 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "active_sh_degree") t->gaussians_->active_sh_degree_ = std::min((int)v, t->gaussians_->max_sh_degree_);
 		else if (k == "cull_empty_tiles") t->cull_empty_tiles_ = v != 0.0;
 		else if (k == "antialiasing") t->antialiasing_ = v != 0.0;
+		else if (k == "filter3d") t->filter3d_ = v != 0.0;
+		else if (k == "filter3d_interval") t->filter3d_interval_ = static_cast<int>(v);
+		else if (k == "filter3d_variance") t->filter3d_variance_ = static_cast<float>(v);
 		else if (k == "optimize_exposure") t->optimize_exposure_ = v != 0.0;
 		else if (k == "exposure_lr_init") t->exposure_lr_init_ = static_cast<float>(v);
 		else if (k == "exposure_lr_final") t->exposure_lr_final_ = static_cast<float>(v);
@@ -518,6 +523,29 @@ std::vector<int64_t> trainer_last_densify(int64_t h)
 	return {r.cloned, r.split, r.pruned, r.points};
 }
 void trainer_save_ply(int64_t h, std::string path) { get(h)->gaussians_->savePly(path); }
+// GaussianModel::savePly(path, fused = true): the 3-D smoothing filter folded into the stored scales and opacities
+void trainer_save_ply_fused(int64_t h, std::string path) { get(h)->gaussians_->savePly(path, true); }
+// TrainStep::setFilterCameras with the [K, 20] rows of gsr_filter3d_camera; the model's filter_3D_ ([0] while it is undefined);
+// GaussianModel::computeFilter3D; getScalingWithFilter3D / getOpacityWithFilter3D
+void trainer_set_filter_cameras(int64_t h, torch::Tensor cameras) { get(h)->setFilterCameras(cameras); }
+torch::Tensor trainer_filter_3d(int64_t h)
+{
+	auto t = get(h);
+	auto g = t->gaussians_;
+	return g->filter_3D_.defined() ? g->filter_3D_ : torch::empty({0}, t->background_.options().dtype(torch::kFloat32).requires_grad(false));
+}
+int64_t trainer_filter3d_renders(int64_t h) { return get(h)->filter3d_renders_; }
+torch::Tensor trainer_compute_filter_3d(int64_t h, torch::Tensor cameras, double variance)
+{
+	auto g = get(h)->gaussians_;
+	return g->computeFilter3D(cameras.to(g->xyz_.device(), torch::kFloat32).contiguous(), static_cast<float>(variance));
+}
+std::vector<torch::Tensor> trainer_filtered_activations(int64_t h)
+{
+	auto g = get(h)->gaussians_;
+	torch::NoGradGuard ng;
+	return {g->getScalingWithFilter3D(), g->getOpacityWithFilter3D()};
+}
 // a fresh trainer from a PLY checkpoint (GaussianModel::loadPly): the tensors land on the device of `bg`
 int64_t trainer_create_from_ply(std::string path, int64_t sh_degree, double spatial_lr_scale, torch::Tensor bg)
 {
@@ -760,6 +788,12 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("trainer_last_seed_pixels", &trainer_last_seed_pixels);
 	m.def("trainer_last_densify", &trainer_last_densify);
 	m.def("trainer_save_ply", &trainer_save_ply);
+	m.def("trainer_save_ply_fused", &trainer_save_ply_fused);
+	m.def("trainer_set_filter_cameras", &trainer_set_filter_cameras);
+	m.def("trainer_filter_3d", &trainer_filter_3d);
+	m.def("trainer_filter3d_renders", &trainer_filter3d_renders);
+	m.def("trainer_compute_filter_3d", &trainer_compute_filter_3d);
+	m.def("trainer_filtered_activations", &trainer_filtered_activations);
 	m.def("trainer_create_from_ply", &trainer_create_from_ply);
 	m.def("trainer_reset_opacity", &trainer_reset_opacity);
 	m.def("trainer_apply_scaled_transformation", &trainer_apply_scaled_transformation);

@@ -6,6 +6,9 @@
 // normals zero.  This writer produces the same bytes (tests/test_points_and_ply.py compares against a file written by the
 // reference's own savePly) without tinyply; the reader takes any property order and ignores properties it does not know, as
 // tinyply's request_properties_from_element does, and like the reference sets the active SH degree to the maximum (:1046).
+// A model that carries Mip-Splatting's 3-D smoothing filter (filter_3D_) writes one more float property behind the reference's,
+// `filter_3D` (upstream Mip-Splatting's layout), and the reader takes it when it is there; with the filter undefined the file is the
+// reference's, byte for byte.  savePly(path, true) folds the filter into the stored scales and opacities instead.
 #include <cstdint>
 #include <cstring>
 #include <fstream>
@@ -29,22 +32,36 @@ std::vector<std::string> property_names(int64_t n_rest)
 }
 }  // namespace
 
-void GaussianModel::savePly(const std::string& result_path)
+void GaussianModel::savePly(const std::string& result_path, bool fused)
 {
 	torch::NoGradGuard ng;
 	syncFeatures();
+	if (fused && !filter_3D_.defined()) throw std::runtime_error("savePly(fused = true) needs filter_3D_ (computeFilter3D)");
 	const int64_t P = xyz_.size(0), M = features_.size(1);
 	auto cpu = [](const torch::Tensor& t) { return t.detach().to(torch::kCPU, torch::kFloat32).contiguous(); };
 	auto xyz = cpu(xyz_);
 	auto feat = cpu(features_);                                                          // [P, M, 3], dc first
 	auto f_dc = feat.slice(1, 0, 1).transpose(1, 2).reshape({P, 3});
 	auto f_rest = feat.slice(1, 1, M).transpose(1, 2).reshape({P, 3 * (M - 1)});
-	auto rows = torch::cat({xyz, torch::zeros_like(xyz), f_dc, f_rest, cpu(opacity_).reshape({P, 1}), cpu(scaling_), cpu(rotation_)}, 1)
-	                .contiguous();
+	// fused: log(s') and logit(o') of the filtered activations, no filter_3D property -- a viewer without the filter shows the map
+	// as it was trained
+	torch::Tensor opacity = opacity_, scaling = scaling_;
+	if (fused) {
+		const auto o = getOpacityWithFilter3D();
+		opacity = torch::log(o / (1 - o));
+		scaling = torch::log(getScalingWithFilter3D());
+	}
+	std::vector<torch::Tensor> columns = {xyz, torch::zeros_like(xyz), f_dc, f_rest, cpu(opacity).reshape({P, 1}), cpu(scaling), cpu(rotation_)};
+	auto names = property_names(3 * (M - 1));
+	if (filter_3D_.defined() && !fused) {
+		columns.push_back(cpu(filter_3D_).reshape({P, 1}));
+		names.push_back("filter_3D");
+	}
+	auto rows = torch::cat(columns, 1).contiguous();
 	std::ofstream os(result_path, std::ios::out | std::ios::binary);
 	if (!os) throw std::runtime_error("failed to open " + result_path);
 	os << "ply\nformat binary_little_endian 1.0\nelement vertex " << P << "\n";
-	for (const auto& n : property_names(3 * (M - 1))) os << "property float " << n << "\n";
+	for (const auto& n : names) os << "property float " << n << "\n";
 	os << "end_header\n";
 	os.write(reinterpret_cast<const char*>(rows.data_ptr<float>()), static_cast<std::streamsize>(rows.numel() * sizeof(float)));
 	if (!os) throw std::runtime_error("failed to write " + result_path);
@@ -116,6 +133,7 @@ void GaussianModel::loadPly(const std::string& ply_path)
 	opacity_ = leaf(take({"opacity"}));
 	scaling_ = leaf(take(scale_names));
 	rotation_ = leaf(take(rot_names));
+	filter_3D_ = col.count("filter_3D") ? take({"filter_3D"}).reshape({count}).contiguous().to(dev) : torch::Tensor();
 	const auto o = xyz_.options().requires_grad(false);
 	max_radii2D_ = torch::zeros({count}, o);
 	xyz_gradient_accum_ = torch::zeros({count, 1}, o);

@@ -126,6 +126,33 @@ void* row_ptr(const torch::Tensor& t, const torch::Tensor& means3D, int P, torch
 
 }  // namespace
 
+torch::Tensor filter3DCameraRow(const torch::Tensor& viewmatrix, float focal_x, float focal_y, float width, float height)
+{
+	torch::Tensor row = torch::zeros({20}, torch::kFloat32);
+	row.narrow(0, 0, 16).copy_(viewmatrix.detach().to(torch::kCPU, torch::kFloat32).reshape({16}));
+	float* p = row.data_ptr<float>();
+	p[16] = focal_x; p[17] = focal_y; p[18] = width; p[19] = height;
+	return row;
+}
+
+torch::Tensor filter3D(const torch::Tensor& means3D, const torch::Tensor& cameras, float variance)
+{
+	torch::NoGradGuard no_grad;
+	const int64_t P = means3D.size(0);
+	if (cameras.dim() != 2 || cameras.size(1) != 20 || cameras.scalar_type() != torch::kFloat32 || !cameras.is_contiguous() ||
+	    cameras.device() != means3D.device())
+		throw std::runtime_error("filter3D: cameras must be a contiguous float32 (K, 20) tensor on the device of means3D");
+	torch::Tensor out = torch::empty({P}, means3D.options().dtype(torch::kFloat32));
+	if (P == 0) return out;
+	F32 m3(means3D.detach());
+	torch::Tensor scratch = torch::empty({static_cast<int64_t>(gsr_filter3d_scratch_bytes(static_cast<int>(P)))}, means3D.options().dtype(torch::kByte));
+	const int K = static_cast<int>(cameras.size(0));
+	check(gsr_filter3d_compute(static_cast<int>(P), m3.ptr, K, K ? reinterpret_cast<const gsr_filter3d_camera*>(cameras.data_ptr<float>()) : nullptr,
+	                           variance, out.data_ptr<float>(), reinterpret_cast<char*>(scratch.data_ptr()), current_stream(means3D)),
+	      "filter3D");
+	return out;
+}
+
 double covisibility(const torch::Tensor& n_touched_a, const torch::Tensor& n_touched_b)
 {
 	const auto a = n_touched_a > 0, b = n_touched_b > 0;
@@ -235,6 +262,10 @@ std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torc
 			throw std::runtime_error("pixel_weight / contribution_accumulate need one of out_weight_sum, out_weight_max, out_n_touched");
 		a.pixel_weight = map_ptr(ext.pixel_weight, means3D, H, W, "pixel_weight");
 		a.contribution_accumulate = ext.contribution_accumulate ? 1 : 0;
+		if (ext.filter_3D_.defined()) {
+			a.filter_3D = static_cast<const float*>(row_ptr(ext.filter_3D_, means3D, P, torch::kFloat32, "filter_3D"));
+			a.raw_params |= GSR_FILTER_3D;
+		}
 		gsr_sh_adam adam{};
 		gsr_sh_adam_lazy lazy{};
 		if (ext.sh_adam && ext.sh_adam->row_step.defined()) {   // lazy SH Adam: the forward pass brings visible rows up to date (in place)
@@ -413,6 +444,10 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
 		a.dL_dscale = (has_scales && !geom) ? dL_dscales.data_ptr<float>() : nullptr;
 		a.dL_drot = (has_scales && !geom) ? dL_drotations.data_ptr<float>() : nullptr;
 		a.raw_params = ext.raw_params | (ext.antialiasing_ ? GSR_ANTIALIAS : 0);
+		if (ext.filter_3D_.defined()) {
+			a.filter_3D = static_cast<const float*>(row_ptr(ext.filter_3D_, means3D, P, torch::kFloat32, "filter_3D"));
+			a.raw_params |= GSR_FILTER_3D;
+		}
 		gsr_geom_adam ga{};
 		if (geom) {
 			gsr_adam_tensor* ts[4] = {&ga.xyz, &ga.opacity, &ga.scaling, &ga.rotation};

@@ -64,6 +64,28 @@ torch::Tensor GaussianModel::getCovarianceActivation(int scaling_modifier)
 	                     cov.select(1, 1).select(1, 1), cov.select(1, 1).select(1, 2), cov.select(1, 2).select(1, 2)}, 1);
 }
 
+// Mip-Splatting's 3-D smoothing filter (include/gsr.h: GSR_FILTER_3D, gsr_filter3d_compute)
+torch::Tensor GaussianModel::computeFilter3D(const torch::Tensor& cameras, float variance)
+{
+	filter_3D_ = filter3D(xyz_.detach(), cameras, variance);
+	return filter_3D_;
+}
+
+torch::Tensor GaussianModel::getScalingWithFilter3D()
+{
+	if (!filter_3D_.defined() || filter_3D_.size(0) != xyz_.size(0))
+		throw std::runtime_error("filter_3D_ is not defined for this model (computeFilter3D)");
+	auto s = getScalingActivation();
+	return torch::sqrt(s * s + (filter_3D_ * filter_3D_).unsqueeze(1));
+}
+
+torch::Tensor GaussianModel::getOpacityWithFilter3D()
+{
+	auto sp = getScalingWithFilter3D();
+	auto r = getScalingActivation() / sp;
+	return getOpacityActivation() * ((r.select(1, 0) * r.select(1, 1)) * r.select(1, 2)).unsqueeze(1);
+}
+
 void GaussianModel::trainingSetup(const GaussianOptimizationParams& opt)
 {
 	opt_ = opt;
@@ -204,9 +226,52 @@ GaussianRasterizationExtensions TrainStep::viewExtensions()
 	ext.raw_params_ = 7;
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
 	ext.antialiasing_ = antialiasing_;
+	ext.filter_3D_ = viewFilter3D();
 	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
 	ext.forward_only_ = true;
 	return ext;
+}
+
+void TrainStep::setFilterCameras(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes)
+{
+	std::vector<torch::Tensor> rows;
+	for (const auto& kf : keyframes) {
+		// the rasterizer's own tan(FoV / 2) (GaussianRenderer::render): focal = size / (2 tan)
+		const double tanfovx = std::tan(kf->FoVx_ * 0.5f), tanfovy = std::tan(kf->FoVy_ * 0.5f);
+		const int W = kf->image_width_, H = kf->image_height_;
+		rows.push_back(filter3DCameraRow(kf->world_view_transform_, static_cast<float>(W / (2.0 * tanfovx)), static_cast<float>(H / (2.0 * tanfovy)),
+		                                 static_cast<float>(W), static_cast<float>(H)));
+	}
+	setFilterCameras(rows.empty() ? torch::zeros({0, 20}, torch::kFloat32) : torch::stack(rows));
+}
+
+void TrainStep::setFilterCameras(const torch::Tensor& cameras)
+{
+	if (cameras.dim() != 2 || cameras.size(1) != 20) throw std::runtime_error("setFilterCameras: a [K, 20] tensor of gsr_filter3d_camera rows");
+	// (a model without tensors yet -- seedFromDepth makes the first ones -- names its device itself)
+	const torch::Device dev = gaussians_->xyz_.defined() ? gaussians_->xyz_.device() : gaussians_->device_;
+	filter_cameras_ = cameras.detach().to(dev, torch::kFloat32).contiguous();
+	gaussians_->filter_3D_ = torch::Tensor();
+}
+
+void TrainStep::checkFilter3D() const
+{
+	if (!filter3d_) return;
+	if (process_group_ || factored_exchange_) throw std::runtime_error("TrainStep: filter3d_ is not supported with a process group");
+	if (!filter_cameras_.defined() || filter_cameras_.size(0) == 0)
+		throw std::runtime_error("TrainStep: filter3d_ is on and no cameras are registered (setFilterCameras)");
+}
+
+torch::Tensor TrainStep::viewFilter3D(bool recompute)
+{
+	if (!filter3d_) return torch::Tensor();
+	checkFilter3D();
+	auto& g = gaussians_;
+	if (!g->xyz_.defined()) return torch::Tensor();   // (no Gaussian yet: nothing is rendered)
+	if (filter_cameras_.device() != g->xyz_.device()) filter_cameras_ = filter_cameras_.to(g->xyz_.device());
+	if (recompute || !g->filter_3D_.defined() || g->filter_3D_.size(0) != g->xyz_.size(0)) g->computeFilter3D(filter_cameras_, filter3d_variance_);
+	filter3d_renders_++;
+	return g->filter_3D_;
 }
 
 torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf, bool apply_exposure)
@@ -382,6 +447,7 @@ std::tuple<torch::Tensor, torch::Tensor> TrainStep::refinePose(std::shared_ptr<G
 	ext.raw_params_ = 7;
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
 	ext.antialiasing_ = antialiasing_;
+	ext.filter_3D_ = viewFilter3D();
 	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
 	std::vector<torch::Tensor> losses;
 	torch::Tensor override_color;
@@ -435,6 +501,7 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		throw std::runtime_error("TrainStep: mcmc_ is not supported with a process group");
 	if (absgrad_ && (process_group_ || factored_exchange_))
 		throw std::runtime_error("TrainStep: absgrad_ is not supported with a process group");
+	checkFilter3D();   // (refuses a process group and a missing camera list before anything of the step happens)
 	last_reg_losses_ = torch::Tensor();
 	last_absgrad_ = torch::Tensor();
 	auto& g = gaussians_;
@@ -487,6 +554,8 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	ext.sh_grad_view_ = sh_grad_view_;
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
 	ext.antialiasing_ = antialiasing_;
+	// the 3-D smoothing filter: recomputed when undefined and every filter3d_interval_ iterations, before this iteration's render
+	ext.filter_3D_ = viewFilter3D(filter3d_interval_ > 0 && iteration_ % filter3d_interval_ == 0);
 	ext.workspace_ = persistent_workspace_ ? &workspace_ : nullptr;
 	torch::Tensor reg_loss;
 	if (reg) {

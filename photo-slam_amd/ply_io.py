@@ -1,7 +1,9 @@
 """Binary-PLY checkpoint interchange with the reference (GaussianModel::savePly / loadPly,
 src/gaussian_model.cpp:838-1047) and with Inria 3DGS viewers: one `vertex` element of float32 properties
   x y z  nx ny nz  f_dc_0..2  f_rest_0..(3*(M-1)-1)  opacity  scale_0..2  rot_0..3
-holding the RAW (pre-activation) parameters; f_dc / f_rest are channel-major (features.transpose(1, 2).flatten(1))."""
+holding the RAW (pre-activation) parameters; f_dc / f_rest are channel-major (features.transpose(1, 2).flatten(1)).
+A map that carries Mip-Splatting's 3-D smoothing filter has one more float property behind them, `filter_3D` (upstream
+Mip-Splatting's layout); without it the file is the reference's, byte for byte."""
 import numpy as np
 
 
@@ -10,13 +12,16 @@ def _names(n_rest):
             ["opacity"] + [f"scale_{i}" for i in range(3)] + [f"rot_{i}" for i in range(4)])
 
 
-def save_ply(path, xyz, features, opacity, scaling, rotation):
-    """features: [P, M, 3] (dc first).  All arrays float32 numpy (raw parameters)."""
+def save_ply(path, xyz, features, opacity, scaling, rotation, filter_3D=None):
+    """features: [P, M, 3] (dc first).  All arrays float32 numpy (raw parameters).  filter_3D: [P] or None (no such property)."""
     P, M = features.shape[0], features.shape[1]
     f_dc = np.transpose(features[:, :1, :], (0, 2, 1)).reshape(P, 3)
     f_rest = np.transpose(features[:, 1:, :], (0, 2, 1)).reshape(P, 3 * (M - 1))
     rows = np.concatenate([xyz, np.zeros_like(xyz), f_dc, f_rest, opacity.reshape(P, 1), scaling, rotation], axis=1)
     names = _names(3 * (M - 1))
+    if filter_3D is not None:
+        rows = np.concatenate([rows, np.asarray(filter_3D, np.float32).reshape(P, 1)], axis=1)
+        names = names + ["filter_3D"]
     header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {P}\n" + \
         "".join(f"property float {n}\n" for n in names) + "end_header\n"
     with open(path, "wb") as f:
@@ -25,7 +30,7 @@ def save_ply(path, xyz, features, opacity, scaling, rotation):
 
 
 def load_ply(path, max_sh_degree=3):
-    """Returns dict(xyz, features [P,M,3], opacity [P,1], scaling, rotation) of float32 arrays."""
+    """Returns dict(xyz, features [P,M,3], opacity [P,1], scaling, rotation, filter_3D [P] or None) of float32 arrays."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError("not a PLY file")
@@ -56,4 +61,5 @@ def load_ply(path, max_sh_degree=3):
     features = np.concatenate([np.transpose(f_dc, (0, 2, 1)), np.transpose(f_rest, (0, 2, 1))], axis=1)
     return dict(xyz=take(["x", "y", "z"]).copy(), features=np.ascontiguousarray(features, np.float32),
                 opacity=take(["opacity"]).copy(), scaling=take([f"scale_{i}" for i in range(3)]).copy(),
-                rotation=take([f"rot_{i}" for i in range(4)]).copy())
+                rotation=take([f"rot_{i}" for i in range(4)]).copy(),
+                filter_3D=np.ascontiguousarray(data[:, col["filter_3D"]], np.float32) if "filter_3D" in col else None)

@@ -117,7 +117,7 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
                            viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
                            prefiltered, raw_params=0, sh_adam=None, workspace=None, out_depth=None, out_alpha=None,
                            antialiasing=False, pixel_weight=None, out_weight_sum=None, out_weight_max=None, out_n_touched=None,
-                           contribution_accumulate=False):
+                           contribution_accumulate=False, filter_3D=None):
     """raw_params (extension, default 0 = reference contract): GSR_RAW_* mask -- opacity / scales / rotations are the
     model's raw parameters and are activated in-kernel (include/gsr.h).  With capi.FORWARD_ONLY in it the call renders the same
     image and radii without preparing anything for a backward pass: the returned buffers are then NOT valid input to
@@ -136,7 +136,11 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
     GSR_CONTRIBUTION -- any of them sets the bit): sum and maximum over the pixels that blend the Gaussian of w alpha T, and the
     number of those pixels with w != 0.  pixel_weight: the [H, W] float32 map w (finite, >= 0), None = ones.
     contribution_accumulate: add to / take the maximum with what the tensors hold instead of overwriting it.  Nothing of this is
-    differentiable; the return tuple is the same."""
+    differentiable; the return tuple is the same.
+    filter_3D (extension, default None = off): a contiguous float32 [P] tensor on the device of means3D, the 3-D smoothing filter
+    of every Gaussian (include/gsr.h: GSR_FILTER_3D -- the keyword sets the bit; filter3D() below computes it from the keyframes).
+    Scales and opacity are filtered in-kernel; not with cov3D_precomp.  The backward call must be given the same tensor.  Not
+    differentiable."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # AT_ERROR, rasterize_points.cu:57-59
     lib = _lib()
@@ -178,6 +182,9 @@ def RasterizeGaussiansCUDA(background, means3D, colors, opacity, scales, rotatio
             raise RuntimeError("pixel_weight / contribution_accumulate need one of out_weight_sum, out_weight_max, out_n_touched")
         a.pixel_weight = _image_arg(pixel_weight, H, W, dev, "pixel_weight")
         a.contribution_accumulate = int(bool(contribution_accumulate))
+        if filter_3D is not None:
+            a.filter_3D = _row_arg(filter_3D, P, torch.float32, dev, "filter_3D")
+            a.raw_params |= capi.FILTER_3D
         if sh_adam is not None and sh_adam.get("row_step") is not None:
             if sh is None or not sh.is_contiguous() or sh.dtype != torch.float32:
                 raise RuntimeError("lazy sh_adam needs a contiguous float32 sh tensor (it is updated in place)")
@@ -228,7 +235,7 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
                                    geomBuffer, R, binningBuffer, imageBuffer, raw_params=0, dL_dcolor_view=None, sh_adam=None,
                                    view_stats=None, geom_adam=None, training_outputs_only=False, packed_view=None,
                                    dL_ddepth=None, dL_dalpha=None, pose_grad=False, workspace=None, antialiasing=False,
-                                   geom_reg=None, absgrad=None):
+                                   geom_reg=None, absgrad=None, filter_3D=None):
     """dL_dcolor_view (extension, default None = reference contract): a [P,3] float tensor that receives the clamp-masked
     colour gradient; dL_dsh is then NOT computed and None is returned in its place (view-factored gradient exchange,
     shGradFromViews below).
@@ -262,7 +269,10 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
     absgrad (extension, default None): a contiguous float32 [P, 2] tensor on the device of means3D that receives the absolute
     screen-space gradients (gsr_backward_args.dL_dmean2D_abs: per Gaussian the sums over its pixels of |d/dmean2D.x| and
     |d/dmean2D.y| of each pixel's own term, AbsGS / gsplat's absgrad); every row is written.  With view_stats the statistics then
-    accumulate the norm of this pair instead of |dL_dmeans2D.xy|.  Not together with dL_dcolor_view.  The return tuple is the same."""
+    accumulate the norm of this pair instead of |dL_dmeans2D.xy|.  Not together with dL_dcolor_view.  The return tuple is the same.
+    filter_3D (extension, default None): the tensor the forward call was given (GSR_FILTER_3D) -- dL_dscales and dL_dopacity are
+    then the gradients of the UNfiltered scales and opacity (the filter's chain rule is applied in-kernel, in front of geom_reg and
+    geom_adam); the filter itself gets no gradient.  Not together with dL_dcolor_view."""
     lib = _lib()
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
@@ -345,6 +355,9 @@ def RasterizeGaussiansBackwardCUDA(background, means3D, radii, colors, scales, r
         a.dL_ddepth = _image_arg(dL_ddepth, H, W, dev, "dL_ddepth")
         a.dL_dalpha = _image_arg(dL_dalpha, H, W, dev, "dL_dalpha")
         a.dL_dmean2D_abs = absgrad.data_ptr() if absgrad is not None else None
+        if filter_3D is not None:
+            a.filter_3D = _row_arg(filter_3D, P, torch.float32, dev, "filter_3D")
+            a.raw_params |= capi.FILTER_3D
         if packed_view is not None:
             # (message, capacity_rows): a message packViewPlan() prepared -- backward writes its rows and header (gsr_backward_args.packed_view)
             msg, cap = packed_view
@@ -605,6 +618,42 @@ def markVisible(means3D, viewmatrix, projmatrix):
         st = lib.gsr_mark_visible(P, p1, p2, p3, C.c_void_p(present.data_ptr()), _stream_ptr(means3D))
         capi.check(lib, st, "markVisible")
     return present
+
+
+def filter3DCameras(cameras, device):
+    """[K, 20] float32 rows of gsr_filter3d_camera (viewmatrix[16], focal_x, focal_y, width, height) on `device` from
+    (viewmatrix, focal_x, focal_y, width, height) tuples; viewmatrix: the [4,4] tensor or array the rasterizer takes"""
+    rows = torch.zeros((len(cameras), 20), dtype=torch.float32)
+    for k, (view, fx, fy, w, h) in enumerate(cameras):
+        rows[k, :16] = torch.as_tensor(view, dtype=torch.float32).detach().cpu().reshape(16)
+        rows[k, 16:] = torch.tensor([float(fx), float(fy), float(w), float(h)])
+    return rows.to(device)
+
+
+def filter3D(means3D, cameras, variance=0.2, out=None):
+    """gsr_filter3d_compute (include/gsr.h): the [P] 3-D smoothing filter of GSR_FILTER_3D from the keyframes that observe each
+    Gaussian -- sqrt(variance) times the smallest z / max(focal_x, focal_y) over the cameras that see it (15 % margin, z > 0.2);
+    Gaussians no camera sees get the largest value.  cameras: a contiguous float32 [K, 20] tensor on the device of means3D
+    (filter3DCameras builds it), K may be 0."""
+    lib = _lib()
+    P = means3D.size(0)
+    dev = means3D.device
+    _check_device(lib, means3D, cameras)
+    if cameras.dim() != 2 or cameras.size(1) != 20 or cameras.dtype != torch.float32 or not cameras.is_contiguous() or cameras.device != dev:
+        raise RuntimeError("cameras must be a contiguous float32 (K, 20) tensor on the device of means3D")
+    if out is None:
+        out = torch.empty((P,), dtype=torch.float32, device=dev)
+    elif out.shape != (P,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError("out must be a contiguous float32 (num_points,) tensor on the device of means3D")
+    if P != 0:
+        with torch.no_grad():
+            k, p = _ptr(means3D.detach().float())
+            scratch = torch.empty((int(lib.gsr_filter3d_scratch_bytes(P)),), dtype=torch.uint8, device=dev)
+            K = cameras.size(0)
+            st = lib.gsr_filter3d_compute(P, p, K, C.c_void_p(cameras.data_ptr()) if K else None, float(variance),
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), _stream_ptr(means3D))
+            capi.check(lib, st, "filter3D")
+    return out
 
 
 def distCUDA2(points):

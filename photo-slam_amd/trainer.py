@@ -209,7 +209,7 @@ def allreduce_mean(tensors, world_size):
 class TrainStep:
     def __init__(self, gaussians, opt, pipe, background, world_size=1, cameras_extent=None, densify=False,
                  densify_min_opacity=0.005, prune_big_point_after_iter=30000, seed=0, factored_exchange=True, fused_sh_adam=True,
-                 lazy_sh_adam_window=32, fused_geom_adam=True, cull_empty_tiles=False, antialiasing=False):
+                 lazy_sh_adam_window=32, fused_geom_adam=True, cull_empty_tiles=False, antialiasing=False, filter3d=False):
         # the rasterizer's scratch buffers, kept across iterations and grown with headroom (rasterize_points.RasterWorkspace);
         # persistent_workspace_ = False: fresh buffers per call, as the reference's resizeFunctional
         from . import rasterize_points as rp
@@ -222,6 +222,16 @@ class TrainStep:
         # keyframe's pyramid level has, render_view, refinePose -- compensates the opacity for the 0.3 px low-pass.  Densification and
         # pruning keep their thresholds on the uncompensated sigmoid(opacity), as upstream does.
         self.antialiasing_ = bool(antialiasing)
+        # Mip-Splatting's 3-D smoothing filter (GSR_FILTER_3D, include/gsr.h), the other half of antialiasing_: every Gaussian is
+        # bounded from below by the sampling interval of the keyframes that observe it.  With filter3d_ on, the model's filter_3D_
+        # is recomputed from the cameras of setFilterCameras whenever it is undefined (a densification, increasePcd, a loop closure
+        # ... reset it) and every filter3d_interval_ iterations (100: upstream's value, a default to override), before that
+        # iteration's render, and EVERY render of this object carries it.  Densification and pruning thresholds, the MCMC moves
+        # and the regularisers stay on the unfiltered parameters, as upstream.
+        self.filter3d_ = bool(filter3d)
+        self.filter3d_interval_ = 100
+        self.filter3d_variance_ = 0.2
+        self.filter_cameras_ = None     # [K, 20] float32 rows of gsr_filter3d_camera on the model's device (setFilterCameras)
         self.cull_empty_tiles_ = bool(cull_empty_tiles)   # option of this object; GSR_CULL_EMPTY_TILES only overrides (gaussian_renderer.py)
         self.gaussians_, self.opt_, self.pipe_, self.background_ = gaussians, opt, pipe, background
         self.cameras_extent_ = cameras_extent if cameras_extent is not None else gaussians.spatial_lr_scale_
@@ -332,6 +342,44 @@ class TrainStep:
                                           12, lr, 0.9, 0.999, 1e-15, kf.exposure_step_, 0, 0, lr, rp._stream_ptr(e)),
                    "gsr_adam_step")
 
+    def setFilterCameras(self, cameras):
+        """The keyframes the 3-D smoothing filter is derived from: a list of GaussianKeyframes (focal lengths W / (2 tanfovx),
+        H / (2 tanfovy) and the size of the keyframe as given: pass it at the finest level it is trained at) or of (viewmatrix,
+        focal_x, focal_y, width, height) tuples.  The model's filter is recomputed before the next render.  An empty list and a
+        negative filter3d_variance_ are refused by the first render, not here.  Works on a model that has no tensors yet
+        (seedFromDepth's start-up): the rows then go to the model's device_."""
+        from . import rasterize_points as rp
+        rows = []
+        for c in cameras:
+            if isinstance(c, (tuple, list)):
+                rows.append(tuple(c))
+            else:
+                W, H = int(c.image_width_), int(c.image_height_)
+                rows.append((c.world_view_transform_, W / (2.0 * c.tanfovx_), H / (2.0 * c.tanfovy_), W, H))
+        g = self.gaussians_
+        self.filter_cameras_ = rp.filter3DCameras(rows, g.xyz_.device if getattr(g, "xyz_", None) is not None else g.device_)
+        g.filter_3D_ = None
+
+    def viewFilter3D(self, recompute=False):
+        """the filter every render of this object carries: None with filter3d_ off; else the model's filter_3D_, computed first when
+        it is undefined (or `recompute`)"""
+        if not self.filter3d_:
+            return None
+        if self.world_size_ > 1:
+            raise RuntimeError("TrainStep: filter3d_ is not supported with a process group")
+        if self.filter_cameras_ is None or self.filter_cameras_.shape[0] == 0:
+            raise RuntimeError("TrainStep: filter3d_ is on and no cameras are registered (setFilterCameras)")
+        g = self.gaussians_
+        if getattr(g, "xyz_", None) is None:   # (no Gaussian yet: nothing is rendered)
+            return None
+        if self.filter_cameras_.device != g.xyz_.device:
+            self.filter_cameras_ = self.filter_cameras_.to(g.xyz_.device)
+        f = g.filter_3D_
+        if recompute or f is None or f.shape[0] != g.xyz_.shape[0]:
+            with torch.no_grad():
+                f = g.computeFilter3D(self.filter_cameras_, self.filter3d_variance_)
+        return f
+
     def render_view(self, viewpoint_cam, with_depth=False, apply_exposure=False):
         """A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe):
         forward-only (GSR_FORWARD_ONLY), into the trainer's second workspace, with lazily stepped SH rows read as they are --
@@ -343,7 +391,7 @@ class TrainStep:
                 viewpoint_cam, viewpoint_cam.image_height_, viewpoint_cam.image_width_, self.gaussians_, self.pipe_,
                 self.background_, cull_empty_tiles=self.cull_empty_tiles_,
                 workspace=self.view_workspace_ if self.persistent_workspace_ else None, forward_only=True,
-                render_depth=bool(with_depth), antialiasing=self.antialiasing_)
+                render_depth=bool(with_depth), antialiasing=self.antialiasing_, filter_3D=self.viewFilter3D())
         image = out[0]
         if apply_exposure and getattr(viewpoint_cam, "exposure_", None) is not None:
             image = loss_utils.apply_exposure(image, viewpoint_cam.exposure_)
@@ -371,7 +419,8 @@ class TrainStep:
                 out = GaussianRenderer.render(kf, kf.image_height_, kf.image_width_, self.gaussians_, self.pipe_, self.background_,
                                               cull_empty_tiles=self.cull_empty_tiles_,
                                               workspace=self.view_workspace_ if self.persistent_workspace_ else None,
-                                              forward_only=True, antialiasing=self.antialiasing_, contribution=c)
+                                              forward_only=True, antialiasing=self.antialiasing_, contribution=c,
+                                              filter_3D=self.viewFilter3D())
                 seen += (out[3] > 0).to(torch.int32)
         return wsum, wmax, touched, seen
 
@@ -451,6 +500,7 @@ class TrainStep:
         if self.pipe_.convert_SHs_ or self.pipe_.compute_cov3D_:
             raise RuntimeError("refinePose renders the raw model (convert_SHs_ / compute_cov3D_ must be off)")
         xyz, sh, opacity, scaling, rotation = self._frozen_map()
+        filter_3D = self.viewFilter3D()
         pose = PoseDelta.from_keyframe(viewpoint_cam)
         dev = xyz.device
         lr = torch.tensor([lr_translation] * 3 + [lr_rotation] * 3, dtype=torch.float32, device=dev)
@@ -470,7 +520,7 @@ class TrainStep:
                 kf.image_height_, kf.image_width_, kf.tanfovx_, kf.tanfovy_, self.background_, 1.0, kf.world_view_transform_,
                 kf.full_proj_transform_, g.active_sh_degree_, kf.camera_center_, False, 7, cull_empty_tiles_=cull,
                 workspace_=self.view_workspace_ if self.persistent_workspace_ else None, render_depth_=use_depth,
-                antialiasing_=self.antialiasing_)
+                antialiasing_=self.antialiasing_, filter_3D_=filter_3D)
             out = GaussianRasterizer(s)(xyz, means2D, opacity, True, False, True, True, False, sh, None, scaling, rotation, None)
             loss = loss_utils.fused_l1_ssim_loss(out[0], gt_image, eff_mask, opt.lambda_dssim_, is_root=True, exposure=exposure)
             if use_depth:
@@ -528,6 +578,8 @@ class TrainStep:
         self.last_reg_losses = None
         if self.absgrad_ and self.world_size_ > 1:
             raise RuntimeError("TrainStep: absgrad_ is not supported with a process group")
+        if self.filter3d_:
+            self.viewFilter3D()   # (refuses a process group and a missing camera list before anything of the step happens)
         self.iteration_ += 1
         it = self.iteration_
         g.updateLearningRate(it if position_lr_step is None else min(int(position_lr_step), opt.position_lr_max_steps_))   # :661-674
@@ -576,7 +628,8 @@ class TrainStep:
                 training_outputs_only=True,   # the statistics are fused (or over): nobody reads the viewspace gradient
                 cull_empty_tiles=self.cull_empty_tiles_, workspace=self.workspace_ if self.persistent_workspace_ else None,
                 render_depth=use_depth, antialiasing=self.antialiasing_, geom_reg=geom_reg,
-                absgrad=bool(self.absgrad_) and view_stats is not None)   # (only the statistics read it)
+                absgrad=bool(self.absgrad_) and view_stats is not None,   # (only the statistics read it)
+                filter_3D=self.viewFilter3D(recompute=bool(self.filter3d_interval_) and it % int(self.filter3d_interval_) == 0))
             rendered_image, viewspace_point_tensor, visibility_filter, radii = out[:4]
         finally:
             g._in_lazy_step = False
