@@ -57,6 +57,10 @@ struct AdamGroup {
 	int step = 0;   // per parameter, as torch::optim::AdamParamState: advances only when the parameter has a gradient
 };
 
+// runs f on every way out of the scope it is declared in, an exception's included
+template <class F> struct ScopeExit { F f; ~ScopeExit() { f(); } };
+template <class F> ScopeExit(F) -> ScopeExit<F>;
+
 class GaussianModel {
 public:
 	GaussianModel(int sh_degree, torch::Tensor xyz, torch::Tensor features, torch::Tensor opacity, torch::Tensor scaling,
@@ -182,6 +186,11 @@ public:
 	//   LazyTaken  the counter's step has been taken: its rates are the newest entry of the history (what shAdamFlush wants)
 	enum class ShStep { Eager, Lazy, LazyTaken };
 	ShAdamStep featuresAdamStep(ShStep which) const;
+	// A step of the SH tensor taken outside optimizerStepGroup(1) (the Python optimizer's begin_fused_step / end_fused_step).  begin:
+	// with lazy, the rows' state is created if there is none (a state of another window is flushed first); the counter advances;
+	// returns featuresAdamStep(Lazy or Eager).  end (lazy, the step taken): its learning rates join the history, trimmed to the window.
+	ShAdamStep beginFeaturesStep(bool lazy, int window);
+	void endFeaturesStep(const ShAdamStep& taken);
 	torch::Tensor features_row_step_;                            // [P] int32 or undefined (= every row is up to date)
 	std::vector<std::pair<double, double>> features_lr_hist_;    // (lr, lr_tail) of the Adam steps since the state exists, newest first
 	int features_lazy_window_ = 0;
@@ -279,12 +288,11 @@ public:
 	~TrainStep();                                  // releases the HIP events of the data-parallel step (keyframe_batch_exchange.cpp)
 	TrainStep(const TrainStep&) = delete;          // (it owns them)
 	TrainStep& operator=(const TrainStep&) = delete;
+	// ---- 1. calls (then: 2. options, 3. results of the last step, 4. data-parallel state, 5. internal state of a step)
 	// forward + backward only (gradients left on the leaves, statistics gathered): lets a data-parallel
 	// driver all-reduce before finishOneIteration()
 	torch::Tensor renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask)
-	{
-		return renderAndBackward(kf, gt_image, mask, torch::Tensor());
-	}
+	{ return renderAndBackward(kf, gt_image, mask, torch::Tensor()); }
 	// ... with the keyframe's [H,W] sensor depth (an RGB-D session's img_auxiliary_undist_): with depth_loss_weight_ != 0 the depth
 	// L1 loss (loss_utils::depth_l1 over depth_min_ < gt < depth_max_) joins the RGB loss before the one backward pass; undefined
 	// gt_depth or weight 0 = the RGB loss alone
@@ -300,33 +308,63 @@ public:
 	// backward); SUM / MAX commute with that accumulation, so the driver reduces xyz_gradient_accum_ and denom_ (SUM) and
 	// max_radii2D_ (MAX) over the ranks only before a finishBegin() that will densify -- densifyDue() says when.
 	bool densifyDue() const;
+	bool opacityResetDue() const   // this iteration's finishBegin() resets the opacity (never with mcmc_)
+	{
+		const auto& o = gaussians_->opt_;
+		return densify_ && !mcmc_ && iteration_ < o.densify_until_iter_ && o.opacity_reset_interval_ && iteration_ % o.opacity_reset_interval_ == 0;
+	}
+	// renderAndBackward + finishOneIteration; with a process group set, the data-parallel step (trainForOneIterationDataParallel).
+	// gt_depth: an RGB-D keyframe, the depth loss of renderAndBackward (not with a process group: throws when the weight is non-zero)
 	torch::Tensor trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask)
-	{
-		if (process_group_) {
-			if (kf->exposure_.defined() || optimize_exposure_)
-				throw std::runtime_error("TrainStep: exposure compensation is not supported with a process group");
-			return trainForOneIterationDataParallel(kf, gt_image, mask);
-		}
-		auto loss = renderAndBackward(kf, gt_image, mask);
-		finishOneIteration();
-		return loss;
-	}
-	// an RGB-D keyframe: the depth loss of renderAndBackward(kf, gt_image, mask, gt_depth) (not with a process group: throws
-	// when the weight is non-zero)
+	{ return trainForOneIteration(kf, gt_image, mask, torch::Tensor()); }
 	torch::Tensor trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
-	                                   torch::Tensor gt_depth)
-	{
-		if (process_group_) {
-			if (usesDepthLoss(gt_depth))
-				throw std::runtime_error("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)");
-			if (kf->exposure_.defined() || optimize_exposure_)
-				throw std::runtime_error("TrainStep: exposure compensation is not supported with a process group");
-			return trainForOneIterationDataParallel(kf, gt_image, mask);
-		}
-		auto loss = renderAndBackward(kf, gt_image, mask, gt_depth);
-		finishOneIteration();
-		return loss;
-	}
+	                                   torch::Tensor gt_depth);
+	// A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe): forward-only
+	// (GSR_FORWARD_ONLY) into a second workspace of its own -- a view between a training forward and its backward must not
+	// overwrite the buffers that forward saved -- with lazily stepped SH rows read as they are: no flush, no counter advanced,
+	// nothing of the model touched.  Returns the [3,H,W] image.
+	// apply_exposure: the image behind the keyframe's exposure_ (what the loss compares with the target), if it has one
+	torch::Tensor renderView(std::shared_ptr<GaussianKeyframe> kf, bool apply_exposure = false);
+	// ... with the depth and alpha maps: (image, depth, alpha), [H,W] each (GaussianRenderer::renderWithDepth)
+	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf);
+	GaussianRasterizationExtensions viewExtensions();   // what the two calls above hand to GaussianRenderer
+	// what every render starts from: raw leaves, cull_empty_tiles_, antialiasing_, the workspace; not the filter (viewFilter3D counts)
+	GaussianRasterizationExtensions baseExtensions(RasterWorkspace* workspace) const;
+	// Photometric refinement of one keyframe's pose against the FROZEN map: `iterations` Adam steps (betas 0.9 / 0.999, eps 1e-8,
+	// learning rates lr_translation for rho and lr_rotation for theta) on the xi of a PoseDelta (gaussian_renderer.h) started at
+	// viewpoint_cam, minimising the train step's loss -- fused L1 + lambda_dssim_ (1 - SSIM), plus the depth L1 loss with gt_depth
+	// when depth_loss_weight_ != 0.  The camera gradients come from the rasterizer's backward (gsr_backward_args.dL_dviewmatrix ...)
+	// and reach xi through the pose's construction by autograd.  The map's tensors enter detached, no optimizer or lazy-row state is
+	// touched (lazily stepped SH rows: a caught-up copy is rendered), and the render uses the second workspace as renderView does.
+	// Returns (the refined W2C [4,4], the loss of every iteration [iterations]).
+	std::tuple<torch::Tensor, torch::Tensor> refinePose(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image,
+	                                                    torch::Tensor mask, int iterations, double lr_translation, double lr_rotation,
+	                                                    torch::Tensor gt_depth = torch::Tensor());
+	// What every Gaussian puts into the given keyframes' images (include/gsr.h: GSR_CONTRIBUTION): one forward-only render per keyframe
+	// through the second workspace, exactly as renderView -- lazily stepped SH rows read as they are, nothing of the model or the
+	// training workspace touched, cull_empty_tiles_ and antialiasing_ honoured -- with the three statistics accumulating over the
+	// keyframes inside the rasterizer.  pixel_weights: empty, or one [H,W] float32 map (finite, >= 0; undefined = ones) per keyframe.
+	// Returns (weight_sum, weight_max, n_touched, views_seen): the sum and the maximum over all pixels of all keyframes of
+	// w alpha T, the number of blending pixels with w != 0, and the number of keyframes with radii > 0.
+	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> scoreContribution(
+	    const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, const std::vector<torch::Tensor>& pixel_weights = {});
+	// Scores the keyframes and removes, through prunePoints, the Gaussians that at least min_views of them have in their frustum
+	// (radii > 0) and whose largest blending weight alpha T at any pixel of any of them stays below min_weight_max.  A Gaussian no
+	// given keyframe sees is kept: not observed is not useless.  Returns the number removed.  Not with a process group: throws.
+	int64_t pruneUncontributing(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, float min_weight_max, int min_views = 1);
+	// Seeding from an RGB-D frame: the mapper's "where does the map fail to explain this frame, and what do I put there" step.
+	// seedFromDepth makes one forward-only render of the map with its depth and alpha maps (renderViewWithDepth; none while the
+	// model is empty -- the first frame of a session initialises the map this way) and calls GaussianModel::seedFromDepth with the
+	// seed_* options (SplaTAM's values), the valid range depth_min_ < gt < depth_max_ of the depth loss and the rasterizer's
+	// own pixel-centre convention fx = W / (2 tanfovx), cx = (W - 1) / 2 (likewise y), so that a seed projects onto the centre of
+	// its pixel.  At most mcmc_cap_max_ - P rows with mcmc_ on, seed_max_new_ otherwise.  Returns the number of rows appended.
+	// Not with a process group: throws.  Nothing calls it by itself.
+	int64_t seedFromDepth(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image, torch::Tensor gt_depth, int iteration,
+	                      bool want_pixels = false);
+	// THE refusal of the single-process-only features: throws "TrainStep: <what> not supported with a process group<suffix>" (what =
+	// the feature and its verb, "mcmc_ is") with a process group set or -- factored_counts -- with the view-factored exchange on
+	void requireSingleProcess(const char* what, bool factored_counts, const char* suffix = "") const;
+	// ---- 2. options
 	// The depth loss of RGB-D keyframes: depth_loss_weight_ * the L1 distance of the rendered depth map (sum z alpha T) to the
 	// sensor's over the pixels with depth_min_ < gt < depth_max_ (RGBD.min_depth / RGBD.max_depth), divided by H W.  0 = off.
 	float depth_loss_weight_ = 0.0f;
@@ -339,6 +377,10 @@ public:
 	// the model's betas and eps; densifying iterations included), at a learning rate that falls log-linearly from exposure_lr_init_
 	// to exposure_lr_final_ over exposure_lr_max_steps_ (< 0: opt_.iterations_) of the keyframe's OWN steps.  refinePose applies
 	// a keyframe's exposure and never optimises it.  Not with a process group: throws.
+	bool optimize_exposure_ = false;
+	float exposure_lr_init_ = 0.01f, exposure_lr_final_ = 0.001f;
+	int exposure_lr_max_steps_ = -1;
+	double exposureLearningRate(int step) const;   // of a keyframe's `step`-th exposure step (1-based)
 	// Regularisers on the Gaussians a view sees, added to the opacity and scale gradients inside the rasterizer's backward
 	// (gsr_backward_args.geom_reg; with fused_geom_adam_ in front of the fused step, so nothing reaches HBM for them):
 	//   opacity_reg_ * mean_V sigmoid(opacity) + scale_reg_ * mean_V,k exp(scaling)  (the L1 terms of 3DGS-MCMC, which push Gaussians
@@ -349,8 +391,7 @@ public:
 	// ignores the three.
 	double opacity_reg_ = 0.0, scale_reg_ = 0.0, isotropic_reg_ = 0.0;
 	bool read_reg_losses_ = true;
-	torch::Tensor lastRegLosses() const { return last_reg_losses_; }
-	torch::Tensor last_reg_losses_;
+	bool usesGeomReg() const { return opacity_reg_ != 0.0 || scale_reg_ != 0.0 || isotropic_reg_ != 0.0; }
 	// Densification by absolute screen-space gradients (AbsGS; gsplat's absgrad): the backward pass sums |d/dmean2D| per pixel
 	// before the reduction over a Gaussian's pixels (gsr_backward_args.dL_dmean2D_abs), the fused statistics accumulate the norm of
 	// those sums, and densifyAndPrune compares their mean with densify_abs_grad_threshold_ instead of densify_grad_threshold_.
@@ -360,8 +401,6 @@ public:
 	// with a process group: throws.
 	bool absgrad_ = false;
 	float densify_abs_grad_threshold_ = 0.0008f;
-	torch::Tensor lastAbsgrad() const { return last_absgrad_; }
-	torch::Tensor last_absgrad_;
 	// Fixed-budget maps (3DGS-MCMC): with mcmc_ on and densify_ set, the iterations that rebuild today run relocateDead + addNew
 	// instead of densifyAndPrune -- the count grows by 5 % per event to exactly mcmc_cap_max_ and then stays, no tensor is rebuilt
 	// on a relocation, that iteration's update is skipped as a rebuild's is, and the opacity is never reset -- and every step adds
@@ -371,59 +410,23 @@ public:
 	int64_t mcmc_cap_max_ = 0;
 	double mcmc_noise_lr_ = 5e5;   // (upstream's noise_lr)
 	float mcmc_min_opacity_ = 0.005f;
-	torch::Tensor last_mcmc_counts_;   // the device counts of the last relocateDead
-	// Seeding from an RGB-D frame: the mapper's "where does the map fail to explain this frame, and what do I put there" step.
-	// seedFromDepth makes one forward-only render of the map with its depth and alpha maps (renderViewWithDepth; none while the
-	// model is empty -- the first frame of a session initialises the map this way) and calls GaussianModel::seedFromDepth with the
-	// seed_* options below (SplaTAM's values), the valid range depth_min_ < gt < depth_max_ of the depth loss and the rasterizer's
-	// own pixel-centre convention fx = W / (2 tanfovx), cx = (W - 1) / 2 (likewise y), so that a seed projects onto the centre of
-	// its pixel.  At most mcmc_cap_max_ - P rows with mcmc_ on, seed_max_new_ otherwise.  Returns the number of rows appended.
-	// Not with a process group: throws.  Nothing calls it by itself.
-	int64_t seedFromDepth(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image, torch::Tensor gt_depth, int iteration,
-	                      bool want_pixels = false);
+	// the options of seedFromDepth
 	float seed_alpha_threshold_ = 0.5f, seed_depth_median_factor_ = 50.0f, seed_depth_error_abs_ = 0.0f;
 	int seed_stride_ = 1;
 	float seed_scale_factor_ = 1.0f, seed_init_opacity_ = 0.5f;
 	int64_t seed_max_new_ = int64_t(1) << 30;
-	bool optimize_exposure_ = false;
-	float exposure_lr_init_ = 0.01f, exposure_lr_final_ = 0.001f;
-	int exposure_lr_max_steps_ = -1;
-	double exposureLearningRate(int step) const;   // of a keyframe's `step`-th exposure step (1-based)
-	std::shared_ptr<GaussianKeyframe> exposure_kf_;   // the keyframe of the last backward pass and the gradient of its exposure,
-	torch::Tensor exposure_grad_;                     // until finishEnd() has taken the step
-	void finishExposure();
-	// Keyframe batches, one keyframe per rank (SURVEY.md 8(e)): with a process group set, trainForOneIteration() is the
-	// data-parallel step -- render + backward of THIS rank's keyframe, the gradient exchange over c10d (RCCL on the GPU boxes:
-	// ViewFactoredExchange by default, the plain GradientReduction otherwise; host/include/keyframe_batch_exchange.h), the
-	// optimizer on the batch-mean gradient, and before a densification the SUM / MAX of the per-rank statistics.  Every rank
-	// holds a replica; replicas stay bit-identical (identical Adam on identical gradients, identically seeded split samples).
-	// No collective is issued from anywhere but here.  A C++ mapper creates c10d::TCPStore + ProcessGroupNCCL and hands the
-	// group over; under Python the default group is resolved by name (ops_register.cpp: trainer_set_process_group).
-	void setProcessGroup(c10::intrusive_ptr<c10d::ProcessGroup> pg, bool factored = true);
-	torch::Tensor trainForOneIterationDataParallel(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask);
-	c10::intrusive_ptr<c10d::ProcessGroup> process_group_;
-	// The all-gather of the view-factored exchange is issued on a stream of its own that waits only for the point inside
-	// backward at which the colour gradients are complete (gsr_backward_args.color_view_ready_stream): it overlaps the SH
-	// backward kernel instead of following it.  A hipStream_t from LibTorch's pool, created on first use; null on the host.
-	void* gather_stream_ = nullptr;
-	bool gather_stream_in_use_ = false;   // this step hands gather_stream_ to the exchange (early_gather_)
-	// Data-parallel keyframe batches with the view-factored exchange (include/gsr.h, gsr_sh_grad_from_views): backward
-	// then leaves the clamp-masked colour gradient of this view in sh_grad_view_ and no gradient on features_; after the
-	// driver has gathered the views of all ranks, setFeaturesGradFromViews() installs the batch-mean SH gradient.  It reads
-	// xyz_, so it must run before finishAdamGroup(0).
 	// Densification schedule of GaussianMapper::trainForOneIteration (src/gaussian_mapper.cpp:711-735), off by default:
 	// every densification_interval_ iterations after densify_from_iter_, and the opacity reset.  Runs inside
 	// finishBegin(); an iteration that rebuilt the tensors skips its optimizer step exactly as the reference does (the
 	// fresh leaves have no gradient).
 	bool densify_ = false;
+	float cameras_extent_ = 1.0f, densify_min_opacity_ = 0.005f;
+	int prune_big_point_after_iter_ = 30000;   // Optimization.prune_big_point_after_iter of the shipped Replica / EuRoC configs (no in-code default in the reference)
+	c10::optional<at::Generator> generator_;
 	// The step of the position learning-rate schedule for the NEXT iteration(s): -1 = the iteration count (the COLMAP flavour,
 	// src/gaussian_mapper.cpp:672-674); a SLAM session sets the keyframe's use count before every iteration (:663-671:
 	// kfs_used_times_[fid], capped at position_lr_max_steps_)
 	int position_lr_step_ = -1;
-	float cameras_extent_ = 1.0f, densify_min_opacity_ = 0.005f;
-	int prune_big_point_after_iter_ = 30000;   // Optimization.prune_big_point_after_iter of the shipped Replica / EuRoC configs (no in-code default in the reference)
-	c10::optional<at::Generator> generator_;
-	GaussianModel::DensifyResult last_densify_;
 	// The Adam step of the SH tensor inside the rasterizer's backward (gsr_backward_args.sh_adam: its gradient rows never
 	// reach HBM, 0.13 ms of a 2.3 ms step at C3); same arithmetic as the separate pass.  Not used on an iteration that
 	// densifies (the reference skips that optimizer step) nor with the factored exchange.
@@ -436,10 +439,16 @@ public:
 	// (gsr_backward_args.geom_adam): the 88 B per Gaussian gradient round trip and four optimizer launches disappear; on the
 	// same iterations as fused_sh_adam_.  The viewspace gradient and dL_dcov3D are then not written either.
 	bool fused_geom_adam_ = true;
-	bool factored_exchange_ = false;
 	// Scheduling / list-building switches, each at its measured-best value; none changes a result.  They
 	// are options of THIS object -- a SLAM process that links the library decides per TrainStep -- and the environment variables
 	// of the bench sessions (GSR_CULL_EMPTY_TILES, GSR_EARLY_GATHER, GSR_LAZY_SLICE_EARLY, GSR_SH_ADAM_SIDE_STREAM) only override.
+	bool cull_empty_tiles_ = false;   // instances of tiles no pixel of which can blend the Gaussian leave the list (a wash on MI355X)
+	bool early_gather_ = true;        // the exchange's all-gather waits for the colour gradients only, not for the whole backward pass
+	bool lazy_slice_late_ = false;    // the lazy SH rows' slice behind the backward blend instead of next to it
+	bool no_side_stream_ = false;     // no second stream inside gsr_forward / gsr_backward
+	// the rasterizer's three scratch buffers are kept across iterations and grown with headroom (workspace_, view_workspace_);
+	// false: fresh buffers per call, as the reference's resizeFunctional
+	bool persistent_workspace_ = true;
 	// Anti-aliased rendering (GSR_ANTIALIAS, include/gsr.h): every render of this object -- the train step at whatever H x W the
 	// keyframe's pyramid level has, renderView, refinePose -- compensates the opacity for the 0.3 px low-pass of the projected
 	// covariance.  Unlike the switches above it CHANGES the result; densification and pruning keep their thresholds on the
@@ -466,64 +475,66 @@ public:
 	// when it is undefined (or `recompute`)
 	torch::Tensor viewFilter3D(bool recompute = false);
 	void checkFilter3D() const;   // the two refusals of viewFilter3D alone (a process group; no cameras): throws or does nothing
+	// pipeline flags of the render call (include/gaussian_parameters.h; every shipped config leaves both off).  The fused
+	// optimizer paths above are taken only when render() keeps the tensors they step inside the rasterizer.
+	GaussianPipelineParams pipe_;
+	// ---- 3. results of the last step
+	torch::Tensor lastRegLosses() const { return last_reg_losses_; }
+	torch::Tensor last_reg_losses_;
+	torch::Tensor lastAbsgrad() const { return last_absgrad_; }
+	torch::Tensor last_absgrad_;
+	torch::Tensor last_mcmc_counts_;   // the device counts of the last relocateDead
+	GaussianModel::DensifyResult last_densify_;
+	torch::Tensor last_viewspace_, last_visibility_ /* undefined when the step fused its consumers: last_radii_ > 0 */, last_radii_;
 	// renders of this object that were handed the filter (every call of viewFilter3D that returned one; RasterizeGaussiansCUDA
 	// refuses a filter whose row count is not the model's): lets a test see that no render went without
 	int64_t filter3d_renders_ = 0;
-	bool cull_empty_tiles_ = false;   // instances of tiles no pixel of which can blend the Gaussian leave the list (a wash on MI355X)
-	// the rasterizer's three scratch buffers, kept across iterations and grown with headroom (rasterize_points.h: RasterWorkspace);
-	// persistent_workspace_ = false: fresh buffers per call, as the reference's resizeFunctional
-	bool persistent_workspace_ = true;
-	RasterWorkspace workspace_;
-	// A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe): forward-only
-	// (GSR_FORWARD_ONLY) into a second workspace of its own -- a view between a training forward and its backward must not
-	// overwrite the buffers that forward saved -- with lazily stepped SH rows read as they are: no flush, no counter advanced,
-	// nothing of the model touched.  Returns the [3,H,W] image.
-	// apply_exposure: the image behind the keyframe's exposure_ (what the loss compares with the target), if it has one
-	torch::Tensor renderView(std::shared_ptr<GaussianKeyframe> kf, bool apply_exposure = false);
-	// ... with the depth and alpha maps: (image, depth, alpha), [H,W] each (GaussianRenderer::renderWithDepth)
-	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf);
-	RasterWorkspace view_workspace_;
-	// Photometric refinement of one keyframe's pose against the FROZEN map: `iterations` Adam steps (betas 0.9 / 0.999, eps 1e-8,
-	// learning rates lr_translation for rho and lr_rotation for theta) on the xi of a PoseDelta (gaussian_renderer.h) started at
-	// viewpoint_cam, minimising the train step's loss -- fused L1 + lambda_dssim_ (1 - SSIM), plus the depth L1 loss with gt_depth
-	// when depth_loss_weight_ != 0.  The camera gradients come from the rasterizer's backward (gsr_backward_args.dL_dviewmatrix ...)
-	// and reach xi through the pose's construction by autograd.  The map's tensors enter detached, no optimizer or lazy-row state is
-	// touched (lazily stepped SH rows: a caught-up copy is rendered), and the render uses the second workspace as renderView does.
-	// Returns (the refined W2C [4,4], the loss of every iteration [iterations]).
-	std::tuple<torch::Tensor, torch::Tensor> refinePose(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image,
-	                                                    torch::Tensor mask, int iterations, double lr_translation, double lr_rotation,
-	                                                    torch::Tensor gt_depth = torch::Tensor());
-	GaussianRasterizationExtensions viewExtensions();   // what the two calls above hand to GaussianRenderer
-	// What every Gaussian puts into the given keyframes' images (include/gsr.h: GSR_CONTRIBUTION): one forward-only render per keyframe
-	// through the second workspace, exactly as renderView -- lazily stepped SH rows read as they are, nothing of the model or the
-	// training workspace touched, cull_empty_tiles_ and antialiasing_ honoured -- with the three statistics accumulating over the
-	// keyframes inside the rasterizer.  pixel_weights: empty, or one [H,W] float32 map (finite, >= 0; undefined = ones) per keyframe.
-	// Returns (weight_sum, weight_max, n_touched, views_seen): the sum and the maximum over all pixels of all keyframes of
-	// w alpha T, the number of blending pixels with w != 0, and the number of keyframes with radii > 0.
-	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> scoreContribution(
-	    const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, const std::vector<torch::Tensor>& pixel_weights = {});
-	// Scores the keyframes and removes, through prunePoints, the Gaussians that at least min_views of them have in their frustum
-	// (radii > 0) and whose largest blending weight alpha T at any pixel of any of them stays below min_weight_max.  A Gaussian no
-	// given keyframe sees is kept: not observed is not useless.  Returns the number removed.  Not with a process group: throws.
-	int64_t pruneUncontributing(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, float min_weight_max, int min_views = 1);
-	bool early_gather_ = true;        // the exchange's all-gather waits for the colour gradients only, not for the whole backward pass
-	// The view-factored exchange in its PACKED form (include/gsr.h: gsr_pack_color_view): every rank sends only the rows its
-	// view sees -- 11.7 MB instead of 24 MB per rank and link at 2 M Gaussians.  The ranks agree on the message capacity by
-	// exchanging their views' visible counts (one int each, host values) over a host-side group (setCountGroup: gloo) right behind
-	// the forward pass; the host picks the result up after it has queued the backward pass (keyframe_batch_exchange.cpp:
-	// beginCountExchange).  Off by default until a multi-GPU node has measured it (bench.py picks the faster form in a guarded
-	// trial); bit-identical results (tests/test_packed_views.py, tests/test_train_step.py).
-	bool packed_exchange_ = false;
-	bool lazy_slice_late_ = false;    // the lazy SH rows' slice behind the backward blend instead of next to it
-	bool no_side_stream_ = false;     // no second stream inside gsr_forward / gsr_backward
 	// exposed communication of the data-parallel step: the time the compute stream spent waiting for a collective (HIP events
 	// around every Work::wait(), recorded only while profile_exchange_ is set); read with exchangeWaitMs()
 	bool profile_exchange_ = false;
 	std::vector<double> exchangeWaitMs();
 	void markWait(int k);   // {all-gather wait, all-reduce wait} of the last data-parallel step, in ms
-	// pipeline flags of the render call (include/gaussian_parameters.h; every shipped config leaves both off).  The fused
-	// optimizer paths above are taken only when render() keeps the tensors they step inside the rasterizer.
-	GaussianPipelineParams pipe_;
+	// ---- 4. data-parallel state
+	// Keyframe batches, one keyframe per rank (SURVEY.md 8(e)): with a process group set, trainForOneIteration() is the
+	// data-parallel step -- render + backward of THIS rank's keyframe, the gradient exchange over c10d (RCCL on the GPU boxes:
+	// ViewFactoredExchange by default, the plain GradientReduction otherwise; host/include/keyframe_batch_exchange.h), the
+	// optimizer on the batch-mean gradient, and before a densification the SUM / MAX of the per-rank statistics.  Every rank
+	// holds a replica; replicas stay bit-identical (identical Adam on identical gradients, identically seeded split samples).
+	// No collective is issued from anywhere but here.  A C++ mapper creates c10d::TCPStore + ProcessGroupNCCL and hands the
+	// group over; under Python the default group is resolved by name (ops_register.cpp: trainer_set_process_group).
+	void setProcessGroup(c10::intrusive_ptr<c10d::ProcessGroup> pg, bool factored = true);
+	torch::Tensor trainForOneIterationDataParallel(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask);
+	c10::intrusive_ptr<c10d::ProcessGroup> process_group_;
+	bool factored_exchange_ = false;
+	// Data-parallel keyframe batches with the view-factored exchange (include/gsr.h, gsr_sh_grad_from_views): backward
+	// then leaves the clamp-masked colour gradient of this view in sh_grad_view_ and no gradient on features_; after the
+	// driver has gathered the views of all ranks, setFeaturesGradFromViews() installs the batch-mean SH gradient.  It reads
+	// xyz_, so it must run before finishAdamGroup(0).
+	torch::Tensor sh_grad_view_;
+	void setFeaturesGradFromViews(torch::Tensor campos_views, torch::Tensor dL_dcolor_views);
+	// ... or rebuilds it and takes the Adam step of features_ in the same pass (gsr_sh_adam_from_views): the mean gradient
+	// never reaches HBM.  Replaces setFeaturesGradFromViews() + finishAdamGroup(1); same ordering constraint.
+	// row0 / first_part: the gathered views may arrive in parts (rows [row0, row0 + views.size(1)) of the Gaussians): each
+	// part is applied as soon as ITS all-gather has landed, while the next one is still on the links; the Adam step counter
+	// advances with the first part only.
+	void stepFeaturesFromViews(torch::Tensor campos_views, torch::Tensor dL_dcolor_views, int64_t row0 = 0, bool first_part = true);
+	// With lazy_sh_adam_window_ >= 2 the factored step is as lean as the single-GPU one: a row no gathered view lights takes a
+	// zero-gradient step, i.e. it may take it LATER (gsr_sh_adam_from_views with sh_adam->lazy) -- renderAndBackward() then
+	// advances the SH step counter itself and hands the lazy struct to the forward pass, stepFeaturesFromViews() steps only the
+	// lit rows, and finishFeaturesFromViews() -- after the last part -- runs this step's slice of the rotating catch-up and
+	// records the step's learning rates.  (finishEnd() calls it if the driver did not.)
+	void finishFeaturesFromViews();
+	ShAdamStep views_adam_;
+	bool views_adam_pending_ = false;
+	// xyz / opacity / scaling / rotation in ONE Adam launch (gsr_adam_step_multi): the data-parallel step's four small
+	// gradients arrive together from one all-reduce.  Replaces finishAdamGroup(0 / 2 / 3 / 4).  grad_scale: the gradients are
+	// multiplied by it as they are read (the 1/N of a batch mean whose all-reduce summed).
+	void finishGeomAdam(float grad_scale = 1.0f);
+	// The all-gather of the view-factored exchange is issued on a stream of its own that waits only for the point inside
+	// backward at which the colour gradients are complete (gsr_backward_args.color_view_ready_stream): it overlaps the SH
+	// backward kernel instead of following it.  A hipStream_t from LibTorch's pool, created on first use; null on the host.
+	void* gather_stream_ = nullptr;
+	bool gather_stream_in_use_ = false;   // this step hands gather_stream_ to the exchange (early_gather_)
 	torch::Tensor sh_send_;        // [P + 1, 3]: rows 0 .. P-1 = sh_grad_view_, row P = this view's camera centre (one all-gather)
 	// [N, P + 1, 3]: what the all-gather writes.  PERSISTENT (re-allocated only when P or N changes) and sized in
 	// renderAndBackward() BEFORE the forward and backward passes are enqueued: the early gather writes it from a second stream
@@ -531,6 +542,13 @@ public:
 	// buffer taken from the caching allocator at that point could be a block the pass has just released and still writes
 	// (record_stream protects the free side, not the first use on a foreign stream).
 	torch::Tensor sh_gathered_;
+	// The view-factored exchange in its PACKED form (include/gsr.h: gsr_pack_color_view): every rank sends only the rows its
+	// view sees -- 11.7 MB instead of 24 MB per rank and link at 2 M Gaussians.  The ranks agree on the message capacity by
+	// exchanging their views' visible counts (one int each, host values) over a host-side group (setCountGroup: gloo) right behind
+	// the forward pass; the host picks the result up after it has queued the backward pass (keyframe_batch_exchange.cpp:
+	// beginCountExchange).  Off by default until a multi-GPU node has measured it (bench.py picks the faster form in a guarded
+	// trial); bit-identical results (tests/test_packed_views.py, tests/test_train_step.py).
+	bool packed_exchange_ = false;
 	// packed form: the message buffers (int32; persistent like sh_gathered_), the pack kernels' scratch and the count exchange
 	torch::Tensor sh_packed_send_, sh_packed_gathered_, sh_pack_scratch_;
 	// counts_host_: every rank's visible count, on the host (pinned only on the RCCL route, whose copies need it)
@@ -561,37 +579,33 @@ public:
 	void stepFeaturesFromPackedViews(torch::Tensor messages, int64_t msg_stride, int64_t n_views);
 	// hipEvent_t: before / after the gather wait, before / after the reduce wait, start and end of the data-parallel step
 	void* wait_events_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-	torch::Tensor sh_grad_view_;
-	void setFeaturesGradFromViews(torch::Tensor campos_views, torch::Tensor dL_dcolor_views);
-	// ... or rebuilds it and takes the Adam step of features_ in the same pass (gsr_sh_adam_from_views): the mean gradient
-	// never reaches HBM.  Replaces setFeaturesGradFromViews() + finishAdamGroup(1); same ordering constraint.
-	// row0 / first_part: the gathered views may arrive in parts (rows [row0, row0 + views.size(1)) of the Gaussians): each
-	// part is applied as soon as ITS all-gather has landed, while the next one is still on the links; the Adam step counter
-	// advances with the first part only.
-	void stepFeaturesFromViews(torch::Tensor campos_views, torch::Tensor dL_dcolor_views, int64_t row0 = 0, bool first_part = true);
-	// With lazy_sh_adam_window_ >= 2 the factored step is as lean as the single-GPU one: a row no gathered view lights takes a
-	// zero-gradient step, i.e. it may take it LATER (gsr_sh_adam_from_views with sh_adam->lazy) -- renderAndBackward() then
-	// advances the SH step counter itself and hands the lazy struct to the forward pass, stepFeaturesFromViews() steps only the
-	// lit rows, and finishFeaturesFromViews() -- after the last part -- runs this step's slice of the rotating catch-up and
-	// records the step's learning rates.  (finishEnd() calls it if the driver did not.)
-	void finishFeaturesFromViews();
-	// xyz / opacity / scaling / rotation in ONE Adam launch (gsr_adam_step_multi): the data-parallel step's four small
-	// gradients arrive together from one all-reduce.  Replaces finishAdamGroup(0 / 2 / 3 / 4).  grad_scale: the gradients are
-	// multiplied by it as they are read (the 1/N of a batch mean whose all-reduce summed).
-	void finishGeomAdam(float grad_scale = 1.0f);
-	ShAdamStep views_adam_;
-	bool views_adam_pending_ = false;
+	// ---- 5. internal state of a step
 	std::shared_ptr<GaussianModel> gaussians_;
 	torch::Tensor background_;
 	int iteration_ = 0;
-	torch::Tensor last_viewspace_, last_visibility_ /* undefined when the step fused its consumers: last_radii_ > 0 */, last_radii_;
+	RasterWorkspace workspace_;        // of the train step's render (rasterize_points.h: RasterWorkspace; persistent_workspace_)
+	RasterWorkspace view_workspace_;   // of the forward-only renders and refinePose
+	std::shared_ptr<GaussianKeyframe> exposure_kf_;   // the keyframe of the last backward pass and the gradient of its exposure,
+	torch::Tensor exposure_grad_;                     // until finishEnd() has taken the step
+	void finishExposure();
 	torch::Tensor root_grad_;   // the constant 1 handed to loss.backward()
 	struct MaskEntry {
 		c10::weak_intrusive_ptr<c10::TensorImpl, c10::UndefinedTensorImpl> self{c10::intrusive_ptr<c10::TensorImpl, c10::UndefinedTensorImpl>()};
 		int64_t version = 0;
 		bool ones = false;
 	};
-	std::map<const void*, MaskEntry> mask_is_ones_;   // masks seen so far: all ones? (renderAndBackward)
+	std::map<const void*, MaskEntry> mask_is_ones_;   // masks seen so far: all ones? (effectiveMask)
+	// the stages of renderAndBackward, in the order it runs them (train_step.cpp); effectiveMask and stepLoss serve refinePose too
+	void checkStepSupported(const std::shared_ptr<GaussianKeyframe>& kf, bool use_depth);
+	void prepareExchangeBuffers(const std::shared_ptr<GaussianKeyframe>& kf);
+	torch::Tensor planRegularisers(GaussianRasterizationExtensions& ext) const;
+	bool planFeaturesStep(GaussianRasterizationExtensions& ext, bool rebuilds);   // -> the SH rows step lazily
+	void planExchangeOverlap(GaussianRasterizationExtensions& ext);
+	void planGeomStep(GaussianRasterizationExtensions& ext, bool resets);
+	void planStatistics(GaussianRasterizationExtensions& ext);
+	torch::Tensor effectiveMask(const torch::Tensor& mask);   // the mask, or an empty tensor for a mask of ones
+	torch::Tensor stepLoss(const torch::Tensor& rendered, const torch::Tensor& depth, const torch::Tensor& exposure, const torch::Tensor& gt_image,
+	                       const torch::Tensor& eff_mask, const torch::Tensor& gt_depth, bool use_depth) const;
 };
 
 // loss = (1-lambda) L1 + lambda (1-SSIM) with its gradient in two HIP kernels (gsr_l1_ssim_loss)

@@ -17,53 +17,62 @@
 
 namespace {
 
-std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians(torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh,
-                                                             torch::Tensor colors_precomp, torch::Tensor opacities,
-                                                             torch::Tensor scales, torch::Tensor rotations,
-                                                             torch::Tensor cov3Ds_precomp, torch::Tensor bg,
-                                                             double scale_modifier, torch::Tensor viewmatrix,
-                                                             torch::Tensor projmatrix, double tanfovx, double tanfovy,
-                                                             int64_t image_height, int64_t image_width, int64_t sh_degree,
-                                                             torch::Tensor campos, bool prefiltered)
+// ---- what the four rasterize_gaussians* ops share: the extensions their raw_params argument names (GSR_RAW_* in bits 1|2|4,
+// GSR_CULL_EMPTY_TILES in 8, GSR_ANTIALIAS in 256), their eighteen leading arguments, and the forward call on them (a tensor without
+// elements = not given; ext null = the reference's GaussianRasterizer)
+GaussianRasterizationExtensions decode_raw_params(int64_t raw_params)
 {
-	GaussianRasterizationSettings s((int)image_height, (int)image_width, (float)tanfovx, (float)tanfovy, bg,
-	                                (float)scale_modifier, viewmatrix, projmatrix, (int)sh_degree, campos, prefiltered);
-	GaussianRasterizer r(s);
-	auto has = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
-	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations),
-	                 has(cov3Ds_precomp), sh, colors_precomp, scales, rotations, cov3Ds_precomp);
+	GaussianRasterizationExtensions e;
+	e.raw_params_ = (int)raw_params & 7;
+	e.cull_empty_tiles_ = (raw_params & 8) != 0;
+	e.antialiasing_ = (raw_params & 256) != 0;
+	return e;
+}
+bool has(const torch::Tensor& t) { return t.defined() && t.numel() != 0; }
+struct RasterArgs {
+	torch::Tensor means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg;
+	double scale_modifier;
+	torch::Tensor viewmatrix, projmatrix;
+	double tanfovx, tanfovy;
+	int64_t image_height, image_width, sh_degree;
+	torch::Tensor campos;
+};
+std::tuple<torch::Tensor, torch::Tensor> forward(RasterArgs in, const GaussianRasterizationExtensions* ext, bool prefiltered = false)
+{
+	GaussianRasterizationSettings s((int)in.image_height, (int)in.image_width, (float)in.tanfovx, (float)in.tanfovy, in.bg, (float)in.scale_modifier,
+	                                in.viewmatrix, in.projmatrix, (int)in.sh_degree, in.campos, prefiltered);
+	auto call = [&](auto&& r) {
+		return r.forward(in.means3D, in.means2D, in.opacities, has(in.sh), has(in.colors_precomp), has(in.scales), has(in.rotations),
+		                 has(in.cov3Ds_precomp), in.sh, in.colors_precomp, in.scales, in.rotations, in.cov3Ds_precomp);
+	};
+	return ext ? call(GaussianRasterizerEx(s, *ext)) : call(GaussianRasterizer(s));
+}
+
+std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians(
+    torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh, torch::Tensor colors_precomp, torch::Tensor opacities,
+    torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3Ds_precomp, torch::Tensor bg, double scale_modifier,
+    torch::Tensor viewmatrix, torch::Tensor projmatrix, double tanfovx, double tanfovy, int64_t image_height, int64_t image_width,
+    int64_t sh_degree, torch::Tensor campos, bool prefiltered)
+{
+	return forward({means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg, scale_modifier, viewmatrix, projmatrix,
+	                tanfovx, tanfovy, image_height, image_width, sh_degree, campos}, nullptr, prefiltered);
 }
 
 // GaussianRasterizer(Ex)::forward as a caller of the forward-only path reaches it: ex = GaussianRasterizerEx with raw_params /
 // GSR_CULL_EMPTY_TILES / forward_only_ (extension_forward_only), otherwise the reference's GaussianRasterizer; no_grad = under
 // torch::NoGradGuard.  (image, radii)
-std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_modes(torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh,
-                                                                   torch::Tensor colors_precomp, torch::Tensor opacities,
-                                                                   torch::Tensor scales, torch::Tensor rotations,
-                                                                   torch::Tensor cov3Ds_precomp, torch::Tensor bg, double scale_modifier,
-                                                                   torch::Tensor viewmatrix, torch::Tensor projmatrix, double tanfovx,
-                                                                   double tanfovy, int64_t image_height, int64_t image_width,
-                                                                   int64_t sh_degree, torch::Tensor campos, bool ex, int64_t raw_params,
-                                                                   bool extension_forward_only, bool no_grad)
+std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_modes(
+    torch::Tensor means3D, torch::Tensor means2D, torch::Tensor sh, torch::Tensor colors_precomp, torch::Tensor opacities,
+    torch::Tensor scales, torch::Tensor rotations, torch::Tensor cov3Ds_precomp, torch::Tensor bg, double scale_modifier,
+    torch::Tensor viewmatrix, torch::Tensor projmatrix, double tanfovx, double tanfovy, int64_t image_height, int64_t image_width,
+    int64_t sh_degree, torch::Tensor campos, bool ex, int64_t raw_params, bool extension_forward_only, bool no_grad)
 {
-	GaussianRasterizationSettings s((int)image_height, (int)image_width, (float)tanfovx, (float)tanfovy, bg,
-	                                (float)scale_modifier, viewmatrix, projmatrix, (int)sh_degree, campos, false);
-	auto has = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
 	c10::optional<torch::NoGradGuard> guard;
 	if (no_grad) guard.emplace();
-	if (!ex) {
-		GaussianRasterizer r(s);
-		return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
-		                 colors_precomp, scales, rotations, cov3Ds_precomp);
-	}
-	GaussianRasterizationExtensions e;
-	e.raw_params_ = (int)raw_params & 7;
-	e.cull_empty_tiles_ = (raw_params & 8) != 0;
-	e.antialiasing_ = (raw_params & 256) != 0;   // GSR_ANTIALIAS
+	GaussianRasterizationExtensions e = decode_raw_params(raw_params);
 	e.forward_only_ = extension_forward_only;
-	GaussianRasterizerEx r(s, e);
-	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
-	                 colors_precomp, scales, rotations, cov3Ds_precomp);
+	return forward({means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg, scale_modifier, viewmatrix, projmatrix,
+	                tanfovx, tanfovy, image_height, image_width, sh_degree, campos}, ex ? &e : nullptr);
 }
 
 // rasterize_gaussians_modes (ex) with the contribution statistics (GaussianRasterizationExtensions::out_weight_sum_ ...): stats =
@@ -76,23 +85,16 @@ std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_contribution(
     bool accumulate)
 {
 	TORCH_CHECK(stats.size() == 4, "stats: {pixel_weight, out_weight_sum, out_weight_max, out_n_touched}");
-	GaussianRasterizationSettings s((int)image_height, (int)image_width, (float)tanfovx, (float)tanfovy, bg,
-	                                (float)scale_modifier, viewmatrix, projmatrix, (int)sh_degree, campos, false);
-	auto has = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
 	torch::NoGradGuard guard;
-	GaussianRasterizationExtensions e;
-	e.raw_params_ = (int)raw_params & 7;
-	e.cull_empty_tiles_ = (raw_params & 8) != 0;
-	e.antialiasing_ = (raw_params & 256) != 0;
+	GaussianRasterizationExtensions e = decode_raw_params(raw_params);
 	e.forward_only_ = extension_forward_only;
 	if (has(stats[0])) e.pixel_weight_ = stats[0];
 	if (has(stats[1])) e.out_weight_sum_ = stats[1];
 	if (has(stats[2])) e.out_weight_max_ = stats[2];
 	if (has(stats[3])) e.out_n_touched_ = stats[3];
 	e.contribution_accumulate_ = accumulate;
-	GaussianRasterizerEx r(s, e);
-	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
-	                 colors_precomp, scales, rotations, cov3Ds_precomp);
+	return forward({means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg, scale_modifier, viewmatrix, projmatrix,
+	                tanfovx, tanfovy, image_height, image_width, sh_degree, campos}, &e);
 }
 // rasterize_gaussians_modes (ex) with the absolute screen-space gradients: backward() of the returned image fills `absgrad`
 // ([P,2], GaussianRasterizationExtensions::absgrad_).  (image, radii)
@@ -102,17 +104,10 @@ std::tuple<torch::Tensor, torch::Tensor> rasterize_gaussians_absgrad(
     torch::Tensor viewmatrix, torch::Tensor projmatrix, double tanfovx, double tanfovy, int64_t image_height, int64_t image_width,
     int64_t sh_degree, torch::Tensor campos, int64_t raw_params, torch::Tensor absgrad)
 {
-	GaussianRasterizationSettings s((int)image_height, (int)image_width, (float)tanfovx, (float)tanfovy, bg,
-	                                (float)scale_modifier, viewmatrix, projmatrix, (int)sh_degree, campos, false);
-	auto has = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
-	GaussianRasterizationExtensions e;
-	e.raw_params_ = (int)raw_params & 7;
-	e.cull_empty_tiles_ = (raw_params & 8) != 0;
-	e.antialiasing_ = (raw_params & 256) != 0;
+	GaussianRasterizationExtensions e = decode_raw_params(raw_params);
 	e.absgrad_ = absgrad;
-	GaussianRasterizerEx r(s, e);
-	return r.forward(means3D, means2D, opacities, has(sh), has(colors_precomp), has(scales), has(rotations), has(cov3Ds_precomp), sh,
-	                 colors_precomp, scales, rotations, cov3Ds_precomp);
+	return forward({means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, bg, scale_modifier, viewmatrix, projmatrix,
+	                tanfovx, tanfovy, image_height, image_width, sh_degree, campos}, &e);
 }
 double covisibility_op(torch::Tensor a, torch::Tensor b) { return covisibility(a, b); }
 
@@ -163,15 +158,27 @@ std::mutex g_mu;
 std::map<int64_t, std::shared_ptr<TrainStep>> g_trainers;
 int64_t g_next = 1;
 
+// a TrainStep around the model behind a new handle
+int64_t adopt(std::shared_ptr<GaussianModel> model, torch::Tensor background)
+{
+	std::lock_guard<std::mutex> lk(g_mu);
+	g_trainers[g_next] = std::make_shared<TrainStep>(model, background);
+	return g_next++;
+}
+// an op returns no undefined tensor: an empty one of the given dtype on `like`'s device stands for it
+torch::Tensor or_empty(const torch::Tensor& t, const torch::Tensor& like, c10::optional<torch::ScalarType> dtype = c10::nullopt,
+                       at::IntArrayRef shape = {0})
+{
+	return t.defined() ? t : torch::empty(shape, like.options().dtype(dtype.value_or(like.scalar_type())).requires_grad(false));
+}
+
 int64_t trainer_create(torch::Tensor xyz, torch::Tensor features, torch::Tensor opacity, torch::Tensor scaling,
                        torch::Tensor rotation, int64_t sh_degree, double spatial_lr_scale, torch::Tensor background)
 {
 	auto model = std::make_shared<GaussianModel>((int)sh_degree, xyz, features, opacity, scaling, rotation,
 	                                             (float)spatial_lr_scale);
 	model->trainingSetup(GaussianOptimizationParams());
-	std::lock_guard<std::mutex> lk(g_mu);
-	g_trainers[g_next] = std::make_shared<TrainStep>(model, background);
-	return g_next++;
+	return adopt(model, background);
 }
 int64_t trainer_create_from_pcd(torch::Tensor points, torch::Tensor colors, int64_t sh_degree, double spatial_lr_scale,
                                 torch::Tensor background)
@@ -179,9 +186,7 @@ int64_t trainer_create_from_pcd(torch::Tensor points, torch::Tensor colors, int6
 	auto model = std::make_shared<GaussianModel>((int)sh_degree);
 	model->createFromPcd(points, colors, (float)spatial_lr_scale);
 	model->trainingSetup(GaussianOptimizationParams());
-	std::lock_guard<std::mutex> lk(g_mu);
-	g_trainers[g_next] = std::make_shared<TrainStep>(model, background);
-	return g_next++;
+	return adopt(model, background);
 }
 // a generator of the tensors' device seeded like torch.Generator(device).manual_seed(seed)
 at::Generator make_generator(const torch::Device& device, int64_t seed)
@@ -227,13 +232,23 @@ torch::Tensor trainer_render_and_backward_depth(int64_t h, torch::Tensor view, t
 torch::Tensor trainer_last_absgrad(int64_t h)
 {
 	auto t = get(h);
-	return t->lastAbsgrad().defined() ? t->lastAbsgrad() : torch::empty({0, 2}, t->gaussians_->xyz_.options().requires_grad(false));
+	return or_empty(t->lastAbsgrad(), t->gaussians_->xyz_, c10::nullopt, {0, 2});
 }
 // TrainStep::lastRegLosses: the three regulariser terms of the last step ([3]), or an empty tensor when they were not formed
 torch::Tensor trainer_last_reg_losses(int64_t h)
 {
 	auto t = get(h);
-	return t->lastRegLosses().defined() ? t->lastRegLosses() : torch::empty({0}, t->gaussians_->xyz_.options().requires_grad(false));
+	return or_empty(t->lastRegLosses(), t->gaussians_->xyz_);
+}
+// the extensions of the two ops that call GaussianRenderer::render themselves: the trainer's antialiasing_ and filter, neither its
+// cull_empty_tiles_ nor a workspace
+GaussianRasterizationExtensions render_extensions(TrainStep& t, int raw_params)
+{
+	GaussianRasterizationExtensions ext;
+	ext.raw_params_ = raw_params;
+	ext.antialiasing_ = t.antialiasing_;
+	ext.filter_3D_ = t.viewFilter3D();
+	return ext;
 }
 // GaussianRenderer::render on the trainer's model with the pipeline flags of GaussianPipelineParams (convert_SHs_,
 // compute_cov3D_: src/gaussian_renderer.cpp:78-113): (image, radii); the image is attached to the model's leaves
@@ -246,12 +261,8 @@ std::tuple<torch::Tensor, torch::Tensor> trainer_render(int64_t h, torch::Tensor
 	pipe.convert_SHs_ = convert_SHs;
 	pipe.compute_cov3D_ = compute_cov3D;
 	torch::Tensor override_color;
-	GaussianRasterizationExtensions ext;
-	ext.raw_params_ = fuse_activations ? 7 : 0;
-	ext.antialiasing_ = t->antialiasing_;
-	ext.filter_3D_ = t->viewFilter3D();
 	auto pkg = GaussianRenderer::render(make_kf(view, proj, campos, fovx, fovy, H, W), (int)H, (int)W, t->gaussians_, pipe,
-	                                    t->background_, override_color, 1.0f, false, ext);
+	                                    t->background_, override_color, 1.0f, false, render_extensions(*t, fuse_activations ? 7 : 0));
 	return std::make_tuple(std::get<0>(pkg), std::get<3>(pkg));
 }
 // TrainStep::renderView: a forward-only render of the current model into the trainer's second workspace (the image, detached)
@@ -279,8 +290,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, int64_t> 
 {
 	auto kf = with_exposure(make_kf(view, proj, campos, fovx, fovy, H, W), state, step);
 	auto loss = get(h)->trainForOneIteration(kf, gt, mask).detach();
-	auto or_empty = [&](const torch::Tensor& t) { return t.defined() ? t : torch::empty({0}, gt.options()); };
-	return std::make_tuple(loss, or_empty(kf->exposure_), or_empty(kf->exposure_exp_avg_), or_empty(kf->exposure_exp_avg_sq_),
+	return std::make_tuple(loss, or_empty(kf->exposure_, gt), or_empty(kf->exposure_exp_avg_, gt), or_empty(kf->exposure_exp_avg_sq_, gt),
 	                       (int64_t)kf->exposure_step_);
 }
 torch::Tensor trainer_render_view_exposure(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx,
@@ -364,17 +374,17 @@ torch::Tensor trainer_pose_gradient(int64_t h, torch::Tensor view, torch::Tensor
 	PoseDelta pose(kf->world_view_transform_, kf->full_proj_transform_);
 	pose.apply(*kf);
 	torch::Tensor override_color;
-	GaussianRasterizationExtensions ext;
-	ext.raw_params_ = 7;
-	ext.antialiasing_ = t->antialiasing_;
-	ext.filter_3D_ = t->viewFilter3D();
-	// (the map frozen for this render: only the camera requires grad)
+	const GaussianRasterizationExtensions ext = render_extensions(*t, 7);
+	// (the map frozen for this render: only the camera requires grad; the leaves get their flags back on every way out of it)
 	auto frozen = t->gaussians_;
-	std::vector<bool> was;
-	for (auto& p : frozen->paramsRaw()) { was.push_back(p.requires_grad()); p.set_requires_grad(false); }
-	auto pkg = GaussianRenderer::render(kf, (int)H, (int)W, frozen, t->pipe_, t->background_, override_color, 1.0f, false, ext);
 	auto leaves = frozen->paramsRaw();
-	for (size_t i = 0; i < leaves.size(); i++) leaves[i].set_requires_grad(was[i]);
+	std::vector<bool> was;
+	for (auto& p : leaves) { was.push_back(p.requires_grad()); p.set_requires_grad(false); }
+	std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> pkg;
+	{
+		ScopeExit restore{[&] { for (size_t i = 0; i < leaves.size(); i++) leaves[i].set_requires_grad(was[i]); }};
+		pkg = GaussianRenderer::render(kf, (int)H, (int)W, frozen, t->pipe_, t->background_, override_color, 1.0f, false, ext);
+	}
 	TORCH_CHECK(std::get<0>(pkg).requires_grad(), "a render in which only the camera requires grad must take the training path");
 	return torch::autograd::grad({(std::get<0>(pkg) * dL_dpix).sum()}, {pose.xi_})[0];
 }
@@ -387,7 +397,7 @@ std::vector<torch::Tensor> trainer_grads(int64_t h)
 {
 	std::vector<torch::Tensor> g;
 	// (features_ has no gradient yet in the factored mode: an empty tensor keeps the positions)
-	for (auto& p : get(h)->gaussians_->paramsRaw()) g.push_back(p.grad().defined() ? p.grad() : torch::empty({0}, p.options()));
+	for (auto& p : get(h)->gaussians_->paramsRaw()) g.push_back(or_empty(p.grad(), p));
 	return g;
 }
 // densification: options of the schedule (names of GaussianOptimizationParams / GaussianMapper without the trailing
@@ -487,7 +497,7 @@ void trainer_add_position_noise(int64_t h, double noise_scale, int64_t seed)
 torch::Tensor trainer_last_mcmc_counts(int64_t h)
 {
 	auto t = get(h);
-	return t->last_mcmc_counts_.defined() ? t->last_mcmc_counts_ : torch::empty({0}, t->gaussians_->xyz_.options().dtype(torch::kInt32).requires_grad(false));
+	return or_empty(t->last_mcmc_counts_, t->gaussians_->xyz_, torch::kInt32);
 }
 // TrainStep::seedFromDepth (the pixels of the new rows are kept: trainer_last_seed_pixels); GaussianModel::last_seed_counts_ / _pixels_
 int64_t trainer_seed_from_depth(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx, double fovy,
@@ -506,15 +516,13 @@ int64_t trainer_create_empty(int64_t sh_degree, torch::Tensor background)
 {
 	auto model = std::make_shared<GaussianModel>((int)sh_degree);
 	model->device_ = background.device();
-	std::lock_guard<std::mutex> lk(g_mu);
-	g_trainers[g_next] = std::make_shared<TrainStep>(model, background);
-	return g_next++;
+	return adopt(model, background);
 }
 std::vector<int64_t> trainer_last_seed_counts(int64_t h) { return get(h)->gaussians_->last_seed_counts_; }
 torch::Tensor trainer_last_seed_pixels(int64_t h)
 {
 	auto g = get(h)->gaussians_;
-	return g->last_seed_pixels_.defined() ? g->last_seed_pixels_ : torch::empty({0}, g->xyz_.options().dtype(torch::kInt32).requires_grad(false));
+	return or_empty(g->last_seed_pixels_, g->xyz_, torch::kInt32);
 }
 torch::Tensor trainer_reorder_along_z_curve(int64_t h) { return get(h)->gaussians_->reorderAlongZCurve(); }
 std::vector<int64_t> trainer_last_densify(int64_t h)
@@ -531,8 +539,7 @@ void trainer_set_filter_cameras(int64_t h, torch::Tensor cameras) { get(h)->setF
 torch::Tensor trainer_filter_3d(int64_t h)
 {
 	auto t = get(h);
-	auto g = t->gaussians_;
-	return g->filter_3D_.defined() ? g->filter_3D_ : torch::empty({0}, t->background_.options().dtype(torch::kFloat32).requires_grad(false));
+	return or_empty(t->gaussians_->filter_3D_, t->background_, torch::kFloat32);
 }
 int64_t trainer_filter3d_renders(int64_t h) { return get(h)->filter3d_renders_; }
 torch::Tensor trainer_compute_filter_3d(int64_t h, torch::Tensor cameras, double variance)
@@ -554,9 +561,7 @@ int64_t trainer_create_from_ply(std::string path, int64_t sh_degree, double spat
 	g->loadPly(path);
 	g->spatial_lr_scale_ = (float)spatial_lr_scale;
 	g->trainingSetup(GaussianOptimizationParams());
-	std::lock_guard<std::mutex> lk(g_mu);
-	g_trainers[g_next] = std::make_shared<TrainStep>(g, bg);
-	return g_next++;
+	return adopt(g, bg);
 }
 void trainer_reset_opacity(int64_t h) { get(h)->gaussians_->resetOpacity(); }
 void trainer_apply_scaled_transformation(int64_t h, double s, torch::Tensor T) { get(h)->gaussians_->applyScaledTransformation((float)s, T); }

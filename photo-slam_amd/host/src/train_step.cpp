@@ -25,6 +25,21 @@ void check(int status, const char* where)
 	if (status != GSR_OK) throw std::runtime_error(std::string(where) + ": " + gsr_strerror(status));
 }
 
+// (render, viewspace_points, visibility_filter, radii, depth, alpha) of GaussianRenderer::renderWithDepth
+using RenderPackage = std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>;
+
+// THE render call of a TrainStep: the keyframe at its own size, the step's pipeline flags and background, no override colours;
+// with_depth appends the depth and alpha maps (undefined tensors otherwise).  Model: GaussianModel, or refinePose's frozen copy
+template <class Model>
+RenderPackage renderModel(TrainStep& t, const std::shared_ptr<GaussianKeyframe>& kf, const std::shared_ptr<Model>& model,
+                          const GaussianRasterizationExtensions& ext, bool with_depth)
+{
+	torch::Tensor none;
+	const int H = kf->image_height_, W = kf->image_width_;
+	if (with_depth) return GaussianRenderer::renderWithDepth(kf, H, W, model, t.pipe_, t.background_, none, 1.0f, false, ext);
+	auto p = GaussianRenderer::render(kf, H, W, model, t.pipe_, t.background_, none, 1.0f, false, ext);
+	return RenderPackage(std::get<0>(p), std::get<1>(p), std::get<2>(p), std::get<3>(p), none, none);
+}
 }  // namespace
 
 torch::Tensor fusedL1SSIMLoss(torch::Tensor rendered, torch::Tensor gt, torch::Tensor mask, float lambda_dssim, bool is_root)
@@ -163,6 +178,25 @@ ShAdamStep GaussianModel::featuresAdamStep(ShStep which) const
 	return s;
 }
 
+ShAdamStep GaussianModel::beginFeaturesStep(bool lazy, int window)
+{
+	AdamGroup& grp = groups_.at(1);
+	if (lazy && features_row_step_.defined() && features_lazy_window_ != window) syncFeatures();
+	if (lazy && !features_row_step_.defined()) {   // every row has taken the grp.step steps so far
+		features_row_step_ = torch::full({features_.size(0)}, grp.step, features_.options().dtype(torch::kInt32).requires_grad(false));
+		features_lazy_window_ = window;
+		features_lr_hist_.clear();
+	}
+	grp.step++;   // the caller takes the step; optimizerStepGroup(1) then finds no gradient
+	return featuresAdamStep(lazy ? ShStep::Lazy : ShStep::Eager);
+}
+
+void GaussianModel::endFeaturesStep(const ShAdamStep& taken)
+{
+	features_lr_hist_.insert(features_lr_hist_.begin(), {taken.lr, taken.lr_tail});
+	if (static_cast<int>(features_lr_hist_.size()) > features_lazy_window_) features_lr_hist_.pop_back();
+}
+
 void GaussianModel::syncFeatures()
 {
 	if (!features_row_step_.defined()) return;
@@ -205,31 +239,53 @@ void GaussianModel::zeroGrad()
 
 void GaussianModel::addDensificationStats(torch::Tensor& viewspace_point_tensor, torch::Tensor& update_filter)
 {
-	auto g = viewspace_point_tensor.grad();
+	addDensificationStats(viewspace_point_tensor, update_filter, viewspace_point_tensor.grad());
+}
+
+void GaussianModel::addDensificationStats(torch::Tensor& viewspace_point_tensor, torch::Tensor& update_filter, const torch::Tensor& absgrad)
+{
+	const torch::Tensor g = absgrad.defined() ? absgrad : viewspace_point_tensor.grad();
 	auto n = torch::norm(g.index({update_filter}).slice(1, 0, 2), 2, {-1}, true);
 	xyz_gradient_accum_.index_put_({update_filter}, xyz_gradient_accum_.index({update_filter}) + n);
 	denom_.index_put_({update_filter}, denom_.index({update_filter}) + 1);
 }
 
-void GaussianModel::addDensificationStats(torch::Tensor& viewspace_point_tensor, torch::Tensor& update_filter, const torch::Tensor& absgrad)
+void TrainStep::requireSingleProcess(const char* what, bool factored_counts, const char* suffix) const
 {
-	if (!absgrad.defined()) return addDensificationStats(viewspace_point_tensor, update_filter);
-	auto n = torch::norm(absgrad.index({update_filter}).slice(1, 0, 2), 2, {-1}, true);
-	xyz_gradient_accum_.index_put_({update_filter}, xyz_gradient_accum_.index({update_filter}) + n);
-	denom_.index_put_({update_filter}, denom_.index({update_filter}) + 1);
+	if (process_group_ || (factored_counts && factored_exchange_))
+		throw std::runtime_error(std::string("TrainStep: ") + what + " not supported with a process group" + suffix);
 }
 
-// a viewer's render: the raw leaves in the rasterizer, forward-only, into the second workspace
-GaussianRasterizationExtensions TrainStep::viewExtensions()
+GaussianRasterizationExtensions TrainStep::baseExtensions(RasterWorkspace* workspace) const
 {
 	GaussianRasterizationExtensions ext;
 	ext.raw_params_ = 7;
 	ext.cull_empty_tiles_ = cull_empty_tiles_;
 	ext.antialiasing_ = antialiasing_;
+	ext.workspace_ = persistent_workspace_ ? workspace : nullptr;
+	return ext;
+}
+
+// a viewer's render: forward-only, into the second workspace
+GaussianRasterizationExtensions TrainStep::viewExtensions()
+{
+	GaussianRasterizationExtensions ext = baseExtensions(&view_workspace_);
 	ext.filter_3D_ = viewFilter3D();
-	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
 	ext.forward_only_ = true;
 	return ext;
+}
+
+torch::Tensor TrainStep::trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
+                                              torch::Tensor gt_depth)
+{
+	if (process_group_) {
+		if (usesDepthLoss(gt_depth)) requireSingleProcess("the depth loss is", false, " (depth_loss_weight_ must be 0)");
+		if (kf->exposure_.defined() || optimize_exposure_) requireSingleProcess("exposure compensation is", false);
+		return trainForOneIterationDataParallel(kf, gt_image, mask);
+	}
+	auto loss = renderAndBackward(kf, gt_image, mask, gt_depth);
+	finishOneIteration();
+	return loss;
 }
 
 void TrainStep::setFilterCameras(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes)
@@ -257,7 +313,7 @@ void TrainStep::setFilterCameras(const torch::Tensor& cameras)
 void TrainStep::checkFilter3D() const
 {
 	if (!filter3d_) return;
-	if (process_group_ || factored_exchange_) throw std::runtime_error("TrainStep: filter3d_ is not supported with a process group");
+	requireSingleProcess("filter3d_ is", true);
 	if (!filter_cameras_.defined() || filter_cameras_.size(0) == 0)
 		throw std::runtime_error("TrainStep: filter3d_ is on and no cameras are registered (setFilterCameras)");
 }
@@ -277,9 +333,7 @@ torch::Tensor TrainStep::viewFilter3D(bool recompute)
 torch::Tensor TrainStep::renderView(std::shared_ptr<GaussianKeyframe> kf, bool apply_exposure)
 {
 	torch::NoGradGuard no_grad;
-	torch::Tensor override_color;
-	auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_, override_color, 1.0f,
-	                                    false, viewExtensions());
+	auto pkg = renderModel(*this, kf, gaussians_, viewExtensions(), false);
 	if (apply_exposure && kf->exposure_.defined()) return loss_utils::apply_exposure(std::get<0>(pkg), kf->exposure_);
 	return std::get<0>(pkg);
 }
@@ -295,7 +349,6 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> TrainStep
 	const auto f32 = xyz.options().dtype(torch::kFloat32).requires_grad(false), i32 = xyz.options().dtype(torch::kInt32).requires_grad(false);
 	auto wsum = torch::zeros({P}, f32), wmax = torch::zeros({P}, f32);
 	auto touched = torch::zeros({P}, i32), seen = torch::zeros({P}, i32);
-	torch::Tensor override_color;
 	for (size_t i = 0; i < keyframes.size(); i++) {
 		const auto& kf = keyframes[i];
 		GaussianRasterizationExtensions ext = viewExtensions();
@@ -304,8 +357,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> TrainStep
 		ext.out_n_touched_ = touched;
 		ext.contribution_accumulate_ = true;
 		if (!pixel_weights.empty() && pixel_weights[i].defined() && pixel_weights[i].numel()) ext.pixel_weight_ = pixel_weights[i];
-		auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_, override_color, 1.0f,
-		                                    false, ext);
+		auto pkg = renderModel(*this, kf, gaussians_, ext, false);
 		seen += (std::get<3>(pkg) > 0).to(torch::kInt32);
 	}
 	return std::make_tuple(wsum, wmax, touched, seen);
@@ -313,7 +365,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> TrainStep
 
 int64_t TrainStep::pruneUncontributing(const std::vector<std::shared_ptr<GaussianKeyframe>>& keyframes, float min_weight_max, int min_views)
 {
-	if (process_group_) throw std::runtime_error("TrainStep: pruneUncontributing is not supported with a process group");
+	requireSingleProcess("pruneUncontributing is", false);
 	torch::NoGradGuard no_grad;
 	auto score = scoreContribution(keyframes);
 	torch::Tensor mask = (std::get<3>(score) >= min_views) & (std::get<1>(score) < min_weight_max);
@@ -357,16 +409,14 @@ void TrainStep::finishExposure()
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::renderViewWithDepth(std::shared_ptr<GaussianKeyframe> kf)
 {
 	torch::NoGradGuard no_grad;
-	torch::Tensor override_color;
-	auto pkg = GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, gaussians_, pipe_, background_,
-	                                             override_color, 1.0f, false, viewExtensions());
+	auto pkg = renderModel(*this, kf, gaussians_, viewExtensions(), true);
 	return std::make_tuple(std::get<0>(pkg), std::get<4>(pkg), std::get<5>(pkg));
 }
 
 int64_t TrainStep::seedFromDepth(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image, torch::Tensor gt_depth,
                                  int iteration, bool want_pixels)
 {
-	if (process_group_ || factored_exchange_) throw std::runtime_error("TrainStep: seedFromDepth is not supported with a process group");
+	requireSingleProcess("seedFromDepth is", true);
 	auto& g = gaussians_;
 	const int64_t P = g->xyz_.defined() ? g->xyz_.size(0) : 0;
 	torch::Tensor alpha, depth;
@@ -441,35 +491,16 @@ std::tuple<torch::Tensor, torch::Tensor> TrainStep::refinePose(std::shared_ptr<G
 	auto lr = torch::cat({torch::full({3}, lr_translation, opts), torch::full({3}, lr_rotation, opts)});
 	auto m = torch::zeros({6}, opts), v = torch::zeros({6}, opts);
 	const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
-	torch::Tensor eff_mask = mask;
-	if (mask.defined() && mask.numel() && (mask == 1).all().item<bool>()) eff_mask = torch::empty({0}, mask.options());
-	GaussianRasterizationExtensions ext;
-	ext.raw_params_ = 7;
-	ext.cull_empty_tiles_ = cull_empty_tiles_;
-	ext.antialiasing_ = antialiasing_;
-	ext.filter_3D_ = viewFilter3D();
-	ext.workspace_ = persistent_workspace_ ? &view_workspace_ : nullptr;
+	const torch::Tensor eff_mask = effectiveMask(mask);
+	GaussianRasterizationExtensions ext = baseExtensions(&view_workspace_);
+	ext.filter_3D_ = viewFilter3D();   // (one call per refinement, not per iteration)
+	// (a keyframe's exposure is applied, not optimised)
+	const torch::Tensor exposure = viewpoint_cam->exposure_.defined() ? viewpoint_cam->exposure_.detach() : torch::Tensor();
 	std::vector<torch::Tensor> losses;
-	torch::Tensor override_color;
 	for (int it = 1; it <= iterations; it++) {
 		pose.apply(*kf);
-		torch::Tensor rendered, depth;
-		if (use_depth) {
-			auto pkg = GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, frozen, pipe_, background_,
-			                                             override_color, 1.0f, false, ext);
-			rendered = std::get<0>(pkg);
-			depth = std::get<4>(pkg);
-		} else {
-			auto pkg = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, frozen, pipe_, background_, override_color, 1.0f,
-			                                    false, ext);
-			rendered = std::get<0>(pkg);
-		}
-		// (a keyframe's exposure is applied, not optimised)
-		auto loss = viewpoint_cam->exposure_.defined()
-		                ? loss_utils::fused_l1_ssim_exposure(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_,
-		                                                     viewpoint_cam->exposure_.detach(), /*is_root=*/true)
-		                : fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
-		if (use_depth) loss = loss + loss_utils::depth_l1(depth, gt_depth, depth_loss_weight_, depth_min_, depth_max_);
+		auto pkg = renderModel(*this, kf, frozen, ext, use_depth);
+		auto loss = stepLoss(std::get<0>(pkg), std::get<4>(pkg), exposure, gt_image, eff_mask, gt_depth, use_depth);
 		auto grad = torch::autograd::grad({loss}, {pose.xi_})[0];
 		{
 			torch::NoGradGuard ng;
@@ -484,107 +515,91 @@ std::tuple<torch::Tensor, torch::Tensor> TrainStep::refinePose(std::shared_ptr<G
 	return std::make_tuple(w2c, losses.empty() ? torch::zeros({0}, opts) : torch::stack(losses));
 }
 
-torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
-                                           torch::Tensor gt_depth)
+// ---- the stages of renderAndBackward, in the order it runs them
+// Every refusal of a step, before anything of it happens (iteration_ has not advanced); what the last step left for its readers (the
+// pending exposure step, lastRegLosses(), lastAbsgrad()) is dropped at the points it always was: a refused call leaves the same state
+void TrainStep::checkStepSupported(const std::shared_ptr<GaussianKeyframe>& kf, bool use_depth)
 {
-	const bool use_depth = usesDepthLoss(gt_depth);
-	if (use_depth && process_group_)
-		throw std::runtime_error("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)");
+	if (use_depth) requireSingleProcess("the depth loss is", false, " (depth_loss_weight_ must be 0)");
 	exposure_kf_.reset();
 	exposure_grad_ = torch::Tensor();
-	if ((kf->exposure_.defined() || optimize_exposure_) && process_group_)
-		throw std::runtime_error("TrainStep: exposure compensation is not supported with a process group");
-	const bool reg = opacity_reg_ != 0.0 || scale_reg_ != 0.0 || isotropic_reg_ != 0.0;
-	if (reg && (process_group_ || factored_exchange_))
-		throw std::runtime_error("TrainStep: the opacity / scale / isotropy regularisers are not supported with a process group");
-	if (mcmc_ && (process_group_ || factored_exchange_))
-		throw std::runtime_error("TrainStep: mcmc_ is not supported with a process group");
-	if (absgrad_ && (process_group_ || factored_exchange_))
-		throw std::runtime_error("TrainStep: absgrad_ is not supported with a process group");
-	checkFilter3D();   // (refuses a process group and a missing camera list before anything of the step happens)
+	if (kf->exposure_.defined() || optimize_exposure_) requireSingleProcess("exposure compensation is", false);
+	if (usesGeomReg()) requireSingleProcess("the opacity / scale / isotropy regularisers are", true);
+	if (mcmc_) requireSingleProcess("mcmc_ is", true);
+	if (absgrad_) requireSingleProcess("absgrad_ is", true);
+	checkFilter3D();   // (refuses a process group and a missing camera list)
 	last_reg_losses_ = torch::Tensor();
 	last_absgrad_ = torch::Tensor();
-	auto& g = gaussians_;
-	if (optimize_exposure_ && !kf->exposure_.defined())   // the identity at first use
-		kf->exposure_ = torch::eye(3, 4, g->xyz_.options().requires_grad(false));
+	if (optimize_exposure_ && !kf->exposure_.defined())   // the identity at first use (created before the check it always passes)
+		kf->exposure_ = torch::eye(3, 4, gaussians_->xyz_.options().requires_grad(false));
 	if (kf->exposure_.defined() && (kf->exposure_.dim() != 2 || kf->exposure_.size(0) != 3 || kf->exposure_.size(1) != 4 ||
 	                                kf->exposure_.scalar_type() != torch::kFloat32 || !kf->exposure_.is_contiguous()))
 		throw std::runtime_error("a keyframe's exposure_ must be a contiguous float32 [3, 4] tensor");
-	iteration_++;
-	// the position learning rate follows the iteration (src/gaussian_mapper.cpp:672-674) or -- a SLAM session -- the number of
-	// times THIS keyframe has been used (:663-671): the caller says which through position_lr_step_
-	g->updateLearningRate(position_lr_step_ >= 0 ? std::min(position_lr_step_, g->opt_.position_lr_max_steps_) : iteration_);
-	GaussianPipelineParams& pipe = pipe_;
-	torch::Tensor override_color;
-	if (factored_exchange_) {
-		const auto P = g->xyz_.size(0);
-		sh_send_ = torch::empty({P + 1, 3}, g->xyz_.options().requires_grad(false));
-		sh_grad_view_ = sh_send_.narrow(0, 0, P);
-		sh_send_.select(0, P).copy_(kf->camera_center_.detach().reshape({3}));
-		// the packed form needs the fused [P,16,3] step of the views (the other layouts take the dense route)
-		packed_this_step_ = packed_exchange_ && process_group_ && g->features_.size(1) == 16 && g->groups_.size() > 1 &&
-		                    g->features_.is_contiguous() && !pipe_.convert_SHs_;
-		if (process_group_ && !packed_this_step_) {
-			const int64_t N = process_group_->getSize();
-			if (!sh_gathered_.defined() || sh_gathered_.size(0) != N || sh_gathered_.size(1) != P + 1 ||
-			    sh_gathered_.device() != sh_send_.device())
-				sh_gathered_ = torch::empty({N, P + 1, 3}, sh_send_.options());
-		}
-		if (packed_this_step_) {
-			// persistent message buffers sized for the worst case (every Gaussian visible), allocated HERE -- before the passes
-			// are enqueued, like sh_gathered_
-			const int64_t N = process_group_->getSize(), words = packedViewWords(P, (P + 3) / 4 * 4);
-			const auto io = sh_send_.options().dtype(torch::kInt32);
-			if (!sh_packed_send_.defined() || sh_packed_send_.numel() != words || sh_packed_send_.device() != sh_send_.device()) {
-				sh_packed_send_ = torch::empty({words}, io);
-				sh_packed_gathered_ = torch::empty({N * words}, io);
-				sh_gathered_ = torch::Tensor();
-			}
-			if (sh_packed_gathered_.numel() != N * words) sh_packed_gathered_ = torch::empty({N * words}, io);
-		}
-	} else {
+}
+
+// the buffers of the view-factored exchange (none without it): this view's message and what the gather of this step writes
+void TrainStep::prepareExchangeBuffers(const std::shared_ptr<GaussianKeyframe>& kf)
+{
+	auto& g = gaussians_;
+	if (!factored_exchange_) {
 		sh_send_ = torch::Tensor();
 		sh_grad_view_ = torch::Tensor();
 		sh_gathered_ = torch::Tensor();
 		packed_this_step_ = false;
+		return;
 	}
-	// the extensions of this step's render: the raw leaves in the rasterizer, and what the blocks below switch on
-	GaussianRasterizationExtensions ext;
-	ext.raw_params_ = 7;
-	ext.sh_grad_view_ = sh_grad_view_;
-	ext.cull_empty_tiles_ = cull_empty_tiles_;
-	ext.antialiasing_ = antialiasing_;
-	// the 3-D smoothing filter: recomputed when undefined and every filter3d_interval_ iterations, before this iteration's render
-	ext.filter_3D_ = viewFilter3D(filter3d_interval_ > 0 && iteration_ % filter3d_interval_ == 0);
-	ext.workspace_ = persistent_workspace_ ? &workspace_ : nullptr;
-	torch::Tensor reg_loss;
-	if (reg) {
-		ext.opacity_reg_ = opacity_reg_;
-		ext.scale_reg_ = scale_reg_;
-		ext.isotropic_reg_ = isotropic_reg_;
-		// (the loss values are formed only when somebody reads them)
-		if (read_reg_losses_) ext.reg_loss_ = reg_loss = torch::zeros({3}, g->xyz_.options().dtype(torch::kFloat32).requires_grad(false));
+	const auto P = g->xyz_.size(0);
+	sh_send_ = torch::empty({P + 1, 3}, g->xyz_.options().requires_grad(false));
+	sh_grad_view_ = sh_send_.narrow(0, 0, P);
+	sh_send_.select(0, P).copy_(kf->camera_center_.detach().reshape({3}));
+	// the packed form needs the fused [P,16,3] step of the views (the other layouts take the dense route)
+	packed_this_step_ = packed_exchange_ && process_group_ && g->features_.size(1) == 16 && g->groups_.size() > 1 &&
+	                    g->features_.is_contiguous() && !pipe_.convert_SHs_;
+	if (process_group_ && !packed_this_step_) {
+		const int64_t N = process_group_->getSize();
+		if (!sh_gathered_.defined() || sh_gathered_.size(0) != N || sh_gathered_.size(1) != P + 1 ||
+		    sh_gathered_.device() != sh_send_.device())
+			sh_gathered_ = torch::empty({N, P + 1, 3}, sh_send_.options());
 	}
-	ShAdamStep& sh_adam = ext.sh_adam_;
-	const auto& o = g->opt_;
-	const bool rebuilds = densifyDue();
-	bool lazy = false;
-	// The fused optimizer steps advance their step counters HERE, so they are taken only when render() will really hand them
-	// to the rasterizer (gaussian_renderer.h: sh_in_rasterizer, raw_params_ == 7): with convert_SHs_ the rasterizer sees colours,
-	// not the SH tensor, and with compute_cov3D_ a covariance, not the raw scaling / rotation leaves -- autograd then leaves
-	// dense gradients and optimizerStepGroup() takes those groups' steps.
-	if (fused_sh_adam_ && !factored_exchange_ && !rebuilds && iteration_ < o.iterations_ && g->groups_.size() > 1 &&
-	    g->features_.size(1) == 16 && !pipe.convert_SHs_) {
-		auto& grp = g->groups_[1];
-		lazy = lazy_sh_adam_window_ >= 2 && g->features_.is_contiguous();
-		if (lazy && g->features_row_step_.defined() && g->features_lazy_window_ != lazy_sh_adam_window_) g->syncFeatures();
-		if (lazy && !g->features_row_step_.defined()) {   // every row has taken the grp.step steps so far
-			g->features_row_step_ = torch::full({g->features_.size(0)}, grp.step, g->features_.options().dtype(torch::kInt32).requires_grad(false));
-			g->features_lazy_window_ = lazy_sh_adam_window_;
-			g->features_lr_hist_.clear();
+	if (packed_this_step_) {
+		// persistent message buffers sized for the worst case (every Gaussian visible), allocated HERE -- before the passes
+		// are enqueued, like sh_gathered_
+		const int64_t N = process_group_->getSize(), words = packedViewWords(P, (P + 3) / 4 * 4);
+		const auto io = sh_send_.options().dtype(torch::kInt32);
+		if (!sh_packed_send_.defined() || sh_packed_send_.numel() != words || sh_packed_send_.device() != sh_send_.device()) {
+			sh_packed_send_ = torch::empty({words}, io);
+			sh_packed_gathered_ = torch::empty({N * words}, io);
+			sh_gathered_ = torch::Tensor();
 		}
-		grp.step++;   // the step happens inside backward; optimizerStepGroup(1) then finds no gradient
-		sh_adam = g->featuresAdamStep(lazy ? GaussianModel::ShStep::Lazy : GaussianModel::ShStep::Eager);
+		if (sh_packed_gathered_.numel() != N * words) sh_packed_gathered_ = torch::empty({N * words}, io);
+	}
+}
+
+// the three regularisers; returns the [3] tensor their loss values are written to (formed only when somebody reads them)
+torch::Tensor TrainStep::planRegularisers(GaussianRasterizationExtensions& ext) const
+{
+	if (!usesGeomReg()) return torch::Tensor();
+	ext.opacity_reg_ = opacity_reg_;
+	ext.scale_reg_ = scale_reg_;
+	ext.isotropic_reg_ = isotropic_reg_;
+	if (read_reg_losses_) ext.reg_loss_ = torch::zeros({3}, gaussians_->xyz_.options().dtype(torch::kFloat32).requires_grad(false));
+	return ext.reg_loss_;
+}
+
+// The Adam step of the SH tensor this iteration takes outside optimizerStepGroup(1), if any; returns whether its rows step lazily.
+// The step counter advances HERE, so the step is planned only when render() will really hand it to the rasterizer
+// (gaussian_renderer.h: sh_in_rasterizer): with convert_SHs_ the rasterizer sees colours, not the SH tensor -- autograd then leaves
+// a dense gradient and optimizerStepGroup() takes the step.
+bool TrainStep::planFeaturesStep(GaussianRasterizationExtensions& ext, bool rebuilds)
+{
+	auto& g = gaussians_;
+	auto steppable = [&] {
+		return !rebuilds && iteration_ < g->opt_.iterations_ && g->groups_.size() > 1 && g->features_.size(1) == 16 && !pipe_.convert_SHs_;
+	};
+	bool lazy = false;
+	if (fused_sh_adam_ && !factored_exchange_ && steppable()) {   // the step happens inside backward
+		lazy = lazy_sh_adam_window_ >= 2 && g->features_.is_contiguous();
+		ext.sh_adam_ = g->beginFeaturesStep(lazy, lazy_sh_adam_window_);
 	}
 	// Data-parallel step with the view-factored exchange: the SH rows step AFTER the exchange (stepFeaturesFromViews), and lazily
 	// there too -- a row no view of the batch lights takes a zero-gradient step, i.e. it may take it later.  The forward pass
@@ -592,22 +607,20 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	// uses it only to run this step's slice of the rows' rotating catch-up next to the blend kernel.
 	views_adam_ = ShAdamStep();
 	views_adam_pending_ = false;
-	if (factored_exchange_ && lazy_sh_adam_window_ >= 3 && !rebuilds && iteration_ < o.iterations_ && g->groups_.size() > 1 &&
-	    g->features_.size(1) == 16 && g->features_.is_contiguous() && !pipe.convert_SHs_) {
-		auto& grp = g->groups_[1];
+	if (factored_exchange_ && lazy_sh_adam_window_ >= 3 && steppable() && g->features_.is_contiguous()) {
 		lazy = true;
-		if (g->features_row_step_.defined() && g->features_lazy_window_ != lazy_sh_adam_window_) g->syncFeatures();
-		if (!g->features_row_step_.defined()) {   // every row has taken the grp.step steps so far
-			g->features_row_step_ = torch::full({g->features_.size(0)}, grp.step, g->features_.options().dtype(torch::kInt32).requires_grad(false));
-			g->features_lazy_window_ = lazy_sh_adam_window_;
-			g->features_lr_hist_.clear();
-		}
-		grp.step++;   // the step happens in stepFeaturesFromViews(); optimizerStepGroup(1) finds no gradient
-		sh_adam = g->featuresAdamStep(GaussianModel::ShStep::Lazy);
-		views_adam_ = sh_adam;
+		ext.sh_adam_ = g->beginFeaturesStep(true, lazy_sh_adam_window_);
+		views_adam_ = ext.sh_adam_;
 		views_adam_pending_ = true;
 	}
-	if (!lazy) g->syncFeatures();   // the render below reads every visible row as it is
+	if (!lazy) g->syncFeatures();   // the render reads every visible row as it is
+	return lazy;
+}
+
+// how the passes overlap with the exchange: the gather's own stream, the SH step's two scheduling switches, the prepacked message
+void TrainStep::planExchangeOverlap(GaussianRasterizationExtensions& ext)
+{
+	auto& g = gaussians_;
 #ifndef GSR_HOST_NO_HIP
 	// early_gather_ (GSR_EARLY_GATHER=0/1 overrides): off = the gather is issued on the compute stream behind the whole backward pass
 	static const int early_env = [] { const char* e = getenv("GSR_EARLY_GATHER"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }();
@@ -620,87 +633,124 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		gather_stream_in_use_ = true;
 	}
 #endif
-	sh_adam.no_side_stream = no_side_stream_;
-	sh_adam.lazy_slice_late = lazy_slice_late_;
+	ext.sh_adam_.no_side_stream = no_side_stream_;
+	ext.sh_adam_.lazy_slice_late = lazy_slice_late_;
 	// packed exchange: the backward pass writes this view's message itself (rows + header; the mask / prefix sections are
-	// planned from the radii right behind the forward pass, below) -- no pack launches between the backward pass and the gather
+	// planned from the radii right behind the forward pass) -- no pack launches between the backward pass and the gather
 	static const int pack_env = [] { const char* e = getenv("GSR_PACK_IN_BACKWARD"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }();
 	prepacked_this_step_ = packed_this_step_ && (pack_env >= 0 ? pack_env != 0 : pack_in_backward_);
 	if (prepacked_this_step_) {
 		ext.packed_view_ = sh_packed_send_;
 		ext.packed_capacity_ = (g->xyz_.size(0) + 3) / 4 * 4;
 	}
+}
+
+// The Adam steps of xyz, opacity, scaling, rotation = groups 0, 2, 3, 4 (trainingSetup) inside backward, on the iterations the SH
+// step is fused on; optimizerStepGroup() then finds no gradient on them.  With compute_cov3D_ the rasterizer sees a covariance,
+// not the raw scaling / rotation leaves, and the groups take their dense steps.
+// (resets: an iteration that resets the opacity replaces that leaf AFTER backward: the reference's optimizer step then skips it --
+// no gradient -- while a step fused into backward would already have been taken: src/gaussian_mapper.cpp:732-735)
+void TrainStep::planGeomStep(GaussianRasterizationExtensions& ext, bool resets)
+{
+	auto& g = gaussians_;
+	if (!(fused_geom_adam_ && !factored_exchange_ && ext.sh_adam_.exp_avg.defined() && g->groups_.size() == 5 && !pipe_.compute_cov3D_ && !resets))
+		return;
 	GeomAdamStep& geom_adam = ext.geom_adam_;
-	// (an iteration that resets the opacity replaces that leaf AFTER backward: the reference's optimizer step then skips it -- no
-	// gradient -- while a step fused into backward would already have been taken: src/gaussian_mapper.cpp:732-735)
-	const bool resets = densify_ && !mcmc_ && iteration_ < o.densify_until_iter_ && o.opacity_reset_interval_ &&
-	                    iteration_ % o.opacity_reset_interval_ == 0;
-	if (fused_geom_adam_ && !factored_exchange_ && sh_adam.exp_avg.defined() && g->groups_.size() == 5 && !pipe.compute_cov3D_ && !resets) {
-		// xyz, opacity, scaling, rotation = groups 0, 2, 3, 4 (trainingSetup); their steps happen inside backward, and
-		// optimizerStepGroup() then finds no gradient on them
-		for (int gi : {0, 2, 3, 4}) {
-			auto& grp = g->groups_[static_cast<size_t>(gi)];
-			grp.step++;
-			geom_adam.param.push_back(grp.param.detach());
-			geom_adam.exp_avg.push_back(grp.exp_avg);
-			geom_adam.exp_avg_sq.push_back(grp.exp_avg_sq);
-			geom_adam.lr.push_back(grp.lr * g->lr_scale_);
-			geom_adam.step.push_back(grp.step);
-		}
+	for (int gi : {0, 2, 3, 4}) {
+		auto& grp = g->groups_[static_cast<size_t>(gi)];
+		grp.step++;
+		geom_adam.param.push_back(grp.param.detach());
+		geom_adam.exp_avg.push_back(grp.exp_avg);
+		geom_adam.exp_avg_sq.push_back(grp.exp_avg_sq);
+		geom_adam.lr.push_back(grp.lr * g->lr_scale_);
+		geom_adam.step.push_back(grp.step);
 	}
+}
+
+void TrainStep::planStatistics(GaussianRasterizationExtensions& ext)
+{
+	auto& g = gaussians_;
 	// the statistics are fused (or over) in every mode of this step: nobody reads the viewspace gradient or dL_dcov3D
 	ext.training_outputs_only_ = true;
-	// the densification statistics of this view (:714-719) are added by the backward kernel that holds dL_dmean2D in
-	// registers
-	if (iteration_ < o.densify_until_iter_) ext.view_stats_ = {g->xyz_gradient_accum_, g->denom_, g->max_radii2D_};
+	// the densification statistics of this view (:714-719) are added by the backward kernel that holds dL_dmean2D in registers
+	if (iteration_ < g->opt_.densify_until_iter_) ext.view_stats_ = {g->xyz_gradient_accum_, g->denom_, g->max_radii2D_};
 	// AbsGS: the statistics accumulate the norm of the absolute pair (only they read it)
 	if (absgrad_ && !ext.view_stats_.empty())
 		ext.absgrad_ = last_absgrad_ = torch::empty({g->xyz_.size(0), 2}, g->xyz_.options().requires_grad(false));
-	g->in_lazy_step_ = lazy;
+}
+
+// rendered * mask with a mask of ones is the identity (src/gaussian_mapper.cpp:692-693; most keyframes carry a full mask):
+// recognised ONCE per mask tensor (one reduction + host read when a keyframe's mask is first seen); the loss kernels then skip its
+// 2 x 25 MB of reads at 1080p.  Returns the mask, or an empty tensor for one of ones (= none: FusedL1SSIMFunction::forward).
+torch::Tensor TrainStep::effectiveMask(const torch::Tensor& mask)
+{
+	if (!mask.defined() || !mask.numel()) return mask;
+	// remembered per TensorImpl through a weak pointer (it keeps the object's address from being reused by another tensor
+	// after this one is freed) together with the version counter (in-place writes invalidate the entry)
+	auto* impl = mask.unsafeGetTensorImpl();
+	const int64_t version = static_cast<int64_t>(mask._version());
+	auto it = mask_is_ones_.find(impl);
+	if (it == mask_is_ones_.end() || it->second.self.expired() || it->second.version != version) {
+		if (mask_is_ones_.size() >= 64) mask_is_ones_.clear();
+		torch::NoGradGuard ng;
+		MaskEntry e;
+		e.self = c10::weak_intrusive_ptr<c10::TensorImpl, c10::UndefinedTensorImpl>(mask.getIntrusivePtr());
+		e.version = version;
+		e.ones = (mask == 1).all().item<bool>();
+		it = mask_is_ones_.insert_or_assign(impl, std::move(e)).first;
+	}
+	return it->second.ones ? torch::empty({0}, mask.options()) : mask;
+}
+
+// the loss of a step and of a pose refinement: fused L1 + lambda_dssim_ (1 - SSIM) behind `exposure` (if defined), plus the depth L1
+// term.  The caller calls backward() on this very value (is_root; the sum's backward hands both terms the root's exact 1).
+torch::Tensor TrainStep::stepLoss(const torch::Tensor& rendered, const torch::Tensor& depth, const torch::Tensor& exposure, const torch::Tensor& gt_image,
+                                  const torch::Tensor& eff_mask, const torch::Tensor& gt_depth, bool use_depth) const
+{
+	const float lambda_dssim = gaussians_->opt_.lambda_dssim_;
+	auto loss = exposure.defined() ? loss_utils::fused_l1_ssim_exposure(rendered, gt_image, eff_mask, lambda_dssim, exposure, /*is_root=*/true)
+	                               : fusedL1SSIMLoss(rendered, gt_image, eff_mask, lambda_dssim, /*is_root=*/true);
+	if (use_depth) loss = loss + loss_utils::depth_l1(depth, gt_depth, depth_loss_weight_, depth_min_, depth_max_);
+	return loss;
+}
+
+torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
+                                           torch::Tensor gt_depth)
+{
+	const bool use_depth = usesDepthLoss(gt_depth);
+	checkStepSupported(kf, use_depth);
+	auto& g = gaussians_;
+	iteration_++;
+	// the position learning rate follows the iteration (src/gaussian_mapper.cpp:672-674) or -- a SLAM session -- the number of
+	// times THIS keyframe has been used (:663-671): the caller says which through position_lr_step_
+	g->updateLearningRate(position_lr_step_ >= 0 ? std::min(position_lr_step_, g->opt_.position_lr_max_steps_) : iteration_);
+	prepareExchangeBuffers(kf);
+	// the extensions of this step's render, and what the stages below switch on
+	GaussianRasterizationExtensions ext = baseExtensions(&workspace_);
+	ext.sh_grad_view_ = sh_grad_view_;
+	// the 3-D smoothing filter: recomputed when undefined and every filter3d_interval_ iterations, before this iteration's render
+	ext.filter_3D_ = viewFilter3D(filter3d_interval_ > 0 && iteration_ % filter3d_interval_ == 0);
+	const torch::Tensor reg_loss = planRegularisers(ext);
+	const bool lazy = planFeaturesStep(ext, densifyDue());
+	planExchangeOverlap(ext);
+	planGeomStep(ext, opacityResetDue());
+	planStatistics(ext);
 	// (with the depth loss: the same render with the depth and alpha maps appended, GaussianRenderer::renderWithDepth)
-	auto pkg = use_depth ? GaussianRenderer::renderWithDepth(kf, kf->image_height_, kf->image_width_, g, pipe, background_,
-	                                                         override_color, 1.0f, false, ext)
-	                     : [&] {
-		                       auto p4 = GaussianRenderer::render(kf, kf->image_height_, kf->image_width_, g, pipe, background_,
-		                                                          override_color, 1.0f, false, ext);
-		                       return std::make_tuple(std::get<0>(p4), std::get<1>(p4), std::get<2>(p4), std::get<3>(p4),
-		                                              torch::Tensor(), torch::Tensor());
-	                       }();
-	g->in_lazy_step_ = false;
+	RenderPackage pkg;
+	{
+		g->in_lazy_step_ = lazy;
+		ScopeExit clear{[&] { g->in_lazy_step_ = false; }};   // (on every way out of the render)
+		pkg = renderModel(*this, kf, g, ext, use_depth);
+	}
 	if (factored_exchange_ && packed_this_step_) beginCountExchange();   // (the forward pass has left this view's visible count)
 	if (prepacked_this_step_) planPackedView(std::get<3>(pkg));
-	auto rendered = std::get<0>(pkg);
 	last_viewspace_ = std::get<1>(pkg);
 	last_visibility_ = std::get<2>(pkg);
 	last_radii_ = std::get<3>(pkg);
-	// rendered * mask with a mask of ones is the identity (src/gaussian_mapper.cpp:692-693; most keyframes carry a full mask):
-	// recognised ONCE per mask tensor (one reduction + host read when a keyframe's mask is first seen, remembered by storage
-	// pointer and version counter); the loss kernels then skip its 2 x 25 MB of reads at 1080p
-	torch::Tensor eff_mask = mask;
-	if (mask.defined() && mask.numel()) {
-		// remembered per TensorImpl through a weak pointer (it keeps the object's address from being reused by another tensor
-		// after this one is freed) together with the version counter (in-place writes invalidate the entry)
-		auto* impl = mask.unsafeGetTensorImpl();
-		const int64_t version = static_cast<int64_t>(mask._version());
-		auto it = mask_is_ones_.find(impl);
-		if (it == mask_is_ones_.end() || it->second.self.expired() || it->second.version != version) {
-			if (mask_is_ones_.size() >= 64) mask_is_ones_.clear();
-			torch::NoGradGuard ng;
-			MaskEntry e;
-			e.self = c10::weak_intrusive_ptr<c10::TensorImpl, c10::UndefinedTensorImpl>(mask.getIntrusivePtr());
-			e.version = version;
-			e.ones = (mask == 1).all().item<bool>();
-			it = mask_is_ones_.insert_or_assign(impl, std::move(e)).first;
-		}
-		if (it->second.ones) eff_mask = torch::empty({0}, mask.options());   // (an empty mask = none: FusedL1SSIMFunction::forward)
-	}
+	const torch::Tensor eff_mask = effectiveMask(mask);
 	torch::Tensor exposure_leaf;   // (a leaf of this step's graph: the keyframe's tensor itself is stepped in place afterwards)
 	if (kf->exposure_.defined()) exposure_leaf = kf->exposure_.detach().set_requires_grad(optimize_exposure_);
-	auto loss = exposure_leaf.defined()
-	                ? loss_utils::fused_l1_ssim_exposure(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, exposure_leaf, /*is_root=*/true)
-	                : fusedL1SSIMLoss(rendered, gt_image, eff_mask, g->opt_.lambda_dssim_, /*is_root=*/true);
-	// (the sum's backward hands both terms the root's exact 1: is_root stays valid)
-	if (use_depth) loss = loss + loss_utils::depth_l1(std::get<4>(pkg), gt_depth, depth_loss_weight_, depth_min_, depth_max_);
+	auto loss = stepLoss(std::get<0>(pkg), std::get<4>(pkg), exposure_leaf, gt_image, eff_mask, gt_depth, use_depth);
 	// the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward()
 	if (!root_grad_.defined() || root_grad_.device() != loss.device()) root_grad_ = torch::ones_like(loss).detach();
 	loss.backward(root_grad_);
@@ -713,11 +763,8 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 		exposure_kf_ = kf;
 		exposure_grad_ = exposure_leaf.grad();
 	}
-	if (lazy && !views_adam_pending_) {   // the step is taken: its learning rates join the history the later catch-ups need
-		auto& hist = g->features_lr_hist_;
-		hist.insert(hist.begin(), {sh_adam.lr, sh_adam.lr_tail});
-		if (static_cast<int>(hist.size()) > g->features_lazy_window_) hist.pop_back();
-	}
+	// the step is taken: its learning rates join the history the later catch-ups need (the factored step: finishFeaturesFromViews)
+	if (lazy && !views_adam_pending_) g->endFeaturesStep(ext.sh_adam_);
 	return loss;
 }
 
@@ -753,29 +800,21 @@ void TrainStep::stepFeaturesFromViews(torch::Tensor campos_views, torch::Tensor 
 	if (iteration_ >= g->opt_.iterations_) return;
 	const int64_t P = g->xyz_.size(0), n = dL_dcolor_views.size(1);
 	if (row0 < 0 || row0 + n > P) throw std::runtime_error("stepFeaturesFromViews: the part exceeds the Gaussians");
-	if (views_adam_pending_) {
-		// lazy rows: renderAndBackward() advanced the step counter and prepared the struct; rows no view lights stay behind
-		ShAdamStep a = views_adam_;
-		a.exp_avg = views_adam_.exp_avg.narrow(0, row0, n);
-		a.exp_avg_sq = views_adam_.exp_avg_sq.narrow(0, row0, n);
-		a.row_step = views_adam_.row_step.narrow(0, row0, n);
-		auto sh = g->features_.detach().narrow(0, row0, n);
-		shAdamFromViews(g->xyz_.detach().narrow(0, row0, n), campos_views, dL_dcolor_views, g->active_sh_degree_,
-		                1.0f / static_cast<float>(dL_dcolor_views.size(0)), sh, a);
-		return;
+	if (!views_adam_pending_) {
+		g->syncFeatures();
+		if (g->features_.size(1) != 16 || g->groups_.size() < 2) {   // other layouts: gradient tensor + separate pass (whole batch only)
+			if (row0 != 0 || n != P) throw std::runtime_error("stepFeaturesFromViews: parts need the [P,16,3] SH layout");
+			setFeaturesGradFromViews(campos_views, dL_dcolor_views);
+			finishAdamGroup(1);
+			return;
+		}
 	}
-	g->syncFeatures();
-	if (g->features_.size(1) != 16 || g->groups_.size() < 2) {   // other layouts: gradient tensor + separate pass (whole batch only)
-		if (row0 != 0 || n != P) throw std::runtime_error("stepFeaturesFromViews: parts need the [P,16,3] SH layout");
-		setFeaturesGradFromViews(campos_views, dL_dcolor_views);
-		finishAdamGroup(1);
-		return;
-	}
-	auto& grp = g->groups_[1];
-	if (first_part) grp.step++;
-	ShAdamStep a = g->featuresAdamStep(GaussianModel::ShStep::Eager);
+	// lazy rows: renderAndBackward() advanced the step counter and prepared the struct; rows no view lights stay behind.  Otherwise
+	// the eager step of every row, whose counter advances with the first part only
+	ShAdamStep a = views_adam_pending_ ? views_adam_ : first_part ? g->beginFeaturesStep(false, 0) : g->featuresAdamStep(GaussianModel::ShStep::Eager);
 	a.exp_avg = a.exp_avg.narrow(0, row0, n);
 	a.exp_avg_sq = a.exp_avg_sq.narrow(0, row0, n);
+	if (a.row_step.defined()) a.row_step = a.row_step.narrow(0, row0, n);
 	auto sh = g->features_.detach().narrow(0, row0, n);
 	shAdamFromViews(g->xyz_.detach().narrow(0, row0, n), campos_views, dL_dcolor_views, g->active_sh_degree_,
 	                1.0f / static_cast<float>(dL_dcolor_views.size(0)), sh, a);
@@ -793,23 +832,17 @@ void TrainStep::stepFeaturesFromPackedViews(torch::Tensor messages, int64_t msg_
 		return;
 	}
 	g->syncFeatures();
-	auto& grp = g->groups_[1];
-	grp.step++;
-	shAdamFromPackedViews(g->xyz_.detach(), messages, msg_stride, n_views, g->active_sh_degree_, scale, sh,
-	                      g->featuresAdamStep(GaussianModel::ShStep::Eager));
+	shAdamFromPackedViews(g->xyz_.detach(), messages, msg_stride, n_views, g->active_sh_degree_, scale, sh, g->beginFeaturesStep(false, 0));
 }
 
 void TrainStep::finishFeaturesFromViews()
 {
 	if (!views_adam_pending_) return;
 	torch::NoGradGuard ng;
-	auto& g = gaussians_;
 	views_adam_pending_ = false;
 	// (the rotating catch-up that bounds the lag of the rows no view lights ran inside the rasterizer's backward, next to the
 	// blend kernel: gsr_backward_args.sh_adam together with dL_dcolor_view)
-	auto& hist = g->features_lr_hist_;   // the step is taken: its learning rates join the history the later catch-ups need
-	hist.insert(hist.begin(), {views_adam_.lr, views_adam_.lr_tail});
-	if (static_cast<int>(hist.size()) > g->features_lazy_window_) hist.pop_back();
+	gaussians_->endFeaturesStep(views_adam_);   // the step is taken: its learning rates join the history the later catch-ups need
 	views_adam_ = ShAdamStep();
 }
 
@@ -877,22 +910,19 @@ void TrainStep::finishBegin()
 	torch::NoGradGuard ng;
 	auto& g = gaussians_;
 	// (the statistics of :714-719 were added inside backward: view_stats)
-	if (iteration_ < g->opt_.densify_until_iter_ && densify_) {
-		const auto& o = g->opt_;
-		if (densifyDue()) {
-			const int size_threshold = iteration_ > prune_big_point_after_iter_ ? 20 : 0;   // src/gaussian_mapper.cpp:723
-			g->zeroGrad();   // shapes change; this step's update is skipped
-			last_absgrad_ = torch::Tensor();   // (its rows are those of the model before the rebuild)
-			if (mcmc_) {
-				last_mcmc_counts_ = g->relocateDead(mcmc_min_opacity_, generator_);
-				g->addNew(mcmc_cap_max_, generator_, mcmc_min_opacity_);
-			} else {
-				// (AbsGS: the accumulator holds the absolute statistic, which has its own threshold)
-				const float max_grad = absgrad_ ? densify_abs_grad_threshold_ : o.densify_grad_threshold_;
-				last_densify_ = g->densifyAndPrune(max_grad, densify_min_opacity_, cameras_extent_, size_threshold, generator_);
-			}
+	if (densifyDue()) {
+		const int size_threshold = iteration_ > prune_big_point_after_iter_ ? 20 : 0;   // src/gaussian_mapper.cpp:723
+		g->zeroGrad();   // shapes change; this step's update is skipped
+		last_absgrad_ = torch::Tensor();   // (its rows are those of the model before the rebuild)
+		if (mcmc_) {
+			last_mcmc_counts_ = g->relocateDead(mcmc_min_opacity_, generator_);
+			g->addNew(mcmc_cap_max_, generator_, mcmc_min_opacity_);
+		} else {
+			// (AbsGS: the accumulator holds the absolute statistic, which has its own threshold)
+			const float max_grad = absgrad_ ? densify_abs_grad_threshold_ : g->opt_.densify_grad_threshold_;
+			last_densify_ = g->densifyAndPrune(max_grad, densify_min_opacity_, cameras_extent_, size_threshold, generator_);
 		}
-		if (!mcmc_ && o.opacity_reset_interval_ && iteration_ % o.opacity_reset_interval_ == 0) g->resetOpacity();
 	}
+	if (opacityResetDue()) g->resetOpacity();
 	if (iteration_ < g->opt_.iterations_) g->beginOptimizerStep();
 }
