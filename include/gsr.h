@@ -596,6 +596,51 @@ size_t gsr_depth_loss_scratch_bytes(int width, int height);
 int gsr_depth_l1_loss(const float* depth, const float* gt_depth, int width, int height, float min_depth, float max_depth,
                       float weight, float* grad_depth, float* loss, char* scratch, void* stream);
 
+/* Monocular depth prior: a relative-depth map q (MiDaS / Depth Anything style) that is right only up to an unknown scale and shift,
+ * against the rendered depth map D (sum z alpha T) and alpha map A of one view.  Per pixel p of the [H,W] view:
+ *   valid = A >= alpha_min  &&  D > 0  &&  q finite and > 0  &&  (valid == NULL || valid[p] != 0)      (NaN fails every test)
+ *   r     = D / A (the expected depth), or A / D with GSR_DEPTH_PRIOR_INVERSE (for affine-invariant inverse-depth networks);
+ *           a pixel whose r is not a positive finite float counts as invalid too.  alpha == NULL means A = 1.
+ *   n     = the number of valid pixels;  x~ = mean over the valid pixels;  S_x = sqrt(sum_valid (x - x~)^2)
+ * Aligned L1 (default):  (s, t) = argmin sum_valid (s q + t - r)^2 in closed form, constants for the gradient;
+ *   loss = weight * sum_valid |r - (s q + t)| / (H W)             (the normalisation of gsr_depth_l1_loss: the weights compare)
+ *   dloss/dr = weight * sign(r - (s q + t)) / (H W), sign(0) = 0
+ * GSR_DEPTH_PRIOR_PEARSON:  loss = weight * (1 - rho), rho the Pearson correlation of r and q over the valid pixels;
+ *   dloss/dr_p = -weight * [ (q_p - q~) / (S_q S_r) - rho (r_p - r~) / S_r^2 ]                          (the full gradient)
+ * Chain rule: dr/dD = 1/A, dr/dA = -D/A^2; inverse: dr/dD = -A/D^2, dr/dA = 1/D.  grad_depth and grad_alpha [H,W] are written for
+ * every pixel, exactly 0 where the pixel is invalid; grad_alpha is NULL exactly when alpha is.
+ * fit[4] = {s, t, rho, n} is written on the device in both modes (rho: a quality signal for the caller); nothing is read on the host.
+ * Degenerate input: n < 2, or sum (q - q~)^2 <= 1e-12 sum q^2 -- and, in the Pearson mode, the same test on r: the loss is 0, both
+ * gradients are all zero, fit = {0, 0, 0, n}.  (Aligned L1 with only r failing the test: s, t and the loss stand, rho = 0.)
+ * No NaN or Inf leaves the kernels for any input.
+ * The six moment sums (n, q, r, qq, qr, rr), the fit, the residuals and the gradients are formed in fp64 and rounded once; sums run
+ * per thread, per workgroup, then over a fixed grid in index order by one workgroup: no atomics, the same bits on every run, and
+ * the same bits from the 16-byte path (every pointer 16-byte aligned) and the scalar path.  Four launches (Pearson: three; fit
+ * only: two).  With grad_depth == NULL && loss == NULL only fit is written (grad_alpha must be NULL then); otherwise both are given.
+ * scratch: gsr_depth_prior_scratch_bytes(width, height) device bytes, 8-byte aligned. */
+#define GSR_DEPTH_PRIOR_INVERSE 1
+#define GSR_DEPTH_PRIOR_PEARSON 2
+typedef struct gsr_depth_prior_args {
+	int width, height;
+	const float* depth;      /* [H,W] D */
+	const float* alpha;      /* [H,W] A, or NULL */
+	const float* prior;      /* [H,W] q */
+	const uint8_t* valid;    /* [H,W] bytes, or NULL */
+	int flags;               /* GSR_DEPTH_PRIOR_* */
+	float alpha_min;
+	float weight;
+	float* grad_depth;       /* [H,W], or NULL together with loss */
+	float* grad_alpha;       /* [H,W]; NULL exactly when alpha is */
+	float* loss;             /* [1] */
+	float* fit;              /* [4] */
+} gsr_depth_prior_args;
+size_t gsr_depth_prior_scratch_bytes(int width, int height);
+int gsr_depth_prior_loss(const gsr_depth_prior_args* args, char* scratch, void* stream);
+/* The prior in the units of the render it was fitted to: out = s q + t, or 1 / (s q + t) with GSR_DEPTH_PRIOR_INVERSE (the flag the
+ * fit was made with), from fit[4] on the device; 0 where q is not finite and positive or the result is not a positive finite float.
+ * out_depth may be prior.  The map gsr_seed_select / gsr_seed_emit take as gt_depth. */
+int gsr_depth_prior_apply(const float* prior, const float* fit, int flags, int width, int height, float* out_depth, void* stream);
+
 /* One torch::optim::Adam step (no amsgrad / weight decay; src/gaussian_model.cpp:477-510 uses eps 1e-15)
  * on a flat fp32 tensor: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
  * p -= (lr / (1-b1^step)) * m / (sqrt(v) / sqrt(1-b2^step) + eps).  The hyper-parameters are double as in

@@ -171,6 +171,14 @@ class SeedEmitArgs(C.Structure):
                 ("out_pixel", C.c_void_p)]
 
 
+class DepthPriorArgs(C.Structure):
+    """gsr_depth_prior_args"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("depth", C.c_void_p), ("alpha", C.c_void_p), ("prior", C.c_void_p),
+                ("valid", C.c_void_p), ("flags", C.c_int), ("alpha_min", C.c_float), ("weight", C.c_float),
+                ("grad_depth", C.c_void_p), ("grad_alpha", C.c_void_p), ("loss", C.c_void_p), ("fit", C.c_void_p)]
+
+
+DEPTH_PRIOR_INVERSE, DEPTH_PRIOR_PEARSON = 1, 2    # GSR_DEPTH_PRIOR_*
 RAW_OPACITY, RAW_SCALING, RAW_ROTATION = 1, 2, 4   # GSR_RAW_* of include/gsr.h
 CULL_EMPTY_TILES, FORWARD_ONLY = 8, 128             # GSR_CULL_EMPTY_TILES, GSR_FORWARD_ONLY
 ANTIALIAS = 256                                     # GSR_ANTIALIAS: forward AND backward (the same value in both calls)
@@ -195,6 +203,7 @@ EXPORTED_SYMBOLS = [
     "gsr_mcmc_scratch_bytes", "gsr_mcmc_relocate", "gsr_mcmc_add_noise",
     "gsr_seed_scratch_bytes", "gsr_seed_select", "gsr_seed_emit",
     "gsr_filter3d_scratch_bytes", "gsr_filter3d_compute",
+    "gsr_depth_prior_scratch_bytes", "gsr_depth_prior_loss", "gsr_depth_prior_apply",
 ]
 
 _libs = {}
@@ -266,6 +275,12 @@ def load(path=None):
     L.gsr_depth_loss_scratch_bytes.argtypes = [i32, i32]
     L.gsr_depth_l1_loss.restype = i32
     L.gsr_depth_l1_loss.argtypes = [vp, vp, i32, i32, f32, f32, f32, vp, vp, vp, vp]
+    L.gsr_depth_prior_scratch_bytes.restype = sz
+    L.gsr_depth_prior_scratch_bytes.argtypes = [i32, i32]
+    L.gsr_depth_prior_loss.restype = i32
+    L.gsr_depth_prior_loss.argtypes = [C.POINTER(DepthPriorArgs), vp, vp]
+    L.gsr_depth_prior_apply.restype = i32
+    L.gsr_depth_prior_apply.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.gsr_adam_step.restype = i32
     f64 = C.c_double
     L.gsr_adam_step.argtypes = [vp, vp, vp, vp, C.c_longlong, f64, f64, f64, f64, i32, i32, i32, f64, vp]

@@ -936,3 +936,326 @@ int gsr_depth_l1_loss(const float* depth, const float* gt_depth, int width, int 
 }
 
 }  // extern "C"
+
+// ---- monocular depth prior (gsr_depth_prior_loss, gsr_depth_prior_apply): a relative-depth map q that is right only up to a scale
+// and a shift, against the rendered quantity r = D / A (or A / D).  Pass 1 leaves six fp64 moment sums per workgroup, pass 2 -- one
+// workgroup -- sums them in index order and solves the fit, pass 3 writes the gradients (and, for the aligned L1, one fp64 partial
+// sum per workgroup), pass 4 -- one workgroup -- sums those.  Fixed grids over a fixed element order, no atomics: the same bits every
+// run.  A thread owns whole groups of four consecutive pixels; the 16-byte and the scalar path differ in how a group is loaded and
+// stored and in nothing else, so they give the same bits.
+namespace gsr {
+constexpr int DP_THREADS = 256;
+constexpr int DP_MAX_BLOCKS = 1024;
+constexpr int DP_MOMENTS = 6;   // n, sum q, sum r, sum qq, sum qr, sum rr
+// coefficients pass 2 leaves for pass 3 and 4 (fp64, in scratch)
+enum { DP_S = 0, DP_T, DP_QM, DP_RM, DP_CA, DP_CB, DP_OK, DP_COEFS = 8 };
+static inline int depth_prior_blocks(size_t n)
+{
+	const size_t groups = (n + 3) / 4, b = (groups + DP_THREADS - 1) / DP_THREADS;
+	return (int)(b < (size_t)DP_MAX_BLOCKS ? b : (size_t)DP_MAX_BLOCKS);
+}
+
+struct DepthPriorParams {
+	const float* depth;
+	const float* alpha;      // or null: all ones
+	const float* prior;
+	const uint8_t* valid;    // or null: all set
+	size_t n;                // H W
+	int vec;                 // every pointer 16-byte aligned: groups move as 16-byte vectors
+	int inverse, pearson;
+	float alpha_min;
+	double weight;
+	float* grad_depth;
+	float* grad_alpha;       // null exactly when alpha is
+	float* loss;             // or null (with grad_depth): the fit only
+	float* fit;              // [4]
+	double* partial;         // [nblocks][DP_MOMENTS]
+	double* coef;            // [DP_COEFS]
+	double* lpartial;        // [nblocks]
+	int nblocks;
+};
+
+// group g = pixels 4 g .. 4 g + 3 (the last group may be short: its missing pixels come back with v = 0)
+__device__ __forceinline__ void depth_prior_load4(const DepthPriorParams& p, size_t g, float (&D)[4], float (&A)[4], float (&q)[4],
+                                                  unsigned (&v)[4])
+{
+	const size_t i = 4 * g;
+	if (p.vec && i + 3 < p.n) {
+		const float4 d4 = *reinterpret_cast<const float4*>(p.depth + i), q4 = *reinterpret_cast<const float4*>(p.prior + i);
+		D[0] = d4.x; D[1] = d4.y; D[2] = d4.z; D[3] = d4.w;
+		q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+		if (p.alpha) {
+			const float4 a4 = *reinterpret_cast<const float4*>(p.alpha + i);
+			A[0] = a4.x; A[1] = a4.y; A[2] = a4.z; A[3] = a4.w;
+		} else {
+			A[0] = A[1] = A[2] = A[3] = 1.f;
+		}
+		const uint32_t m = p.valid ? *reinterpret_cast<const uint32_t*>(p.valid + i) : 0x01010101u;
+		v[0] = m & 0xffu; v[1] = (m >> 8) & 0xffu; v[2] = (m >> 16) & 0xffu; v[3] = m >> 24;
+	} else {
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const bool in = i + k < p.n;
+			D[k] = in ? p.depth[i + k] : 0.f;
+			q[k] = in ? p.prior[i + k] : 0.f;
+			A[k] = in && p.alpha ? p.alpha[i + k] : 1.f;
+			v[k] = in ? (p.valid ? (unsigned)p.valid[i + k] : 1u) : 0u;
+		}
+	}
+}
+
+// The validity rule and the rendered quantity of one pixel (r in fp64 from the fp32 maps).  Every comparison is false for a NaN.  A
+// pixel whose r is not a positive finite float (alpha 0 under an alpha_min <= 0, a depth of +Inf) is left out like an invalid one:
+// nothing that is not finite enters a sum.
+__device__ __forceinline__ bool depth_prior_pixel(float D, float A, float q, unsigned v, float alpha_min, int inverse, double& r)
+{
+	const bool ok = A >= alpha_min && D > 0.f && q > 0.f && q <= 3.4028234663852886e38f && v != 0u;
+	const double num = inverse ? (double)A : (double)D, den = inverse ? (double)D : (double)A;
+	r = ok ? num / den : 0.0;
+	const bool fin = r > 0.0 && r <= 3.4028234663852886e38;
+	if (!fin) r = 0.0;
+	return ok && fin;
+}
+
+__device__ __forceinline__ void depth_prior_accumulate(double (&m)[DP_MOMENTS], double q, double r)
+{
+#pragma clang fp contract(off)
+	m[0] += 1.0;
+	m[1] += q;
+	m[2] += r;
+	m[3] += q * q;
+	m[4] += q * r;
+	m[5] += r * r;
+}
+
+// K sums over the workgroup in a fixed tree, valid in every thread (fp64 has no DPP form here: through LDS)
+template <int K>
+__device__ __forceinline__ void block_sum_f64(double (&v)[K], double* s /*[K][DP_THREADS]*/)
+{
+	const int tid = (int)threadIdx.x;
+	__syncthreads();   // s reuse across calls
+#pragma unroll
+	for (int k = 0; k < K; k++) s[k * DP_THREADS + tid] = v[k];
+	__syncthreads();
+	for (int off = DP_THREADS / 2; off > 0; off >>= 1) {
+		if (tid < off) {
+#pragma unroll
+			for (int k = 0; k < K; k++) s[k * DP_THREADS + tid] += s[k * DP_THREADS + tid + off];
+		}
+		__syncthreads();
+	}
+#pragma unroll
+	for (int k = 0; k < K; k++) v[k] = s[k * DP_THREADS];
+}
+
+__global__ void __launch_bounds__(DP_THREADS)
+depth_prior_moments_kernel(const DepthPriorParams p)
+{
+	__shared__ double s_red[DP_MOMENTS * DP_THREADS];
+	double m[DP_MOMENTS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+	const size_t groups = (p.n + 3) / 4, stride = (size_t)gridDim.x * DP_THREADS;
+	for (size_t g = (size_t)blockIdx.x * DP_THREADS + threadIdx.x; g < groups; g += stride) {
+		float D[4], A[4], q[4];
+		unsigned v[4];
+		depth_prior_load4(p, g, D, A, q, v);
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			double r;
+			if (depth_prior_pixel(D[k], A[k], q[k], v[k], p.alpha_min, p.inverse, r)) depth_prior_accumulate(m, (double)q[k], r);
+		}
+	}
+	block_sum_f64<DP_MOMENTS>(m, s_red);
+	if (threadIdx.x == 0) {
+#pragma unroll
+		for (int k = 0; k < DP_MOMENTS; k++) p.partial[(size_t)blockIdx.x * DP_MOMENTS + k] = m[k];
+	}
+}
+
+// One workgroup: the moments from the partial sums in index order, the closed-form fit, rho and the degenerate rule.
+__global__ void __launch_bounds__(DP_THREADS)
+depth_prior_fit_kernel(const DepthPriorParams p)
+{
+	__shared__ double s_red[DP_MOMENTS * DP_THREADS];
+	double m[DP_MOMENTS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+	for (int i = (int)threadIdx.x; i < p.nblocks; i += DP_THREADS)
+#pragma unroll
+		for (int k = 0; k < DP_MOMENTS; k++) m[k] += p.partial[(size_t)i * DP_MOMENTS + k];
+	block_sum_f64<DP_MOMENTS>(m, s_red);
+	if (threadIdx.x != 0) return;
+	const double n = m[0];
+	double s = 0.0, t = 0.0, rho = 0.0, qm = 0.0, rm = 0.0, ca = 0.0, cb = 0.0;
+	bool ok = false;
+	if (n >= 2.0) {
+		qm = m[1] / n;
+		rm = m[2] / n;
+		const double sqq = m[3] - m[1] * qm, sqr = m[4] - m[1] * rm, srr = m[5] - m[2] * rm;
+		const bool q_ok = sqq > 1e-12 * m[3], r_ok = srr > 1e-12 * m[5];
+		if (q_ok && r_ok) {
+			rho = sqr / sqrt(sqq * srr);
+			rho = rho > 1.0 ? 1.0 : (rho < -1.0 ? -1.0 : rho);
+			ca = 1.0 / sqrt(sqq * srr);   // 1 / (S_q S_r)
+			cb = rho / srr;               // rho / S_r^2
+		}
+		ok = p.pearson ? (q_ok && r_ok) : q_ok;
+		if (ok) {
+			s = sqr / sqq;
+			t = rm - s * qm;
+		} else {
+			rho = 0.0;
+		}
+	}
+	p.fit[0] = (float)s; p.fit[1] = (float)t; p.fit[2] = (float)rho; p.fit[3] = (float)n;
+	p.coef[DP_S] = s; p.coef[DP_T] = t; p.coef[DP_QM] = qm; p.coef[DP_RM] = rm; p.coef[DP_CA] = ca; p.coef[DP_CB] = cb;
+	p.coef[DP_OK] = ok ? 1.0 : 0.0;
+	if (p.loss && p.pearson) p.loss[0] = ok ? (float)(p.weight * (1.0 - rho)) : 0.f;
+}
+
+// one pixel's dloss/dr, and for the aligned L1 its |residual|
+__device__ __forceinline__ double depth_prior_dr(const DepthPriorParams& p, const double (&c)[DP_COEFS], double wl, double q, double r,
+                                                 double& abs_res)
+{
+#pragma clang fp contract(off)
+	if (p.pearson) return -p.weight * ((q - c[DP_QM]) * c[DP_CA] - c[DP_CB] * (r - c[DP_RM]));
+	const double res = r - (c[DP_S] * q + c[DP_T]);
+	abs_res += fabs(res);
+	return res > 0.0 ? wl : (res < 0.0 ? -wl : 0.0);
+}
+__device__ __forceinline__ float depth_prior_finite(double g)
+{
+	const float f = (float)g;
+	return f >= -3.4028234663852886e38f && f <= 3.4028234663852886e38f ? f : 0.f;
+}
+
+__global__ void __launch_bounds__(DP_THREADS)
+depth_prior_grad_kernel(const DepthPriorParams p)
+{
+	__shared__ double s_red[DP_THREADS];
+	double c[DP_COEFS];
+#pragma unroll
+	for (int k = 0; k < DP_COEFS; k++) c[k] = p.coef[k];
+	const bool ok = c[DP_OK] != 0.0;
+	const double wl = p.weight / (double)p.n;
+	double acc[1] = {0.0};
+	const size_t groups = (p.n + 3) / 4, stride = (size_t)gridDim.x * DP_THREADS;
+	for (size_t g = (size_t)blockIdx.x * DP_THREADS + threadIdx.x; g < groups; g += stride) {
+		float D[4], A[4], q[4], gd[4], ga[4];
+		unsigned v[4];
+		depth_prior_load4(p, g, D, A, q, v);
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			double r;
+			gd[k] = 0.f;
+			ga[k] = 0.f;
+			if (depth_prior_pixel(D[k], A[k], q[k], v[k], p.alpha_min, p.inverse, r) && ok) {
+				const double dr = depth_prior_dr(p, c, wl, (double)q[k], r, acc[0]);
+				// default: dr/dD = 1/A, dr/dA = -D/A^2 = -r/A;  inverse: dr/dD = -A/D^2 = -r/D, dr/dA = 1/D
+				const double den = p.inverse ? (double)D[k] : (double)A[k];
+				const double direct = dr / den, cross = -(dr * r) / den;
+				gd[k] = depth_prior_finite(p.inverse ? cross : direct);
+				ga[k] = depth_prior_finite(p.inverse ? direct : cross);
+			}
+		}
+		const size_t i = 4 * g;
+		if (p.vec && i + 3 < p.n) {
+			*reinterpret_cast<float4*>(p.grad_depth + i) = make_float4(gd[0], gd[1], gd[2], gd[3]);
+			if (p.grad_alpha) *reinterpret_cast<float4*>(p.grad_alpha + i) = make_float4(ga[0], ga[1], ga[2], ga[3]);
+		} else {
+#pragma unroll
+			for (int k = 0; k < 4; k++)
+				if (i + k < p.n) {
+					p.grad_depth[i + k] = gd[k];
+					if (p.grad_alpha) p.grad_alpha[i + k] = ga[k];
+				}
+		}
+	}
+	if (p.pearson) return;   // (workgroup-uniform) its loss left pass 2
+	block_sum_f64<1>(acc, s_red);
+	if (threadIdx.x == 0) p.lpartial[blockIdx.x] = acc[0];
+}
+
+__global__ void __launch_bounds__(DP_THREADS)
+depth_prior_final_kernel(const DepthPriorParams p)
+{
+	__shared__ double s_red[DP_THREADS];
+	double a[1] = {0.0};
+	for (int i = (int)threadIdx.x; i < p.nblocks; i += DP_THREADS) a[0] += p.lpartial[i];
+	block_sum_f64<1>(a, s_red);
+	if (threadIdx.x == 0) p.loss[0] = depth_prior_finite(a[0] * (p.weight / (double)p.n));
+}
+
+// gsr_depth_prior_apply: the fitted map, 0 where the prior is invalid or the result is not a positive finite float; out may be prior
+__global__ void __launch_bounds__(DP_THREADS)
+depth_prior_apply_kernel(const float* prior, const float* __restrict__ fit, int inverse, size_t n, float* out)
+{
+	const double s = (double)fit[0], t = (double)fit[1];
+	const size_t stride = (size_t)gridDim.x * DP_THREADS;
+	for (size_t i = (size_t)blockIdx.x * DP_THREADS + threadIdx.x; i < n; i += stride) {
+		const float q = prior[i];
+		float o = 0.f;
+		if (q > 0.f && q <= 3.4028234663852886e38f) {
+			double m = s * (double)q + t;
+			if (inverse) m = m > 0.0 ? 1.0 / m : 0.0;
+			const float f = (float)m;
+			if (f > 0.f && f <= 3.4028234663852886e38f) o = f;
+		}
+		out[i] = o;
+	}
+}
+}  // namespace gsr
+extern "C" {
+
+size_t gsr_depth_prior_scratch_bytes(int width, int height)
+{
+	if (width <= 0 || height <= 0) return 0;
+	const size_t nb = (size_t)depth_prior_blocks((size_t)width * height);
+	return (nb * (DP_MOMENTS + 1) + DP_COEFS) * sizeof(double);
+}
+
+int gsr_depth_prior_loss(const gsr_depth_prior_args* a, char* scratch, void* stream_)
+{
+	if (!a || !scratch || (reinterpret_cast<uintptr_t>(scratch) & 7) || !a->depth || !a->prior || !a->fit || a->width <= 0 ||
+	    a->height <= 0)
+		return GSR_ERR_INVALID_ARG;
+	if (a->flags & ~(GSR_DEPTH_PRIOR_INVERSE | GSR_DEPTH_PRIOR_PEARSON)) return GSR_ERR_INVALID_ARG;
+	const bool grads = a->grad_depth != nullptr;
+	if (grads != (a->loss != nullptr)) return GSR_ERR_INVALID_ARG;   // both or neither (neither: the fit only)
+	if (grads ? (a->grad_alpha != nullptr) != (a->alpha != nullptr) : a->grad_alpha != nullptr) return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	DepthPriorParams p;
+	p.depth = a->depth; p.alpha = a->alpha; p.prior = a->prior; p.valid = a->valid;
+	p.n = (size_t)a->width * a->height;
+	p.vec = !((reinterpret_cast<uintptr_t>(a->depth) | reinterpret_cast<uintptr_t>(a->alpha) | reinterpret_cast<uintptr_t>(a->prior) |
+	           reinterpret_cast<uintptr_t>(a->valid) | reinterpret_cast<uintptr_t>(a->grad_depth) |
+	           reinterpret_cast<uintptr_t>(a->grad_alpha)) & 15);
+	p.inverse = (a->flags & GSR_DEPTH_PRIOR_INVERSE) ? 1 : 0;
+	p.pearson = (a->flags & GSR_DEPTH_PRIOR_PEARSON) ? 1 : 0;
+	p.alpha_min = a->alpha_min;
+	p.weight = (double)a->weight;
+	p.grad_depth = a->grad_depth; p.grad_alpha = a->grad_alpha; p.loss = a->loss; p.fit = a->fit;
+	p.nblocks = depth_prior_blocks(p.n);
+	p.partial = reinterpret_cast<double*>(scratch);
+	p.coef = p.partial + (size_t)p.nblocks * DP_MOMENTS;
+	p.lpartial = p.coef + DP_COEFS;
+	GSR_LAUNCH(depth_prior_moments_kernel, p.nblocks, DP_THREADS, stream, p);
+	GSR_LAUNCH(depth_prior_fit_kernel, 1, DP_THREADS, stream, p);
+	if (grads) {
+		GSR_LAUNCH(depth_prior_grad_kernel, p.nblocks, DP_THREADS, stream, p);
+		if (!p.pearson) GSR_LAUNCH(depth_prior_final_kernel, 1, DP_THREADS, stream, p);
+	}
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+int gsr_depth_prior_apply(const float* prior, const float* fit, int flags, int width, int height, float* out_depth, void* stream_)
+{
+	if (!prior || !fit || !out_depth || width <= 0 || height <= 0 || (flags & ~(GSR_DEPTH_PRIOR_INVERSE | GSR_DEPTH_PRIOR_PEARSON)))
+		return GSR_ERR_INVALID_ARG;
+	hipStream_t stream = (hipStream_t)stream_;
+	const size_t n = (size_t)width * height;
+	GSR_LAUNCH(depth_prior_apply_kernel, stream_blocks(n), DP_THREADS, stream, prior, fit, (flags & GSR_DEPTH_PRIOR_INVERSE) ? 1 : 0, n,
+	           out_depth);
+	GSR_CHECK_LAUNCH();
+	return GSR_OK;
+}
+
+}  // extern "C"

@@ -296,8 +296,10 @@ public:
 	// ... with the keyframe's [H,W] sensor depth (an RGB-D session's img_auxiliary_undist_): with depth_loss_weight_ != 0 the depth
 	// L1 loss (loss_utils::depth_l1 over depth_min_ < gt < depth_max_) joins the RGB loss before the one backward pass; undefined
 	// gt_depth or weight 0 = the RGB loss alone
+	// prior_depth: a monocular network's relative [H,W] map of the keyframe: with depth_prior_weight_ != 0 the depth-prior term
+	// (loss_utils::depth_prior on the rendered depth AND alpha maps) joins the loss in the same way; both maps may be given
 	torch::Tensor renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
-	                                torch::Tensor gt_depth);
+	                                torch::Tensor gt_depth, torch::Tensor prior_depth = torch::Tensor());
 	void finishOneIteration();
 	// finishOneIteration() in three pieces for the overlapped data-parallel step (bench.py): statistics, then Adam per
 	// group as the reductions complete, then the gradient reset
@@ -317,8 +319,9 @@ public:
 	// gt_depth: an RGB-D keyframe, the depth loss of renderAndBackward (not with a process group: throws when the weight is non-zero)
 	torch::Tensor trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask)
 	{ return trainForOneIteration(kf, gt_image, mask, torch::Tensor()); }
+	// prior_depth: a monocular keyframe, the depth-prior term of renderAndBackward (likewise not with a process group)
 	torch::Tensor trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
-	                                   torch::Tensor gt_depth);
+	                                   torch::Tensor gt_depth, torch::Tensor prior_depth = torch::Tensor());
 	// A viewer / evaluation render of the current model (GaussianMapper::renderFromPose, renderAndRecordKeyframe): forward-only
 	// (GSR_FORWARD_ONLY) into a second workspace of its own -- a view between a training forward and its backward must not
 	// overwrite the buffers that forward saved -- with lazily stepped SH rows read as they are: no flush, no counter advanced,
@@ -361,6 +364,13 @@ public:
 	// Not with a process group: throws.  Nothing calls it by itself.
 	int64_t seedFromDepth(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image, torch::Tensor gt_depth, int iteration,
 	                      bool want_pixels = false);
+	// A monocular network's relative [H,W] map in the units of the map: one forward-only render with its depth and alpha maps
+	// (renderViewWithDepth), the scale-and-shift fit of the depth-prior loss against it (depth_prior_inverse_, depth_prior_alpha_min_;
+	// valid: an optional uint8 / bool [H,W] mask), then gsr_depth_prior_apply.  Returns (the metric [H,W] map -- 0 where the prior is
+	// invalid --, fit = [s, t, rho, n] on the device); the map is what seedFromDepth takes as gt_depth.  A degenerate fit
+	// (include/gsr.h) gives an all-zero map, which seeds nothing.  An empty model has no render to align to: throws.
+	std::tuple<torch::Tensor, torch::Tensor> alignDepthPrior(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor prior,
+	                                                         torch::Tensor valid = torch::Tensor());
 	// THE refusal of the single-process-only features: throws "TrainStep: <what> not supported with a process group<suffix>" (what =
 	// the feature and its verb, "mcmc_ is") with a process group set or -- factored_counts -- with the view-factored exchange on
 	void requireSingleProcess(const char* what, bool factored_counts, const char* suffix = "") const;
@@ -371,6 +381,17 @@ public:
 	float depth_min_ = 0.0f;
 	float depth_max_ = std::numeric_limits<float>::infinity();
 	bool usesDepthLoss(const torch::Tensor& gt_depth) const { return gt_depth.defined() && depth_loss_weight_ != 0.0f; }
+	// Monocular keyframes: depth_prior_weight_ * the depth-prior term (include/gsr.h: gsr_depth_prior_loss) of prior_depth against the
+	// rendered depth and alpha maps: the aligned L1 after a per-frame scale-and-shift fit, or 1 - Pearson correlation with
+	// depth_prior_pearson_; depth_prior_inverse_: the prior is an inverse depth (MiDaS / Depth Anything); pixels with alpha <
+	// depth_prior_alpha_min_ take no part.  0 = off.  lastDepthPriorFit(): [s, t, rho, n] of the last step with the term (device).
+	float depth_prior_weight_ = 0.0f;
+	bool depth_prior_pearson_ = false;
+	bool depth_prior_inverse_ = true;
+	float depth_prior_alpha_min_ = 0.5f;
+	bool usesDepthPrior(const torch::Tensor& prior_depth) const { return prior_depth.defined() && depth_prior_weight_ != 0.0f; }
+	torch::Tensor lastDepthPriorFit() const { return last_depth_prior_fit_; }
+	torch::Tensor last_depth_prior_fit_;
 	// Per-keyframe exposure compensation (upstream 3DGS's per-image exposure): a keyframe that carries exposure_ has it applied
 	// between render and loss, inside the loss kernels, in renderAndBackward and refinePose.  optimize_exposure_: the keyframe of a
 	// train step gets the identity at first use and takes one Adam step on its 12 floats in finishEnd() (gsr_adam_step,
@@ -596,7 +617,7 @@ public:
 	};
 	std::map<const void*, MaskEntry> mask_is_ones_;   // masks seen so far: all ones? (effectiveMask)
 	// the stages of renderAndBackward, in the order it runs them (train_step.cpp); effectiveMask and stepLoss serve refinePose too
-	void checkStepSupported(const std::shared_ptr<GaussianKeyframe>& kf, bool use_depth);
+	void checkStepSupported(const std::shared_ptr<GaussianKeyframe>& kf, bool use_depth, bool use_prior = false);
 	void prepareExchangeBuffers(const std::shared_ptr<GaussianKeyframe>& kf);
 	torch::Tensor planRegularisers(GaussianRasterizationExtensions& ext) const;
 	bool planFeaturesStep(GaussianRasterizationExtensions& ext, bool rebuilds);   // -> the SH rows step lazily

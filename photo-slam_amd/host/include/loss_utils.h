@@ -63,5 +63,20 @@ torch::Tensor apply_exposure(torch::Tensor image, torch::Tensor exposure);
 //   weight * sum over the pixels with min_depth < gt_depth < max_depth of |depth - gt_depth|, divided by H W
 // depth, gt_depth: [H,W] float32 on one device; differentiable in depth.
 torch::Tensor depth_l1(torch::Tensor depth, torch::Tensor gt_depth, float weight, float min_depth, float max_depth);
+// (extension) the monocular depth-prior term of one view (csrc/train_ops.hip, gsr_depth_prior_loss; the semantics: include/gsr.h;
+// deterministic): prior is a network's relative [H,W] map, right up to a scale and a shift, compared with depth / alpha (inverse:
+// alpha / depth) over the pixels with alpha >= alpha_min, depth > 0, a finite positive prior and valid != 0 -- the aligned L1 after a
+// closed-form per-frame fit, divided by H W, or weight * (1 - Pearson correlation) with pearson.  depth, alpha, prior: float32 [H,W] on
+// one device; alpha undefined / empty = all ones; valid: uint8 / bool [H,W] or undefined / empty.  Differentiable in depth and alpha.
+// fit: if given, receives [s, t, rho, n] (device).
+torch::Tensor depth_prior(torch::Tensor depth, torch::Tensor alpha, torch::Tensor prior, float weight, bool inverse = true,
+                          bool pearson = false, float alpha_min = 0.5f, torch::Tensor valid = torch::Tensor(),
+                          torch::Tensor* fit = nullptr);
+// (extension) [s, t, rho, n] of the fit alone (two launches, no gradient)
+torch::Tensor depth_prior_fit(torch::Tensor depth, torch::Tensor alpha, torch::Tensor prior, bool inverse = true, float alpha_min = 0.5f,
+                              torch::Tensor valid = torch::Tensor());
+// (extension) the prior in the units of the render it was fitted to (gsr_depth_prior_apply): s q + t, or 1 / (s q + t) with inverse; 0
+// where the prior is invalid or the result is not finite and positive.  in_place: written over prior (contiguous), which is returned.
+torch::Tensor depth_prior_apply(torch::Tensor prior, torch::Tensor fit, bool inverse = true, bool in_place = false);
 
 }

@@ -114,6 +114,81 @@ public:
 	}
 };
 
+// ---- the monocular depth prior (include/gsr.h: gsr_depth_prior_loss).  An empty tensor stands for "not given" (alpha, valid).
+struct DepthPriorMaps {
+	torch::Tensor d, a, q, v;
+};
+DepthPriorMaps depth_prior_maps(const torch::Tensor& depth, const torch::Tensor& alpha, const torch::Tensor& prior, const torch::Tensor& valid)
+{
+	DepthPriorMaps m;
+	m.d = depth.contiguous();
+	m.q = prior.contiguous();
+	if (m.d.dim() != 2 || m.q.sizes() != m.d.sizes() || m.d.scalar_type() != torch::kFloat32 || m.q.scalar_type() != torch::kFloat32 ||
+	    m.q.device() != m.d.device())
+		throw std::runtime_error("depth_prior: depth and prior must be float32 [H, W] tensors of the same shape on one device");
+	if (alpha.defined() && alpha.numel()) {
+		m.a = alpha.contiguous();
+		if (m.a.sizes() != m.d.sizes() || m.a.scalar_type() != torch::kFloat32 || m.a.device() != m.d.device())
+			throw std::runtime_error("depth_prior: alpha must be a float32 [H, W] tensor like depth");
+	}
+	if (valid.defined() && valid.numel()) {
+		m.v = valid.contiguous();
+		if (m.v.scalar_type() == torch::kBool) m.v = m.v.view(torch::kByte);
+		if (m.v.sizes() != m.d.sizes() || m.v.scalar_type() != torch::kByte || m.v.device() != m.d.device())
+			throw std::runtime_error("depth_prior: valid must be a uint8 or bool [H, W] tensor on the device of depth");
+	}
+	return m;
+}
+int depth_prior_flags(bool inverse, bool pearson) { return (inverse ? GSR_DEPTH_PRIOR_INVERSE : 0) | (pearson ? GSR_DEPTH_PRIOR_PEARSON : 0); }
+
+// {loss [1], grad_depth, grad_alpha, fit [4]}; with_grads false: the fit alone (the others undefined)
+std::vector<torch::Tensor> depth_prior_call(const DepthPriorMaps& m, float weight, int flags, float alpha_min, bool with_grads)
+{
+	const int H = static_cast<int>(m.d.size(0)), W = static_cast<int>(m.d.size(1));
+	torch::Tensor loss, grad_d, grad_a;
+	auto fit = torch::empty({4}, m.d.options());
+	if (with_grads) {
+		loss = torch::empty({1}, m.d.options());
+		grad_d = torch::empty_like(m.d);
+		if (m.a.defined()) grad_a = torch::empty_like(m.d);
+	}
+	auto scratch = torch::empty({static_cast<int64_t>(gsr_depth_prior_scratch_bytes(W, H))}, m.d.options().dtype(torch::kByte));
+	gsr_depth_prior_args a{};
+	a.width = W; a.height = H;
+	a.depth = m.d.data_ptr<float>();
+	a.alpha = m.a.defined() ? m.a.data_ptr<float>() : nullptr;
+	a.prior = m.q.data_ptr<float>();
+	a.valid = m.v.defined() ? m.v.data_ptr<uint8_t>() : nullptr;
+	a.flags = flags; a.alpha_min = alpha_min; a.weight = weight;
+	a.grad_depth = grad_d.defined() ? grad_d.data_ptr<float>() : nullptr;
+	a.grad_alpha = grad_a.defined() ? grad_a.data_ptr<float>() : nullptr;
+	a.loss = loss.defined() ? loss.data_ptr<float>() : nullptr;
+	a.fit = fit.data_ptr<float>();
+	check(gsr_depth_prior_loss(&a, reinterpret_cast<char*>(scratch.data_ptr()), stream_of(m.d)), "gsr_depth_prior_loss");
+	return {loss, grad_d, grad_a, fit};
+}
+
+class DepthPriorFunction : public torch::autograd::Function<DepthPriorFunction> {
+public:
+	static torch::autograd::tensor_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth, torch::Tensor alpha,
+	                                            torch::Tensor prior, double weight, int64_t flags, double alpha_min, torch::Tensor valid)
+	{
+		const auto m = depth_prior_maps(depth, alpha, prior, valid);
+		auto r = depth_prior_call(m, static_cast<float>(weight), static_cast<int>(flags), static_cast<float>(alpha_min), true);
+		ctx->saved_data["has_alpha"] = m.a.defined();
+		if (m.a.defined()) ctx->save_for_backward({r[1], r[2]});
+		else ctx->save_for_backward({r[1]});
+		ctx->mark_non_differentiable({r[3]});
+		return {r[0][0], r[3]};
+	}
+	static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::tensor_list go)
+	{
+		auto saved = ctx->get_saved_variables();
+		const torch::Tensor none;
+		return {saved[0] * go[0], ctx->saved_data["has_alpha"].toBool() ? saved[1] * go[0] : none, none, none, none, none, none};
+	}
+};
+
 // what the kernels cover: one float32 [3,H,W] (or [1,3,H,W]) image pair on one device, the target without a gradient
 bool fused_applies(const torch::Tensor& a, const torch::Tensor& b)
 {
@@ -164,6 +239,38 @@ torch::Tensor depth_l1(torch::Tensor depth, torch::Tensor gt_depth, float weight
 {
 	return DepthL1Function::apply(depth, gt_depth, static_cast<double>(weight), static_cast<double>(min_depth),
 	                              static_cast<double>(max_depth));
+}
+
+torch::Tensor depth_prior(torch::Tensor depth, torch::Tensor alpha, torch::Tensor prior, float weight, bool inverse, bool pearson,
+                          float alpha_min, torch::Tensor valid, torch::Tensor* fit)
+{
+	if (!alpha.defined()) alpha = torch::empty({0}, depth.options());   // (autograd::Function::apply needs every tensor argument defined)
+	if (!valid.defined()) valid = torch::empty({0}, depth.options().dtype(torch::kByte));
+	auto out = DepthPriorFunction::apply(depth, alpha, prior, static_cast<double>(weight),
+	                                     static_cast<int64_t>(depth_prior_flags(inverse, pearson)), static_cast<double>(alpha_min), valid);
+	if (fit) *fit = out[1];
+	return out[0];
+}
+
+torch::Tensor depth_prior_fit(torch::Tensor depth, torch::Tensor alpha, torch::Tensor prior, bool inverse, float alpha_min,
+                              torch::Tensor valid)
+{
+	const auto m = depth_prior_maps(depth.detach(), alpha.defined() ? alpha.detach() : alpha, prior.detach(), valid);
+	return depth_prior_call(m, 0.0f, depth_prior_flags(inverse, false), alpha_min, false)[3];
+}
+
+torch::Tensor depth_prior_apply(torch::Tensor prior, torch::Tensor fit, bool inverse, bool in_place)
+{
+	if (prior.dim() != 2 || prior.scalar_type() != torch::kFloat32 || fit.numel() != 4 || fit.scalar_type() != torch::kFloat32 ||
+	    prior.device() != fit.device())
+		throw std::runtime_error("depth_prior_apply: a float32 [H, W] prior and a float32 [4] fit on one device");
+	if (in_place && !prior.is_contiguous()) throw std::runtime_error("depth_prior_apply: in place needs a contiguous prior");
+	auto q = prior.detach().contiguous(), f = fit.detach().contiguous();
+	auto out = in_place ? q : torch::empty_like(q);
+	check(gsr_depth_prior_apply(q.data_ptr<float>(), f.data_ptr<float>(), depth_prior_flags(inverse, false), static_cast<int>(q.size(1)),
+	                            static_cast<int>(q.size(0)), out.data_ptr<float>(), stream_of(q)),
+	      "gsr_depth_prior_apply");
+	return out;
 }
 
 torch::Tensor l1_loss(torch::Tensor &network_output, torch::Tensor &gt)

@@ -126,6 +126,22 @@ torch::Tensor l1_ssim_loss_exposure(torch::Tensor rendered, torch::Tensor gt, to
 	return loss_utils::fused_l1_ssim_exposure(rendered, gt, mask, (float)lambda_dssim, exposure, is_root);
 }
 torch::Tensor apply_exposure(torch::Tensor image, torch::Tensor exposure) { return loss_utils::apply_exposure(image, exposure); }
+// loss_utils::depth_prior and its companions (alpha, valid with no elements = not given): (loss, fit [4])
+std::tuple<torch::Tensor, torch::Tensor> depth_prior_loss(torch::Tensor depth, torch::Tensor alpha, torch::Tensor prior, double weight,
+                                                          bool inverse, bool pearson, double alpha_min, torch::Tensor valid)
+{
+	torch::Tensor fit;
+	auto loss = loss_utils::depth_prior(depth, alpha, prior, (float)weight, inverse, pearson, (float)alpha_min, valid, &fit);
+	return std::make_tuple(loss, fit);
+}
+torch::Tensor depth_prior_fit(torch::Tensor depth, torch::Tensor alpha, torch::Tensor prior, bool inverse, double alpha_min, torch::Tensor valid)
+{
+	return loss_utils::depth_prior_fit(depth, alpha, prior, inverse, (float)alpha_min, valid);
+}
+torch::Tensor depth_prior_apply(torch::Tensor prior, torch::Tensor fit, bool inverse, bool in_place)
+{
+	return loss_utils::depth_prior_apply(prior, fit, inverse, in_place);
+}
 
 torch::Tensor transform_points(torch::Tensor points, torch::Tensor transformmatrix)
 {
@@ -227,6 +243,26 @@ torch::Tensor trainer_render_and_backward_depth(int64_t h, torch::Tensor view, t
                                                 torch::Tensor gt_depth)
 {
 	return get(h)->renderAndBackward(make_kf(view, proj, campos, fovx, fovy, H, W), gt, mask, gt_depth).detach();
+}
+// TrainStep::trainForOneIteration with a sensor depth and / or a monocular prior (no elements = not given)
+torch::Tensor trainer_train_depth_prior(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos, double fovx, double fovy,
+                                        int64_t H, int64_t W, torch::Tensor gt, torch::Tensor mask, torch::Tensor gt_depth,
+                                        torch::Tensor prior_depth)
+{
+	return get(h)->trainForOneIteration(make_kf(view, proj, campos, fovx, fovy, H, W), gt, mask, gt_depth.numel() ? gt_depth : torch::Tensor(),
+	                                    prior_depth.numel() ? prior_depth : torch::Tensor()).detach();
+}
+// TrainStep::lastDepthPriorFit: [s, t, rho, n] of the last step with the depth-prior term, or an empty tensor
+torch::Tensor trainer_last_depth_prior_fit(int64_t h)
+{
+	auto t = get(h);
+	return or_empty(t->lastDepthPriorFit(), t->gaussians_->xyz_);
+}
+// TrainStep::alignDepthPrior: (the metric map, fit)
+std::tuple<torch::Tensor, torch::Tensor> trainer_align_depth_prior(int64_t h, torch::Tensor view, torch::Tensor proj, torch::Tensor campos,
+                                                                   double fovx, double fovy, int64_t H, int64_t W, torch::Tensor prior)
+{
+	return get(h)->alignDepthPrior(make_kf(view, proj, campos, fovx, fovy, H, W), prior);
 }
 // TrainStep::lastAbsgrad: the [P,2] absolute screen-space gradients of the last step that formed them, or an empty tensor
 torch::Tensor trainer_last_absgrad(int64_t h)
@@ -443,6 +479,10 @@ void trainer_set_options(int64_t h, c10::Dict<std::string, double> o)
 		else if (k == "depth_loss_weight") t->depth_loss_weight_ = static_cast<float>(v);
 		else if (k == "depth_min") t->depth_min_ = static_cast<float>(v);
 		else if (k == "depth_max") t->depth_max_ = static_cast<float>(v);
+		else if (k == "depth_prior_weight") t->depth_prior_weight_ = static_cast<float>(v);
+		else if (k == "depth_prior_pearson") t->depth_prior_pearson_ = v != 0.0;
+		else if (k == "depth_prior_inverse") t->depth_prior_inverse_ = v != 0.0;
+		else if (k == "depth_prior_alpha_min") t->depth_prior_alpha_min_ = static_cast<float>(v);
 		else if (k == "persistent_workspace") t->persistent_workspace_ = v != 0.0;
 		else if (k == "early_gather") t->early_gather_ = v != 0.0;
 		else if (k == "packed_exchange") t->packed_exchange_ = v != 0.0;
@@ -739,6 +779,12 @@ TORCH_LIBRARY(photoslam_amd, m)
 	m.def("l1_ssim_loss", &l1_ssim_loss);
 	m.def("l1_ssim_loss_exposure", &l1_ssim_loss_exposure);
 	m.def("apply_exposure", &apply_exposure);
+	m.def("depth_prior_loss", &depth_prior_loss);
+	m.def("depth_prior_fit", &depth_prior_fit);
+	m.def("depth_prior_apply", &depth_prior_apply);
+	m.def("trainer_train_depth_prior", &trainer_train_depth_prior);
+	m.def("trainer_last_depth_prior_fit", &trainer_last_depth_prior_fit);
+	m.def("trainer_align_depth_prior", &trainer_align_depth_prior);
 	m.def("trainer_train_exposure", &trainer_train_exposure);
 	m.def("trainer_render_view_exposure", &trainer_render_view_exposure);
 	m.def("trainer_refine_pose_exposure", &trainer_refine_pose_exposure);

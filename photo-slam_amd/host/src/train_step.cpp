@@ -276,14 +276,15 @@ GaussianRasterizationExtensions TrainStep::viewExtensions()
 }
 
 torch::Tensor TrainStep::trainForOneIteration(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
-                                              torch::Tensor gt_depth)
+                                              torch::Tensor gt_depth, torch::Tensor prior_depth)
 {
 	if (process_group_) {
 		if (usesDepthLoss(gt_depth)) requireSingleProcess("the depth loss is", false, " (depth_loss_weight_ must be 0)");
+		if (usesDepthPrior(prior_depth)) requireSingleProcess("the depth prior is", false, " (depth_prior_weight_ must be 0)");
 		if (kf->exposure_.defined() || optimize_exposure_) requireSingleProcess("exposure compensation is", false);
 		return trainForOneIterationDataParallel(kf, gt_image, mask);
 	}
-	auto loss = renderAndBackward(kf, gt_image, mask, gt_depth);
+	auto loss = renderAndBackward(kf, gt_image, mask, gt_depth, prior_depth);
 	finishOneIteration();
 	return loss;
 }
@@ -413,6 +414,18 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> TrainStep::renderViewWit
 	return std::make_tuple(std::get<0>(pkg), std::get<4>(pkg), std::get<5>(pkg));
 }
 
+std::tuple<torch::Tensor, torch::Tensor> TrainStep::alignDepthPrior(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor prior,
+                                                                    torch::Tensor valid)
+{
+	if (!gaussians_->xyz_.defined() || gaussians_->xyz_.size(0) == 0)
+		throw std::runtime_error("TrainStep: alignDepthPrior needs a render to align to, and the model is empty "
+		                         "(seed the first frame from a metric depth map)");
+	torch::NoGradGuard no_grad;
+	auto maps = renderViewWithDepth(viewpoint_cam);
+	auto fit = loss_utils::depth_prior_fit(std::get<1>(maps), std::get<2>(maps), prior, depth_prior_inverse_, depth_prior_alpha_min_, valid);
+	return std::make_tuple(loss_utils::depth_prior_apply(prior, fit, depth_prior_inverse_), fit);
+}
+
 int64_t TrainStep::seedFromDepth(std::shared_ptr<GaussianKeyframe> viewpoint_cam, torch::Tensor gt_image, torch::Tensor gt_depth,
                                  int iteration, bool want_pixels)
 {
@@ -518,9 +531,10 @@ std::tuple<torch::Tensor, torch::Tensor> TrainStep::refinePose(std::shared_ptr<G
 // ---- the stages of renderAndBackward, in the order it runs them
 // Every refusal of a step, before anything of it happens (iteration_ has not advanced); what the last step left for its readers (the
 // pending exposure step, lastRegLosses(), lastAbsgrad()) is dropped at the points it always was: a refused call leaves the same state
-void TrainStep::checkStepSupported(const std::shared_ptr<GaussianKeyframe>& kf, bool use_depth)
+void TrainStep::checkStepSupported(const std::shared_ptr<GaussianKeyframe>& kf, bool use_depth, bool use_prior)
 {
 	if (use_depth) requireSingleProcess("the depth loss is", false, " (depth_loss_weight_ must be 0)");
+	if (use_prior) requireSingleProcess("the depth prior is", false, " (depth_prior_weight_ must be 0)");
 	exposure_kf_.reset();
 	exposure_grad_ = torch::Tensor();
 	if (kf->exposure_.defined() || optimize_exposure_) requireSingleProcess("exposure compensation is", false);
@@ -530,6 +544,7 @@ void TrainStep::checkStepSupported(const std::shared_ptr<GaussianKeyframe>& kf, 
 	checkFilter3D();   // (refuses a process group and a missing camera list)
 	last_reg_losses_ = torch::Tensor();
 	last_absgrad_ = torch::Tensor();
+	last_depth_prior_fit_ = torch::Tensor();
 	if (optimize_exposure_ && !kf->exposure_.defined())   // the identity at first use (created before the check it always passes)
 		kf->exposure_ = torch::eye(3, 4, gaussians_->xyz_.options().requires_grad(false));
 	if (kf->exposure_.defined() && (kf->exposure_.dim() != 2 || kf->exposure_.size(0) != 3 || kf->exposure_.size(1) != 4 ||
@@ -715,10 +730,10 @@ torch::Tensor TrainStep::stepLoss(const torch::Tensor& rendered, const torch::Te
 }
 
 torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf, torch::Tensor gt_image, torch::Tensor mask,
-                                           torch::Tensor gt_depth)
+                                           torch::Tensor gt_depth, torch::Tensor prior_depth)
 {
-	const bool use_depth = usesDepthLoss(gt_depth);
-	checkStepSupported(kf, use_depth);
+	const bool use_depth = usesDepthLoss(gt_depth), use_prior = usesDepthPrior(prior_depth);
+	checkStepSupported(kf, use_depth, use_prior);
 	auto& g = gaussians_;
 	iteration_++;
 	// the position learning rate follows the iteration (src/gaussian_mapper.cpp:672-674) or -- a SLAM session -- the number of
@@ -740,7 +755,7 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	{
 		g->in_lazy_step_ = lazy;
 		ScopeExit clear{[&] { g->in_lazy_step_ = false; }};   // (on every way out of the render)
-		pkg = renderModel(*this, kf, g, ext, use_depth);
+		pkg = renderModel(*this, kf, g, ext, use_depth || use_prior);
 	}
 	if (factored_exchange_ && packed_this_step_) beginCountExchange();   // (the forward pass has left this view's visible count)
 	if (prepacked_this_step_) planPackedView(std::get<3>(pkg));
@@ -751,6 +766,9 @@ torch::Tensor TrainStep::renderAndBackward(std::shared_ptr<GaussianKeyframe> kf,
 	torch::Tensor exposure_leaf;   // (a leaf of this step's graph: the keyframe's tensor itself is stepped in place afterwards)
 	if (kf->exposure_.defined()) exposure_leaf = kf->exposure_.detach().set_requires_grad(optimize_exposure_);
 	auto loss = stepLoss(std::get<0>(pkg), std::get<4>(pkg), exposure_leaf, gt_image, eff_mask, gt_depth, use_depth);
+	if (use_prior)   // (not in stepLoss: refinePose shares that and takes no prior)
+		loss = loss + loss_utils::depth_prior(std::get<4>(pkg), std::get<5>(pkg), prior_depth, depth_prior_weight_, depth_prior_inverse_,
+		                                      depth_prior_pearson_, depth_prior_alpha_min_, torch::Tensor(), &last_depth_prior_fit_);
 	// the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward()
 	if (!root_grad_.defined() || root_grad_.device() != loss.device()) root_grad_ = torch::ones_like(loss).detach();
 	loss.backward(root_grad_);

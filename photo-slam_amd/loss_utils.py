@@ -182,3 +182,101 @@ def depth_l1_loss(depth, gt_depth, weight, min_depth, max_depth):
     """weight * sum over the pixels with min_depth < gt_depth < max_depth of |depth - gt_depth|, divided by H W (a scalar
     tensor; differentiable in depth)"""
     return _DepthL1.apply(depth, gt_depth, weight, min_depth, max_depth)
+
+
+# Monocular depth prior (csrc/train_ops.hip, gsr_depth_prior_loss; the semantics: include/gsr.h): a relative-depth map that is right
+# up to a scale and a shift against r = depth / alpha (inverse: alpha / depth) -- the aligned L1 after a closed-form per-frame fit,
+# or 1 - Pearson correlation -- with its gradients w.r.t. the rendered depth and alpha maps, deterministic, nothing read on the host.
+def _depth_prior_flags(inverse, pearson):
+    from . import capi
+    return (capi.DEPTH_PRIOR_INVERSE if inverse else 0) | (capi.DEPTH_PRIOR_PEARSON if pearson else 0)
+
+
+def _depth_prior_maps(lib, depth, alpha, prior, valid):
+    _rp._check_device(lib, depth, prior)
+    d = depth.contiguous().float()
+    q = prior.contiguous().float()
+    if d.dim() != 2 or q.shape != d.shape:
+        raise RuntimeError("depth and prior must be [H, W] tensors of the same shape")
+    a = None
+    if alpha is not None:
+        a = alpha.contiguous().float()
+        if a.shape != d.shape or a.device != d.device:
+            raise RuntimeError("alpha must be an [H, W] tensor like depth")
+    v = None
+    if valid is not None:
+        v = valid.contiguous()
+        if v.dtype == torch.bool:
+            v = v.view(torch.uint8)
+        if v.dtype != torch.uint8 or v.shape != d.shape or v.device != d.device:
+            raise RuntimeError("valid must be an [H, W] uint8 or bool tensor on the device of depth")
+    return d, a, q, v
+
+
+def _depth_prior_call(lib, d, a, q, v, weight, flags, alpha_min, with_grads):
+    from . import capi
+    H, W = d.shape
+    fit = torch.empty(4, dtype=torch.float32, device=d.device)
+    grad_d = torch.empty_like(d) if with_grads else None
+    grad_a = torch.empty_like(d) if with_grads and a is not None else None
+    loss = torch.empty(1, dtype=torch.float32, device=d.device) if with_grads else None
+    scratch = torch.empty(int(lib.gsr_depth_prior_scratch_bytes(W, H)), dtype=torch.uint8, device=d.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    args = capi.DepthPriorArgs(W, H, ptr(d), ptr(a), ptr(q), ptr(v), int(flags), float(alpha_min), float(weight),
+                               ptr(grad_d), ptr(grad_a), ptr(loss), ptr(fit))
+    st = lib.gsr_depth_prior_loss(_C.byref(args), scratch.data_ptr(), _rp._stream_ptr(d))
+    capi.check(lib, st, "gsr_depth_prior_loss")
+    return loss, grad_d, grad_a, fit
+
+
+class _DepthPrior(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, alpha, prior, weight, flags, alpha_min, valid):
+        lib = _rp._lib()
+        d, a, q, v = _depth_prior_maps(lib, depth, alpha, prior, valid)
+        loss, grad_d, grad_a, fit = _depth_prior_call(lib, d, a, q, v, weight, flags, alpha_min, True)
+        ctx.has_alpha = a is not None
+        ctx.save_for_backward(*([grad_d, grad_a] if a is not None else [grad_d]))
+        ctx.mark_non_differentiable(fit)
+        return loss[0], fit
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_fit):
+        saved = ctx.saved_tensors
+        return (saved[0] * grad_out, saved[1] * grad_out if ctx.has_alpha else None, None, None, None, None, None)
+
+
+def depth_prior_loss(depth, alpha, prior, weight, inverse=True, pearson=False, alpha_min=0.5, valid=None, return_fit=False):
+    """The monocular depth-prior term of one view (a scalar tensor; differentiable in depth and alpha): depth and alpha are the
+    rendered [H,W] maps (alpha None = all ones), prior the network's [H,W] map, valid an optional [H,W] uint8 / bool mask.
+    inverse: the prior is an inverse depth (compared with alpha / depth); pearson: 1 - correlation instead of the aligned L1.
+    return_fit: (loss, fit) with fit = [s, t, rho, n] on the device."""
+    loss, fit = _DepthPrior.apply(depth, alpha, prior, weight, _depth_prior_flags(inverse, pearson), alpha_min, valid)
+    return (loss, fit) if return_fit else loss
+
+
+def depth_prior_fit(depth, alpha, prior, inverse=True, alpha_min=0.5, valid=None):
+    """fit = [s, t, rho, n] of prior against the rendered maps alone (two launches, no gradient)"""
+    lib = _rp._lib()
+    d, a, q, v = _depth_prior_maps(lib, depth.detach(), None if alpha is None else alpha.detach(), prior, valid)
+    return _depth_prior_call(lib, d, a, q, v, 0.0, _depth_prior_flags(inverse, False), alpha_min, False)[3]
+
+
+def depth_prior_apply(prior, fit, inverse=True, out=None):
+    """The prior in the units of the render it was fitted to (gsr_depth_prior_apply): s q + t, or 1 / (s q + t) with inverse; 0
+    where the prior is invalid or the result is not finite and positive.  out may be prior itself (contiguous float32)."""
+    from . import capi
+    lib = _rp._lib()
+    _rp._check_device(lib, prior, fit)
+    q = prior.detach().contiguous().float()
+    f = fit.detach().contiguous().float()
+    if q.dim() != 2 or f.numel() != 4:
+        raise RuntimeError("depth_prior_apply takes an [H, W] prior and a [4] fit")
+    if out is None:
+        out = torch.empty_like(q)
+    elif out.shape != q.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q.device:
+        raise RuntimeError("depth_prior_apply: out must be a contiguous float32 tensor like prior")
+    st = lib.gsr_depth_prior_apply(q.data_ptr(), f.data_ptr(), _depth_prior_flags(inverse, False), q.size(1), q.size(0),
+                                   out.data_ptr(), _rp._stream_ptr(q))
+    capi.check(lib, st, "gsr_depth_prior_apply")
+    return out

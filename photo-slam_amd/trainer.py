@@ -261,6 +261,16 @@ class TrainStep:
         self.depth_loss_weight_ = 0.0
         self.depth_min_ = 0.0
         self.depth_max_ = float("inf")
+        # Monocular keyframes: trainForOneIteration(..., prior_depth) adds depth_prior_weight_ * the depth-prior term of
+        # loss_utils.depth_prior_loss (include/gsr.h: gsr_depth_prior_loss) on the rendered depth and alpha maps: the aligned L1
+        # after a per-frame scale-and-shift fit, or 1 - Pearson correlation with depth_prior_pearson_; depth_prior_inverse_: the
+        # prior is an inverse depth (MiDaS / Depth Anything); pixels with alpha < depth_prior_alpha_min_ take no part.
+        # 0 = off, prior_depth ignored.  last_depth_prior_fit_: [s, t, rho, n] of the last step with the term (device), else None.
+        self.depth_prior_weight_ = 0.0
+        self.depth_prior_pearson_ = False
+        self.depth_prior_inverse_ = True
+        self.depth_prior_alpha_min_ = 0.5
+        self.last_depth_prior_fit_ = None
         # Per-keyframe exposure compensation (upstream 3DGS's per-image exposure): a keyframe that carries exposure_ -- a [3,4]
         # affine colour map -- has it applied between render and loss, inside the loss kernels (gsr_l1_ssim_loss_exposure), in
         # trainForOneIteration and refinePose.  optimize_exposure_: the keyframe of a train step gets the identity at first use
@@ -438,6 +448,21 @@ class TrainStep:
                 self.gaussians_.prunePoints(mask)
         return n
 
+    def alignDepthPrior(self, viewpoint_cam, prior, valid=None):
+        """A monocular network's relative [H,W] map in the units of the map: one forward-only render with its depth and alpha maps
+        (render_view), the scale-and-shift fit of the depth-prior loss against it (depth_prior_inverse_, depth_prior_alpha_min_),
+        then gsr_depth_prior_apply.  Returns (metric [H,W] map -- 0 where the prior is invalid --, fit = [s, t, rho, n] on the
+        device); the map is what seedFromDepth takes as gt_depth.  A degenerate fit (include/gsr.h) gives an all-zero map, which
+        seeds nothing.  An empty model has no render to align to: that throws."""
+        g = self.gaussians_
+        if getattr(g, "xyz_", None) is None or int(g.xyz_.shape[0]) == 0:
+            raise RuntimeError("TrainStep: alignDepthPrior needs a render to align to, and the model is empty "
+                               "(seed the first frame from a metric depth map)")
+        _, depth, alpha = self.render_view(viewpoint_cam, with_depth=True)
+        fit = loss_utils.depth_prior_fit(depth, alpha, prior, inverse=self.depth_prior_inverse_,
+                                         alpha_min=self.depth_prior_alpha_min_, valid=valid)
+        return loss_utils.depth_prior_apply(prior, fit, inverse=self.depth_prior_inverse_), fit
+
     def seedFromDepth(self, viewpoint_cam, gt_image, gt_depth, iteration, want_pixels=False):
         """The mapper's "where does the map fail to explain this frame, and what do I put there" step (SplaTAM's add_new_gaussians,
         MonoGS's unexplored-region insertion): one forward-only render of the map with its depth and alpha maps (render_view; none
@@ -553,14 +578,20 @@ class TrainStep:
                 entry = cache[id(mask)] = (weakref.ref(mask), mask._version, bool((mask == 1).all().item()))
         return None if entry[2] else mask
 
-    def trainForOneIteration(self, viewpoint_cam, gt_image, mask, sync_loss=True, position_lr_step=None, gt_depth=None):
+    def trainForOneIteration(self, viewpoint_cam, gt_image, mask, sync_loss=True, position_lr_step=None, gt_depth=None,
+                             prior_depth=None):
         """position_lr_step: the step of the position learning-rate schedule -- None = the iteration (src/gaussian_mapper.cpp:672-674,
         the COLMAP flavour); a SLAM session passes the keyframe's use count (:663-671, capped at position_lr_max_steps_).
         gt_depth: the keyframe's [H,W] sensor depth (an RGB-D session's img_auxiliary_undist_); with depth_loss_weight_ != 0 the
-        depth L1 loss joins the RGB loss before the one backward pass (its gradient reaches the positions through the depth map)."""
+        depth L1 loss joins the RGB loss before the one backward pass (its gradient reaches the positions through the depth map).
+        prior_depth: a monocular network's relative [H,W] map of the keyframe; with depth_prior_weight_ != 0 the depth-prior term
+        joins the loss in the same way (through the depth AND alpha maps); both may be given."""
         use_depth = gt_depth is not None and self.depth_loss_weight_ != 0.0
         if use_depth and self.world_size_ > 1:
             raise RuntimeError("TrainStep: the depth loss is not supported with a process group (depth_loss_weight_ must be 0)")
+        use_prior = prior_depth is not None and self.depth_prior_weight_ != 0.0
+        if use_prior and self.world_size_ > 1:
+            raise RuntimeError("TrainStep: the depth prior is not supported with a process group (depth_prior_weight_ must be 0)")
         exposure = self._exposure_of(viewpoint_cam, create=self.optimize_exposure_)
         if exposure is not None and self.world_size_ > 1:
             raise RuntimeError("TrainStep: exposure compensation is not supported with a process group")
@@ -576,6 +607,7 @@ class TrainStep:
                             lambda_isotropic=float(self.isotropic_reg_),
                             loss=torch.zeros(3, dtype=torch.float32, device=g.xyz_.device) if sync_loss else None)
         self.last_reg_losses = None
+        self.last_depth_prior_fit_ = None
         if self.absgrad_ and self.world_size_ > 1:
             raise RuntimeError("TrainStep: absgrad_ is not supported with a process group")
         if self.filter3d_:
@@ -627,7 +659,7 @@ class TrainStep:
                 sh_grad_view=sh_view, sh_adam=fwd_adam, view_stats=view_stats, geom_adam=geom_adam,
                 training_outputs_only=True,   # the statistics are fused (or over): nobody reads the viewspace gradient
                 cull_empty_tiles=self.cull_empty_tiles_, workspace=self.workspace_ if self.persistent_workspace_ else None,
-                render_depth=use_depth, antialiasing=self.antialiasing_, geom_reg=geom_reg,
+                render_depth=use_depth or use_prior, antialiasing=self.antialiasing_, geom_reg=geom_reg,
                 absgrad=bool(self.absgrad_) and view_stats is not None,   # (only the statistics read it)
                 filter_3D=self.viewFilter3D(recompute=bool(self.filter3d_interval_) and it % int(self.filter3d_interval_) == 0))
             rendered_image, viewspace_point_tensor, visibility_filter, radii = out[:4]
@@ -641,6 +673,11 @@ class TrainStep:
                                              exposure=exposure_leaf)
         if use_depth:   # (the sum's backward hands both terms the root's exact 1: is_root stays valid)
             loss = loss + loss_utils.depth_l1_loss(out[4], gt_depth, self.depth_loss_weight_, self.depth_min_, self.depth_max_)
+        if use_prior:
+            prior_loss, self.last_depth_prior_fit_ = loss_utils.depth_prior_loss(
+                out[4], out[5], prior_depth, self.depth_prior_weight_, inverse=self.depth_prior_inverse_,
+                pearson=self.depth_prior_pearson_, alpha_min=self.depth_prior_alpha_min_, return_fit=True)
+            loss = loss + prior_loss
         # :699 (the root gradient: a cached 1 instead of the ones_like fill autograd launches per backward())
         if getattr(self, "_root_grad", None) is None or self._root_grad.device != loss.device:
             self._root_grad = torch.ones_like(loss).detach()
